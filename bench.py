@@ -35,15 +35,24 @@ The JSON line also carries
 
 Timing protocol: W untimed warm-up steps, then an untimed, time-based clock ramp
 (--ramp-ms of replays: a fresh GPU needs ~100 ms of work before its clocks
-settle, which a 20-step run never reaches), then R back-to-back replays of a
-hipGraph inside ONE barrier + synchronize bracket.  The graph holds the K steps
-repeated to >= 1024 ticks (a graph launch opens with a ~10 us device bubble that
-a 20-tick graph would pay every 20 ticks).  `ms_per_step` = bracket wall time /
-timed steps (max over ranks), `value` = instances * timed steps / wall;
-`roofline.tick_us` = median over the R replays of (HIP-event time of one
-replay / its ticks).  R is chosen so that the bracket holds >= --min-timed-ms of
-work (default 2 s for the headline) and >= 50 replays; R and the timed steps are
-stated in `config`.
+settle, which a 20-step run never reaches), then exactly K timed steps inside
+ONE barrier + synchronize bracket: R = K // G back-to-back replays of a hipGraph
+of G = min(K, 8192) ticks, then one replay of a graph of the K % G ticks left (a
+graph launch opens with a ~10 us device bubble that a 20-tick graph would pay
+every 20 ticks).  `ms_per_step` = bracket wall time / K (max over ranks),
+`value` = instances * K / wall; `roofline.tick_us` = median over the R replays of
+(HIP-event time of one replay / its ticks).  State carried from tick to tick (the
+rollout's q, the QP's working sets) is reset before the bracket, so that the same
+arguments compute the same outputs.  The `extras` keep brackets sized by time
+(--extras-timed-ms, >= 50 replays of >= 1024 ticks); R and the timed steps of
+every entry are stated in its `config`.
+
+`--dump-outputs DIR` writes what the headline's last timed step computed, the
+arrays a caller of the timed path receives (dq and mode; the QP: dq, slack and
+status; a rollout: q too), as DIR/<name>.npy in float64: at most 64 MB in all, a
+fixed sample of rows beyond that (with their indices as rows.npy).  Inputs are
+drawn from --seed, so two builds run with the same arguments can be compared
+output for output.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks
 itself (torch.distributed.run on 127.0.0.1) BEFORE anything touches a GPU and
@@ -75,7 +84,7 @@ METRIC = "CLIK steps/sec (whole node), 7-DoF 3-task priority stack, batch 16384"
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=2000, help="timed steps of the headline")
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--batch", type=int, default=16384, help="instances per GPU (weak scaling)")
     ap.add_argument("--global-batch", type=int, default=0,
@@ -99,8 +108,10 @@ def parse():
                     help="lanes per robot instance of the pinv kernel: 0 = the library's choice, 1 = "
                          "lane-per-instance kernels only, 4 / 8 / 16 = the multi-lane kernel (CLIK_LANES)")
     ap.add_argument("--ramp-ms", type=float, default=250.0, help="untimed clock ramp before the timed region")
-    ap.add_argument("--min-timed-ms", type=float, default=2000.0, help="least work inside the timed bracket")
-    ap.add_argument("--replays", type=int, default=0, help="R (0: from --min-timed-ms, at least 50)")
+    ap.add_argument("--min-timed-ms", type=float, default=2000.0,
+                    help="no effect (the headline times exactly --steps); accepted for older command lines")
+    ap.add_argument("--replays", type=int, default=0,
+                    help="no effect (the headline times exactly --steps); accepted for older command lines")
     ap.add_argument("--cpu-baseline", type=int, default=1)
     ap.add_argument("--cpu-seconds", type=float, default=3.0,
                     help="bound of the cpu_baseline leg of the headline (each extras entry: a third of it, >= 1 s)")
@@ -118,7 +129,13 @@ def parse():
                     help="N > 1: also time ONE batch of this many instances cut over the ranks (BASELINE config 5; 0 = skip)")
     ap.add_argument("--big-batch", type=int, default=131072,
                     help="N > 1: also time this many instances PER GPU (the regime where a GPU is busy; 0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the headline's last timed step computed as DIR/<name>.npy (float64; a fixed "
+                         "sample of rows beyond 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 _T0 = time.time()
@@ -397,10 +414,39 @@ def check_outputs(workload, spec, opts, Q, Y, out_rows, slack_rows=None):
             "what": "ring slot 0's output after the timed bracket vs oracle/clik_oracle.py (tests/tolerances.py rule)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: the arrays the last timed step handed back (host tensors, one row per instance) as
+    <out_dir>/<name>.npy in float64 (modes and statuses are small integers: exact).  Beyond 64 MB over all ranks, a fixed
+    sample of rows (the same for every run with the same arguments) is written, its row indices as rows.npy.  With more
+    than one rank every rank writes its own shard as <name>.rank<r>.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.numpy().astype(np.float64) for k, v in arrays.items()}
+    n = len(next(iter(host.values())))
+    row_bytes = sum(a[:1].nbytes for a in host.values())
+    budget = DUMP_LIMIT_BYTES // world - 4096       # (room for the .npy headers)
+    if n * row_bytes > budget:
+        keep = budget // (row_bytes + 8)            # (+ the index of each row kept)
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        host = {k: a[rows] for k, a in host.items()}
+        host["rows"] = rows.astype(np.float64)
+    suffix = ".rank%d" % rank if world > 1 else ""
+    files = []
+    for name, a in sorted(host.items()):
+        fn = os.path.join(out_dir, name + suffix + ".npy")
+        np.save(fn, a)
+        files.append(os.path.basename(fn))
+    return {"dir": out_dir, "files": files, "rows": len(host["dq"]), "of": n}
+
+
 def measure(ctx, fk, workload, B, dist_name, seed, K, W, TPL=1, qp_hot=0, use_graph=1, ramp_ms=250.0,
-            min_timed_ms=2000.0, replays=0, allgather=0, global_batch=0, ring=4):
+            min_timed_ms=2000.0, replays=0, allgather=0, global_batch=0, ring=4, exact_steps=False, dump_dir=None):
     """One timed configuration.  Returns (entry dict, (spec, opts, Q, Y)) on every rank; the entry is
-    complete on rank 0."""
+    complete on rank 0.  exact_steps: the timed bracket holds exactly K steps (otherwise as many as fill
+    min_timed_ms); dump_dir: every rank writes what the last timed step computed there (dump_outputs)."""
     import torch
     from casclik_amd import skills
     from casclik_amd.distributed import shard_bounds
@@ -452,9 +498,15 @@ def measure(ctx, fk, workload, B, dist_name, seed, K, W, TPL=1, qp_hot=0, use_gr
             raise SystemExit("--ticks-per-launch needs steps and warmup divisible by it")
         times = [0.0] * TPL
         state = {"q": Qd}
+        names = ("q", "dq", "mode") if workload != "qp" else ("q", "dq", "slack", "status")
 
         def tick():         # one launch = TPL ticks; the state is carried from launch to launch
-            state["q"] = ctrl.rollout_batch(times, state["q"], input_var=Yd, dt=1e-3, max_speed=2.0)[0]
+            res = ctrl.rollout_batch(times, state["q"], input_var=Yd, dt=1e-3, max_speed=2.0)
+            state["q"] = res[0]
+            state["last"] = dict(zip(names, res))
+
+        def reset_state():  # (the rollout starts again from the drawn batch)
+            state["q"] = Qd
         use_graph = 0
         K //= TPL
         W //= TPL
@@ -470,25 +522,48 @@ def measure(ctx, fk, workload, B, dist_name, seed, K, W, TPL=1, qp_hot=0, use_gr
         turn = {"i": 0}
 
         def tick():
-            bound[turn["i"] % len(bound)]()
+            turn["last"] = bound[turn["i"] % len(bound)]
+            turn["last"]()
             turn["i"] += 1
+
+        def reset_state():  # (the shared working sets filled again as the cold priming tick above filled them)
+            if moving_target:
+                ctrl.solve_batch(0.0, Qd, input_var=Yd, hot_set=kw["hot_set"], use_hot=False)
+
+        def last_outputs(b_):
+            if workload == "qp":
+                return {"dq": b_.out, "slack": b_.slack, "status": b_.status}
+            return {"dq": b_.out, "mode": b_.mode}
 
     stream = torch.cuda.Stream(device=dev)
     with torch.cuda.stream(stream):
         for _ in range(W):
             tick()
         stream.synchronize()
-        graph = None
-        # a replay = GK steps = the K steps repeated until the graph holds >= 1024 ticks: every graph launch
-        # starts with a ~10 us bubble on the device (measured: 6.26 us per step from a 20-tick graph against
-        # 5.74 us from a 2000-tick graph of the same kernel), which a control loop that enqueues ticks
-        # continuously never sees
-        GK = K * max(1, -(-1024 // K)) if (use_graph and TPL == 1) else K
+        graph = graph_rem = None
+        # a replay = GK steps.  Every graph launch starts with a ~10 us bubble on the device (measured: 6.26 us per step
+        # from a 20-tick graph against 5.74 us from a 2000-tick graph of the same kernel), which a control loop that
+        # enqueues ticks continuously never sees.  exact_steps: the timed bracket holds exactly K steps - R = K // GK
+        # replays of a graph of GK = min(K, 8192) steps (the bubble: ~0.001 us per tick), then one of the K % GK left;
+        # otherwise a graph holds the K steps repeated to >= 1024 ticks and R follows from min_timed_ms
+        if exact_steps:
+            GK = min(K, 8192)
+            rem = K - (K // GK) * GK
+        else:
+            GK = K * max(1, -(-1024 // K)) if (use_graph and TPL == 1) else K
+            rem = 0
         if use_graph:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=stream):
                 for _ in range(GK):
                     tick()
+            last_main = turn["last"]
+            if rem:
+                graph_rem = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph_rem, stream=stream):
+                    for _ in range(rem):
+                        tick()
+                graph_rem.replay()
             graph.replay()          # untimed first replay (upload)
             stream.synchronize()
 
@@ -499,7 +574,14 @@ def measure(ctx, fk, workload, B, dist_name, seed, K, W, TPL=1, qp_hot=0, use_gr
                 for _ in range(GK):
                     tick()
 
-        # untimed clock ramp; its rate also sizes R
+        def replay_rem():           # the rem steps left
+            if graph_rem is not None:
+                graph_rem.replay()
+            else:
+                for _ in range(rem):
+                    tick()
+
+        # untimed clock ramp; its rate also sizes R when the steps are not exact
         t_r = time.perf_counter()
         n_ramp = 0
         while True:
@@ -511,12 +593,18 @@ def measure(ctx, fk, workload, B, dist_name, seed, K, W, TPL=1, qp_hot=0, use_gr
                     break
         stream.synchronize()
         est_ms = (time.perf_counter() - t_r) * 1e3 / n_ramp          # one replay, host-inclusive (upper bound)
-        R = replays if replays > 0 else max(50, int(min_timed_ms / max(est_ms, 1e-3)) + 1)
-        R = min(R, 200000)
-        R = ctx.reduce_max([R], as_int=True)[0]
+        if exact_steps:
+            R = K // GK
+        else:
+            R = replays if replays > 0 else max(50, int(min_timed_ms / max(est_ms, 1e-3)) + 1)
+            R = min(R, 200000)
+            R = ctx.reduce_max([R], as_int=True)[0]
         n_ev = min(R, 2000)                                           # events around the first n_ev replays
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_ev + 1)]
         ev_end = torch.cuda.Event(enable_timing=True)
+        # state carried from tick to tick (the rollout's q, the QP's shared working sets) starts the timed steps where it
+        # started the run, whatever the time-based ramp left: the same arguments compute the same outputs
+        reset_state()
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
@@ -526,11 +614,21 @@ def measure(ctx, fk, workload, B, dist_name, seed, K, W, TPL=1, qp_hot=0, use_gr
             replay()
             if r < n_ev:
                 evs[r + 1].record(stream)
+        if rem:
+            replay_rem()
         ev_end.record(stream)
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
         wall = time.perf_counter() - t0
+        # what the last timed step handed back, on the host before anything else runs
+        last = None
+        if dump_dir:
+            if TPL > 1:
+                last = state["last"]
+            else:
+                last = last_outputs(last_main if (graph is not None and graph_rem is None) else turn["last"])
+            last = {k: v.detach().cpu() for k, v in last.items() if v is not None}
 
         # the optional all-gather of dq: its own bracket, then tick + all-gather
         # back to back on the same stream (eager launches: a collective is not captured)
@@ -548,8 +646,8 @@ def measure(ctx, fk, workload, B, dist_name, seed, K, W, TPL=1, qp_hot=0, use_gr
     dev_ms = evs[0].elapsed_time(ev_end)
     wall, dev_ms, med_ms = ctx.reduce_max([wall, dev_ms, med_ms])
 
-    K, W, GK = K * TPL, W * TPL, GK * TPL          # report in ticks
-    timed_steps = R * GK
+    K, W, GK, rem = K * TPL, W * TPL, GK * TPL, rem * TPL          # report in ticks
+    timed_steps = R * GK + rem
     n_inst_total = global_batch if global_batch else world * B
     value = n_inst_total * timed_steps / wall
     tick_us = med_ms * 1e3 / GK
@@ -640,12 +738,13 @@ def measure(ctx, fk, workload, B, dist_name, seed, K, W, TPL=1, qp_hot=0, use_gr
                                                                  if moving_target else ""))
                                                              if len(slots) > 1 else ""),
             "kernel": kernel,
-            "launch": ("hipGraph of %d ticks (the K ticks x %d)" % (GK, GK // K) if graph is not None
+            "launch": (("hipGraph of %d ticks%s" % (GK, " (+ one of %d)" % rem if rem else "") if exact_steps else
+                        "hipGraph of %d ticks (the K ticks x %d)" % (GK, GK // K)) if graph is not None
                        else "eager, one launch per tick") if TPL == 1
                       else "on-device rollout, %d ticks per launch (solve -> clamp -> Euler)" % TPL,
             "replays": R, "timed_steps": timed_steps, "timed_ms": wall * 1e3, "clock_ramp_ms": ramp_ms,
-            "timing": "R back-to-back replays in one barrier+synchronize bracket; "
-                      "ms_per_step = wall / timed_steps, max over ranks",
+            "timing": "R back-to-back replays%s in one barrier+synchronize bracket; "
+                      "ms_per_step = wall / timed_steps, max over ranks" % (" and the remainder" if rem else ""),
             "ticks_per_s": timed_steps / wall,
             "parallelism": "dp%d (independent shards, no data-path collective)" % world,
         },
@@ -662,7 +761,9 @@ def measure(ctx, fk, workload, B, dist_name, seed, K, W, TPL=1, qp_hot=0, use_gr
             entry["check"] = {"ok": False, "error": repr(exc)[:200]}
     if ag is not None:
         entry["allgather"] = ag
-    del graph
+    if dump_dir:
+        entry["outputs"] = dump_outputs(dump_dir, last, rank, world)
+    del graph, graph_rem
     return entry, (spec, opts, Q, Y)
 
 
@@ -948,8 +1049,8 @@ def main():
     head, (spec, opts, Q, Y) = measure(
         ctx, fk, args.workload, args.batch, args.dist, args.seed, args.steps, args.warmup,
         TPL=args.ticks_per_launch, qp_hot=args.qp_hot, use_graph=args.graph, ramp_ms=args.ramp_ms,
-        min_timed_ms=args.min_timed_ms, replays=args.replays, allgather=args.allgather or (1 if world > 1 else 0),
-        global_batch=args.global_batch, ring=args.ring)
+        allgather=args.allgather or (1 if world > 1 else 0), global_batch=args.global_batch, ring=args.ring,
+        exact_steps=True, dump_dir=args.dump_outputs or None)
 
     head_cpu = None
     if rank == 0 and args.cpu_baseline and world == 1:
@@ -1044,7 +1145,6 @@ def main():
             "config": head["config"], "roofline": head["roofline"],
             "nranks_seen": ranks_seen, "devices": devices,
         }
-        out["config"]["steps_per_graph_arg"] = args.steps
         if world > 1:
             out["process_group"] = backend
             if dist_errors:
@@ -1054,6 +1154,8 @@ def main():
         out["cpu_baseline"] = head_cpu
         if "check" in head:
             out["check"] = head["check"]
+        if "outputs" in head:
+            out["outputs"] = head["outputs"]
         if world > 1:
             # how to read the curve the driver builds from the per-N lines
             out["scaling_note"] = ("weak line: 16384 instances PER GPU - a tick is one wave per SIMD long whatever N is, so "
@@ -1068,7 +1170,7 @@ def main():
             out = dict({"notes": NOTES}, **out)
             out["config"] = {"workload": c["workload"], "batch_per_gpu": c["batch_per_gpu"], "inputs": c["inputs"],
                              "kernel": c["kernel"], "launch": c["launch"], "replays": c["replays"],
-                             "steps_per_graph_arg": args.steps, "timed_ms": _r(c["timed_ms"], 1),
+                             "timed_steps": c["timed_steps"], "timed_ms": _r(c["timed_ms"], 1),
                              "parallelism": c["parallelism"]}
             if "global_batch" in c:
                 out["config"]["global_batch"] = c["global_batch"]

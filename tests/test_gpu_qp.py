@@ -1050,10 +1050,11 @@ def test_resident_qp_ticks(iiwa_fk):
     """Round 5 (VERDICT r4 missing 3): resident ticks of the ReactiveQPController (clik_qp_resident_run,
     qp_resident_box_front4_kernel): ONE launch solves tick k's QP whenever ticket k is published; every instance's working
     set stays in the kernel, so every tick after the first is hot-started as the reference's qpOASES instance is
-    (reactive_qp.py:491-513).  (a) four ticks fed one by one from the host with fresh targets: statuses equal and
-    minimisers equal (to rounding: another instantiation, another start) to an ordinary launch on the same inputs, and
-    the oracle's within the rule on the last tick; (b) a ring of four slots with every ticket published ahead."""
-    import time
+    (reactive_qp.py:491-513).  (a) four ticks one at a time with fresh targets: a closed loop - the producer publishes
+    ticket k only once every wave has finished tick k - 1, so the kernel polls for each ticket -, the targets of tick k in
+    slot k - 1 of a ring as deep as the run, the same instances in every slot: statuses equal and minimisers equal (to
+    rounding: another instantiation, another start) to an ordinary launch on the same inputs, and the oracle's within the
+    rule on the last tick; (b) a ring of four slots with every ticket published ahead."""
     import torch
     from oracle import clik_oracle
     spec = skills.qp_skill(iiwa_fk)
@@ -1068,38 +1069,26 @@ def test_resident_qp_ticks(iiwa_fk):
     Ys = [skills.synthetic_inputs(iiwa_fk, B, seed=30 + k, distribution="mixed")[1] for k in range(NT)]
     Qd = dev(Q)
     want = [ctrl.solve_batch(0.0, Qd, input_var=dev(Yk), use_hot=False) for Yk in Ys]
-    Yd = torch.zeros((B, 7), dtype=torch.float64, device="cuda")
+    # (every input in place before the launch, and nothing enqueued by the host while the kernel runs: a copy or a
+    # read-back on a stream the runtime has put on the resident kernel's hardware queue waits until its watchdog lets it
+    # go - seen in the long test run, never in this test alone)
+    Qr = torch.stack([Qd] * NT).contiguous()
+    Yr = torch.stack([dev(y) for y in Ys]).contiguous()
     torch.cuda.synchronize()
-    run = ctrl.resident_start(Qd, Yd, NT, timeout_s=30.0)
-    feed = ctrl.resident_feed_stream()       # (a stream that makes progress beside the resident kernel)
+    run = ctrl.resident_start(Qr, Yr, NT, timeout_s=30.0, ring_depth=NT)
     assert run["waves"] == (B + 15) // 16
-    try:
-        for k in range(1, NT + 1):
-            with torch.cuda.stream(feed):
-                Yd.copy_(dev(Ys[k - 1]))
-                run["ticket"][0:1].copy_(torch.tensor([k], dtype=torch.int32))
-            feed.synchronize()
-            t0 = time.time()
-            while True:
-                with torch.cuda.stream(feed):
-                    tk, dn = run["ticket"].cpu(), run["done"].cpu()
-                if int(dn.min()) >= k or int(tk[32]) != 0 or time.time() - t0 > 25.0:
-                    break
-                time.sleep(0.001)
-            assert int(tk[32]) == 0 and int(dn.min()) == k and int(dn.max()) == k, (k, tk[[0, 32, 48, 49]].tolist())
-            with torch.cuda.stream(feed):
-                got, gsl, gst = run["out"].cpu().numpy(), run["slack"].cpu().numpy(), run["status"].cpu().numpy()
-            feed.synchronize()
-            wdq, wsl, wst = want[k - 1][0].cpu().numpy(), want[k - 1][2].cpu().numpy(), want[k - 1][3].cpu().numpy()
-            assert np.array_equal(gst, wst), k
-            good = wst == 0
-            assert _rel(got[good], wdq[good]).max() < 1e-8 and _rel(gsl[good], wsl[good]).max() < 1e-8, k
-    finally:
-        with torch.cuda.stream(feed):
-            run["ticket"][32:33].copy_(torch.tensor([1], dtype=torch.int32))
-        feed.synchronize()
-        run["stream"].synchronize()
-    assert int(run["ticket"].cpu()[49]) == NT
+    feeder = ctrl.resident_feed(run, NT, closed_loop=True, timeout_s=30.0)
+    run["stream"].synchronize()
+    feeder.synchronize()
+    tk = run["ticket"].cpu()
+    assert int(tk[32]) == 0 and int(tk[49]) == NT and int(run["done"].min()) == NT == int(run["done"].max()), \
+        tk[[0, 32, 48, 49]].tolist()
+    for k in range(1, NT + 1):
+        got, gsl, gst = run["out"][k - 1].cpu().numpy(), run["slack"][k - 1].cpu().numpy(), run["status"][k - 1].cpu().numpy()
+        wdq, wsl, wst = want[k - 1][0].cpu().numpy(), want[k - 1][2].cpu().numpy(), want[k - 1][3].cpu().numpy()
+        assert np.array_equal(gst, wst), k
+        good = wst == 0
+        assert _rel(got[good], wdq[good]).max() < 1e-8 and _rel(gsl[good], wsl[good]).max() < 1e-8, k
     n = 300
     rdq, _, rslack, rstatus = clik_oracle.qp_solve_batch(spec, 0.0, Q[:n], Y=Ys[-1][:n])
     assert np.array_equal(gst[:n], rstatus)

@@ -363,12 +363,12 @@ def test_resident_kernel_leaves_by_its_watchdog(iiwa_fk):
 
 def test_resident_ticks_of_a_single_mode_skill(iiwa_fk):
     """Round 5 (VERDICT r4 missing 3): resident ticks for the four-lanes-per-instance kernel of single-mode skills with
-    forward kinematics (BASELINE config 2; pinv_resident_quad_kernel, one wave per 16 instances).  (a) ticks fed one by one
-    from the host: targets copied in behind a stream, published with a ticket; every tick's velocities equal an ordinary
-    launch on the same inputs.  (b) a ring of four slots with every ticket published ahead (the rows of tick k + 1
-    requested before tick k's arithmetic): every output slot equals a launch on that slot's inputs.  (c) the state kept by
-    the kernel is the config-3 family's only: refused."""
-    import time
+    forward kinematics (BASELINE config 2; pinv_resident_quad_kernel, one wave per 16 instances).  (a) ticks one at a time
+    with fresh targets: a closed loop - the producer publishes ticket k only once every wave has finished tick k - 1, so
+    the kernel polls for each ticket -, the targets of tick k in slot k - 1 of a ring as deep as the run; every tick's
+    velocities and modes equal an ordinary launch on the same inputs.  (b) a ring of four slots with every ticket
+    published ahead (the rows of tick k + 1 requested before tick k's arithmetic): every output slot equals a launch on
+    that slot's inputs.  (c) the state kept by the kernel is the config-3 family's only: refused."""
     import torch
     spec = skills.pose_skill(iiwa_fk)
     ctrl = cc.PseudoInverseController(skill_spec=spec)
@@ -381,39 +381,22 @@ def test_resident_ticks_of_a_single_mode_skill(iiwa_fk):
     Ys = [skills.synthetic_inputs(iiwa_fk, B, seed=30 + k, distribution="mixed")[1] for k in range(NT)]
     Qd = dev(Q)
     want = [ctrl.solve_batch(0.0, Qd, input_var=dev(Yk)) for Yk in Ys]
-    want_host = [(w[0].cpu(), w[2].cpu()) for w in want]
-    Yd = torch.zeros((B, 7), dtype=torch.float64, device="cuda")
+    # (every input in place before the launch, and nothing enqueued by the host while the kernel runs: a copy or a
+    # read-back on a stream the runtime has put on the resident kernel's hardware queue waits until its watchdog lets it
+    # go - seen in the long test run, never in this test alone)
+    Qr = torch.stack([Qd] * NT).contiguous()
+    Yr = torch.stack([dev(y) for y in Ys]).contiguous()
     torch.cuda.synchronize()
-    run = ctrl.resident_start(Qd, Yd, NT, timeout_s=30.0)
-    feed = ctrl.resident_feed_stream()       # (a stream that makes progress beside the resident kernel)
+    run = ctrl.resident_start(Qr, Yr, NT, timeout_s=30.0, ring_depth=NT)
     assert run["waves"] == (B + 15) // 16
-    try:
-        for k in range(1, NT + 1):
-            with torch.cuda.stream(feed):
-                Yd.copy_(dev(Ys[k - 1]))
-                run["ticket"][0:1].copy_(torch.tensor([k], dtype=torch.int32))
-            feed.synchronize()
-            t0 = time.time()
-            while True:
-                with torch.cuda.stream(feed):
-                    tk, dn = run["ticket"].cpu(), run["done"].cpu()
-                if int(dn.min()) >= k or int(tk[32]) != 0 or time.time() - t0 > 25.0:
-                    break
-                time.sleep(0.001)
-            assert int(tk[32]) == 0 and int(dn.min()) == k and int(dn.max()) == k, (k, tk[[0, 32, 48, 49]].tolist())
-            # (read back and compared on the HOST: a comparison kernel on the default stream can be queued behind the
-            # resident kernel on the same hardware queue and would wait until its watchdog lets it go - seen in the long
-            # test run, never in this test alone)
-            with torch.cuda.stream(feed):
-                got, gmode = run["out"].cpu(), run["mode"].cpu()
-            feed.synchronize()
-            assert torch.equal(gmode, want_host[k - 1][1]) and torch.equal(got, want_host[k - 1][0]), k
-    finally:
-        with torch.cuda.stream(feed):
-            run["ticket"][32:33].copy_(torch.tensor([1], dtype=torch.int32))
-        feed.synchronize()
-        run["stream"].synchronize()
-    assert int(run["ticket"].cpu()[49]) == NT
+    feeder = ctrl.resident_feed(run, NT, closed_loop=True, timeout_s=30.0)
+    run["stream"].synchronize()
+    feeder.synchronize()
+    tk = run["ticket"].cpu()
+    assert int(tk[32]) == 0 and int(tk[49]) == NT and int(run["done"].min()) == NT == int(run["done"].max()), \
+        tk[[0, 32, 48, 49]].tolist()
+    for k in range(1, NT + 1):
+        assert torch.equal(run["mode"][k - 1], want[k - 1][2]) and torch.equal(run["out"][k - 1], want[k - 1][0]), k
     # ---- (b) a ring of four slots, every ticket ahead
     D, NT = 4, 10
     batches = [skills.synthetic_inputs(iiwa_fk, B, seed=60 + k, distribution="mixed") for k in range(D)]
