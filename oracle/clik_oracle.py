@@ -366,13 +366,20 @@ def _num(val, m):
 
 
 def _gain_apply(gain, vec):
-    """cs.mtimes(gain, vec) for float or square-matrix gains."""
+    """cs.mtimes(gain, vec) for float or square-matrix gains.  A zero entry of a matrix gain is a term the product does
+    not have: with an infinite component of `vec` (a one-sided bound set_max = inf) or a NaN one, only the rows whose
+    gain reads it become non-finite, as in clik_oracle_c.c::gain_apply and the lowered device image (0 * inf would
+    make a NaN bound of a finite row).  Finite `vec`: the plain product, unchanged."""
     if hasattr(gain, "toarray"):
         gain = gain.toarray()
     g = np.asarray(gain, dtype=float)
     if g.ndim == 0 or g.size == 1:
         return float(g.reshape(-1)[0]) * vec
-    return g.dot(vec)
+    vec = np.asarray(vec, dtype=float)
+    if np.isfinite(vec).all():
+        return g.dot(vec)
+    with np.errstate(invalid="ignore"):
+        return np.where(g != 0.0, g * vec[None, :], 0.0).sum(axis=1)
 
 
 def default_pinv_options(opt=None):
@@ -451,6 +458,8 @@ def condition_of(result):
 
 
 def _sym_cond(A):
+    if not np.isfinite(A).all():
+        return float("inf")     # (a poisoned instance: no condition number, and eigvalsh would raise)
     w = np.linalg.eigvalsh(A)
     lo, hi = abs(w[0]), abs(w[-1])
     return float(hi / lo) if lo > 0.0 else float("inf")
@@ -945,15 +954,33 @@ def qp_condition(hdiag, A, lb, ub, x, act_tol=1e-8):
     return kh * float(sv[0] / sv[-1])
 
 
+def qp_nonfinite(hd, A, lb, ub):
+    """[B] bool: the instance's QP data hold a value that is no number or no usable bound - a non-finite entry of H or
+    A, a NaN bound, lb = +inf or ub = -inf (status 3).  -inf / +inf as "no bound" stays legal.  (The
+    solver alone would not see it: an infinite or NaN bound fails `isfinite` and is dropped as "no constraint", which
+    handed out a finite minimiser with status 0.)"""
+    hd, A, lb, ub = (np.asarray(v, dtype=float) for v in (hd, A, lb, ub))
+    bad = ~np.isfinite(hd).all(axis=-1) | ~np.isfinite(A).all(axis=(-2, -1))
+    bad |= (np.isnan(lb) | (lb == np.inf)).any(axis=-1)
+    bad |= (np.isnan(ub) | (ub == -np.inf)).any(axis=-1)
+    return bad
+
+
 def qp_solve_batch(spec, t, Q, X=None, Y=None, weights=None, mu=0.001, cond_out=None, _wrong=None):
     """Literal ReactiveQPController.solve: (dq [B,nq], dx [B,nx] | None,
-    slack [B,ns] | None, status [B]).  `cond_out` [B]: qp_condition of every solved instance."""
+    slack [B,ns] | None, status [B]).  `cond_out` [B]: qp_condition of every solved instance.  Status: 0 optimal,
+    2 infeasible, 3 non-finite problem data (`qp_nonfinite`); the rows of 2 and 3 are NaN."""
     hd, A, lbA, ubA = qp_data_batch(spec, t, Q, X, Y, weights, mu, _wrong)
     B, nv = hd.shape
     xs = np.zeros((B, nv))
     status = np.zeros(B, dtype=np.int32)
     kappa = np.ones(B)
+    poisoned = qp_nonfinite(hd, A, lbA, ubA)
     for b in range(B):
+        if poisoned[b]:
+            status[b] = 3
+            xs[b] = np.nan
+            continue
         try:
             xs[b] = qp_solve_dense(hd[b], A[b], lbA[b], ubA[b])
             kappa[b] = qp_condition(hd[b], A[b], lbA[b], ubA[b], xs[b])

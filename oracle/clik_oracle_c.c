@@ -232,13 +232,22 @@ static double row_eval(const clik_skill_desc* d, const clik_row* r, const kin_t*
     int n = d->n_q + d->n_x;
     double v = r->c;
     *dt = 0.0;
+    /* (a zero coefficient is a term the expression does not have: skipped, so that a NaN / inf in a value the row
+     * does not read stays out of it, as in the reference's expression graph) */
     for (int j = 0; j < n; ++j) grad[j] = r->a[j];
-    for (int j = 0; j < n; ++j) v += r->a[j] * z[j];
+    for (int j = 0; j < n; ++j) if (r->a[j] != 0.0) v += r->a[j] * z[j];
     for (int i = 0; i < 3; ++i) {
-        v += r->b[i] * k->p[i] + r->h[i] * k->o[i];
-        for (int j = 0; j < n; ++j) grad[j] += r->b[i] * k->dp[j][i] + r->h[i] * k->dO[j][i];
+        if (r->b[i] != 0.0) {
+            v += r->b[i] * k->p[i];
+            for (int j = 0; j < n; ++j) grad[j] += r->b[i] * k->dp[j][i];
+        }
+        if (r->h[i] != 0.0) {
+            v += r->h[i] * k->o[i];
+            for (int j = 0; j < n; ++j) grad[j] += r->h[i] * k->dO[j][i];
+        }
     }
     for (int i = 0; i < 9; ++i) {
+        if (r->g[i] == 0.0) continue;
         v += r->g[i] * k->R[i];
         for (int j = 0; j < n; ++j) grad[j] += r->g[i] * k->dR[j][i];
     }
@@ -366,7 +375,9 @@ static void gain_apply(const clik_task* t, const double* v, double* out)
     } else {
         for (int i = 0; i < m; ++i) {
             double s = 0.0;
-            for (int k = 0; k < m; ++k) s += t->gain[i * m + k] * v[k];
+            for (int k = 0; k < m; ++k)         /* (a zero entry is no term: 0 * inf / NaN stays out, as in the
+                                                   numpy oracle's _gain_apply) */
+                if (t->gain[i * m + k] != 0.0) s += t->gain[i * m + k] * v[k];
             out[i] = s;
         }
     }
@@ -756,7 +767,21 @@ static int qp_solve_dense_c(int nv, int nc, const double* hd, const double* A, c
     return 2;
 }
 
+/* status 3: a non-finite entry of H or A, a NaN bound, lb = +inf or ub = -inf.  -inf / +inf as "no
+ * bound" stays legal.  (The solver alone would drop such a bound as "no constraint" and report a finite optimum.) */
+static int qp_nonfinite(int nv, int nc, const double* hd, const double* A, const double* lb, const double* ub)
+{
+    for (int j = 0; j < nv; ++j) if (!isfinite(hd[j])) return 1;
+    for (int i = 0; i < nc * nv; ++i) if (!isfinite(A[i])) return 1;
+    for (int i = 0; i < nc; ++i) {
+        if (isnan(lb[i]) || lb[i] == INFINITY) return 1;
+        if (isnan(ub[i]) || ub[i] == -INFINITY) return 1;
+    }
+    return 0;
+}
+
 /* literal ReactiveQPController.solve (reactive_qp.py:461-528) for a batch: xs [B][nv], status [B] */
+/* status: 0 optimal, 2 infeasible, 3 non-finite problem data; the rows of 2 and 3 are NaN */
 int orc_qp_solve_batch(const clik_skill_desc* d, const clik_qp_opts* o, int64_t B,
                        const double* tterms, const double* q, const double* x, const double* y,
                        double* xs, int32_t* status, int nthreads)
@@ -775,7 +800,7 @@ int orc_qp_solve_batch(const clik_skill_desc* d, const clik_qp_opts* o, int64_t 
     for (int64_t b = 0; b < B; ++b) {
         double Hd[QV_MAX], A[QC_MAX * QV_MAX], lb[QC_MAX], ub[QC_MAX];
         orc_qp_data_batch(d, o, 1, tterms, q + b * nq, x ? x + b * nx : 0, y ? y + b * ny : 0, Hd, A, lb, ub);
-        int st = qp_solve_dense_c(nv, nc, Hd, A, lb, ub, xs + b * nv, 200);
+        int st = qp_nonfinite(nv, nc, Hd, A, lb, ub) ? 3 : qp_solve_dense_c(nv, nc, Hd, A, lb, ub, xs + b * nv, 200);
         status[b] = st;
         if (st) for (int j = 0; j < nv; ++j) xs[b * nv + j] = NAN;
     }

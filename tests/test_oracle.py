@@ -453,3 +453,145 @@ def test_the_tolerance_rule_cannot_pass_without_comparing():
     ok = status == 0
     assert tol.qp_close(rdq.copy(), rdq, rows=ok) and tol.LAST["rule"] == "kappa"
     assert tol.qp_close(rdq[ok].copy(), rdq[ok]) and tol.LAST["rule"] == "ceiling"
+
+
+# ---------------------------------------------------------------- non-finite inputs
+POISON = [np.nan, np.inf, -np.inf]
+
+
+def _poison(Q, Y, rows):
+    """NaN / +inf / -inf into q or into input_var of the instances `rows` (a different component each)"""
+    Q, Y = Q.copy(), Y.copy()
+    for k, b in enumerate(rows):
+        if k % 2 == 0:
+            Q[b, k % Q.shape[1]] = POISON[k % 3]
+        else:
+            Y[b, k % Y.shape[1]] = POISON[k % 3]
+    return Q, Y
+
+
+@pytest.mark.filterwarnings("ignore::RuntimeWarning")
+@pytest.mark.parametrize("name,make,opts,ny", CASES)
+def test_oracles_agree_on_poisoned_pinv_batches(name, make, opts, ny, iiwa_fk):
+    """numpy and C pseudo-inverse oracles on batches with NaN / inf in q or input_var: the same modes and the same
+    finite rows; the clean instances are the answers of the clean batch, bit for bit"""
+    from oracle.c_oracle import CPinvOracle
+    spec = make(iiwa_fk)
+    co = CPinvOracle(spec, opts)
+    Q, Y = skills.synthetic_inputs(iiwa_fk, 48, seed=11, distribution="mixed")
+    Y = Y[:, :ny]
+    rows = [0, 3, 7, 12, 20, 31, 40, 47]
+    Qp, Yp = _poison(Q, Y, rows)
+    ref, rmode = orc.pinv_solve_batch(spec, opts, 0.0, Qp, Y=Yp)
+    dq, _, mode = co.solve_batch(0.0, Qp, Y=Yp)
+    assert np.array_equal(mode, rmode)
+    fin = np.isfinite(ref).all(axis=1)
+    assert np.array_equal(np.isfinite(dq).all(axis=1), fin)
+    assert not fin[rows[::2]].any()                      # (q poisoned: forward kinematics reach every row)
+    assert _rel(dq[fin], ref[fin]).max() < 1e-8
+    clean = np.setdiff1d(np.arange(len(Q)), rows)
+    cref, cmode = orc.pinv_solve_batch(spec, opts, 0.0, Q, Y=Y)
+    assert np.array_equal(ref[clean], cref[clean]) and np.array_equal(rmode[clean], cmode[clean])
+
+
+@pytest.mark.filterwarnings("ignore::RuntimeWarning")
+def test_poisoned_qp_data_is_status_3_in_both_oracles(iiwa_fk):
+    """QP data with a non-finite entry, a NaN bound, lb = +inf or ub = -inf: status 3 and NaN rows in the numpy and the
+    C oracle (before, an infinite or NaN bound was dropped as "no bound" and the answer was finite with status 0);
+    the clean instances are unchanged"""
+    from oracle import c_oracle
+    spec = skills.qp_skill(iiwa_fk)
+    Q, Y = skills.synthetic_inputs(iiwa_fk, 24, seed=4, distribution="mixed")
+    rows = [1, 2, 5, 9, 16, 23]
+    Qp, Yp = _poison(Q, Y, rows)
+    dq, _, slack, status = orc.qp_solve_batch(spec, 0.0, Qp, Y=Yp)
+    cdq, _, cslack, cstatus = c_oracle.CQpOracle(spec).solve_batch(0.0, Qp, Y=Yp)
+    assert np.array_equal(status, cstatus)
+    assert (status[rows] == 3).all() and (np.delete(status, rows) == 0).all()
+    assert np.isnan(dq[rows]).all() and np.isnan(slack[rows]).all() and np.isnan(cdq[rows]).all()
+    clean = np.setdiff1d(np.arange(len(Q)), rows)
+    rdq, _, rslack, _ = orc.qp_solve_batch(spec, 0.0, Q, Y=Y)
+    assert np.array_equal(dq[clean], rdq[clean]) and np.array_equal(slack[clean], rslack[clean])
+    assert np.abs(cdq[clean] - rdq[clean]).max() < 1e-10 and np.abs(cslack[clean] - rslack[clean]).max() < 1e-10
+    # the rule itself, on hand-made data: +-inf as "no bound" stays legal
+    hd, A = np.ones((1, 2)), np.array([[[1.0, 0.0], [0.0, 1.0]]])
+    lb, ub = np.array([[-np.inf, 0.5]]), np.array([[np.inf, 1.0]])
+    assert not orc.qp_nonfinite(hd, A, lb, ub).any()
+    for where, val in (("lb", np.nan), ("lb", np.inf), ("ub", np.nan), ("ub", -np.inf), ("A", np.inf), ("H", np.nan)):
+        h2, A2, l2, u2 = hd.copy(), A.copy(), lb.copy(), ub.copy()
+        {"lb": l2[0], "ub": u2[0], "A": A2[0, 0], "H": h2[0]}[where][1] = val
+        assert orc.qp_nonfinite(h2, A2, l2, u2).all(), (where, val)
+
+
+def _one_set_skill():
+    """q (2), y (1): the set 0.0 <= q0 <= 1.0 (priority 0), then the equality q1 - y0 (priority 1)"""
+    t = cs.MX.sym("t")
+    q = cs.MX.sym("q", 2)
+    y = cs.MX.sym("y", 1)
+    return cc.SkillSpecification("one_set", t, q, input_var=y, constraints=[
+        cc.SetConstraint("box", q[0], set_min=0.0, set_max=1.0, priority=0),
+        cc.EqualityConstraint("track", q[1] - y[0], gain=1.0, priority=1)])
+
+
+@pytest.mark.filterwarnings("ignore::RuntimeWarning")
+def test_cone_semantics_on_nan_read_off_the_reference():
+    """pseudo_inverse.py:161-185 with IEEE compares: `set_min - e < 1e-12` is false for e = NaN, so the 1-D cone test
+    returns `dexpr > 0`, false for a NaN velocity too -> the set-inactive mode is rejected, mode 1 (set active).  A NaN
+    only in a target no set reads leaves an inside set inside (mode 0), the row NaN; outside, the NaN velocity fails the
+    cone test (mode 1).  Both oracles."""
+    from oracle.c_oracle import CPinvOracle
+    spec = _one_set_skill()
+    Q = np.array([[np.nan, 0.2], [0.5, 0.2], [1.5, 0.2], [0.5, 0.2]])
+    Y = np.array([[0.3], [np.nan], [np.nan], [0.3]])
+    for dq, mode in (orc.pinv_solve_batch(spec, None, 0.0, Q, Y=Y), CPinvOracle(spec).solve_batch(0.0, Q, Y=Y)[::2]):
+        assert mode.tolist() == [1, 0, 1, 0]
+        # NaN q0 under an active set with a constant Jacobian: the set only freezes q0, the equality moves q1
+        assert dq[0, 0] == 0.0 and abs(dq[0, 1] - 0.1) < 1e-6
+        assert np.isnan(dq[1]).all() and np.isnan(dq[2]).all() and np.isfinite(dq[3]).all()
+
+
+def test_nonfinite_rows_agree_helper():
+    """tests/tolerances.py::nonfinite_rows_agree: row finiteness must match the oracle's, a non-finite row must be quiet
+    NaN in every component, and the mask it returns selects the rows left for the stated rule"""
+    import tolerances as tol
+    ref = np.array([[1.0, 2.0], [np.nan, np.nan], [np.nan, 0.5], [3.0, 4.0]])
+    good = np.array([[1.0, 2.0], [np.nan, np.nan], [np.nan, np.nan], [3.0, 4.0]])
+    fin = tol.nonfinite_rows_agree(good, ref)
+    assert fin.tolist() == [True, False, False, True]
+    assert tol.qp_close(good, ref, rows=fin)
+    with pytest.raises(AssertionError):
+        tol.nonfinite_rows_agree(np.array([[1.0, 2.0], [0.0, 0.0], [np.nan, np.nan], [3.0, 4.0]]), ref)   # NaN lost
+    with pytest.raises(AssertionError):
+        tol.nonfinite_rows_agree(np.array([[np.nan, 2.0], [np.nan, np.nan], [np.nan, np.nan], [3.0, 4.0]]), ref)
+    with pytest.raises(AssertionError):
+        tol.nonfinite_rows_agree(np.array([[1.0, 2.0], [np.nan, 7.0], [np.nan, np.nan], [3.0, 4.0]]), ref)   # part NaN
+    with pytest.raises(AssertionError):
+        tol.nonfinite_rows_agree(np.array([[1.0, 2.0], [np.inf, np.nan], [np.nan, np.nan], [3.0, 4.0]]), ref)  # an inf
+    assert tol.nonfinite_rows_agree(good, ref, rows=np.array([True, False, False, False])).tolist() == [True, False, False, False]
+
+
+def test_matrix_gain_with_a_one_sided_infinite_bound_is_no_poison():
+    """set_max = inf in one component under a square-matrix gain is "no bound", not non-finite data: the gain's zero
+    entries do not multiply the infinity into the other rows (0 * inf = NaN made a finite row's bound NaN and a clean
+    instance status 3).  Numpy and C oracles agree: status 0 inside, 2 where the speed limits cannot reach the set."""
+    from oracle import c_oracle
+    t = cs.MX.sym("t")
+    q = cs.MX.sym("q", 2)
+    for gain in (np.diag([2.0, 3.0]), cs.DM(np.diag([2.0, 3.0]))):
+        spec = cc.SkillSpecification("one_sided", t, q, constraints=[
+            cc.SetConstraint("box", q, set_min=np.array([-1.0, -1.0]), set_max=np.array([np.inf, 1.0]), gain=gain,
+                             priority=0),
+            cc.VelocitySetConstraint("speed", q, set_min=-np.ones(2), set_max=np.ones(2), priority=1)])
+        Q = np.array([[0.1, 0.2], [2.0, 2.0]])
+        hd, A, lb, ub = orc.qp_data_batch(spec, 0.0, Q)
+        assert not orc.qp_nonfinite(hd, A, lb, ub).any()
+        assert np.isposinf(ub[:, 0]).all() and np.isfinite(ub[:, 1:]).all()
+        dq, _, _, status = orc.qp_solve_batch(spec, 0.0, Q)
+        cdq, _, _, cstatus = c_oracle.CQpOracle(spec).solve_batch(0.0, Q)
+        assert status.tolist() == [0, 2] and cstatus.tolist() == [0, 2]
+        assert np.abs(dq[0] - cdq[0]).max() < 1e-10
+        # and the pseudo-inverse path reads the same gain: finite, and the same in both oracles
+        opts = {"multidim_sets": True}
+        ref, rmode = orc.pinv_solve_batch(spec, opts, 0.0, Q)
+        pdq, _, pmode = c_oracle.CPinvOracle(spec, opts).solve_batch(0.0, Q)
+        assert np.array_equal(rmode, pmode) and np.isfinite(ref).all() and np.abs(pdq - ref).max() < 1e-8

@@ -167,3 +167,22 @@ def worst_over_tol(a, ref, rows=None, kappa=None):
         return float("inf"), float("inf"), int((keep & ~posed).sum())
     err = rel_err(a[posed], ref[posed])
     return float((err / tol[posed]).max()), float(err.max()), int((keep & ~posed).sum())
+
+
+def nonfinite_rows_agree(a, ref, rows=None):
+    """The non-finite rule: row by row, `a` is finite exactly where the oracle's `ref` is, and
+    every non-finite row of `a` is quiet NaN in every component, by bits.  Returns the boolean mask of the rows that
+    are finite in both (within `rows`, when given), for the caller to hand to `pinv_close` / `qp_close` as `rows=`:
+    the poisoned rows are masked out there, not counted as left out."""
+    a, ref = np.atleast_2d(np.asarray(a, dtype=float)), np.atleast_2d(np.asarray(ref, dtype=float))
+    assert a.shape == ref.shape, (a.shape, ref.shape)
+    sel = np.ones(len(ref), dtype=bool) if rows is None else np.asarray(rows, dtype=bool)
+    fin_a, fin_ref = np.isfinite(a).all(axis=1), np.isfinite(ref).all(axis=1)
+    differ = sel & (fin_a != fin_ref)
+    assert not differ.any(), ("row finiteness differs from the oracle's", np.nonzero(differ)[0][:8].tolist())
+    bad = sel & ~fin_a
+    if bad.any():
+        bits = a[bad].view(np.uint64)
+        quiet = (bits & np.uint64(0x7ff8000000000000)) == np.uint64(0x7ff8000000000000)
+        assert quiet.all(), ("a non-finite row that is not quiet NaN in every component", np.nonzero(bad)[0][:8].tolist())
+    return sel & fin_a
