@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: CLIK steps/sec on the 7-DoF 3-task priority stack.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 A *step* is one controller tick over the whole batch resident in HBM (one
 kernel launch per tick per GPU).  `value` = instance-steps per second =
@@ -10,6 +10,13 @@ node), 7-DoF 3-task priority stack, batch 16384" (batch is per GPU: weak
 scaling, as in BASELINE config 5 = 131072 instances over 8 GPUs;
 `--global-batch G` cuts ONE batch of G instances over the ranks instead: strong
 scaling, reported as such).
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed
+steps, --dump-outputs if given, and the JSON line with the headline's roofline.
+`--full` adds everything else: `cpu_baseline`, `check`, `extras` (N = 1), the
+strong and big-batch lines and the all-gather of dq (N > 1).  `--cpu-baseline`,
+`--extras` and `--allgather` set to 0 or 1 override what --full chooses.
+`--long 1` prints the long form of the line instead of the compact one.
 
 The JSON line also carries
   roofline      algorithmic HBM bytes (q 56 B + target 56 B +
@@ -22,9 +29,11 @@ The JSON line also carries
                 of this configuration (with its source); `fp64` is the executed
                 fp64 VALU rate from the PMC passes under profiles/ against the
                 78.6 TF vector peak, and `binds` names the bound that applies
+and with --full
   cpu_baseline  the C restatement of the reference algorithm (oracle/, kind
                 "port") timed on this host's cores on a bounded sample
-  extras        (default N=1 run only) the other BASELINE configurations under
+  check         one output slot of the timed bracket against the numpy oracle
+  extras        (default N=1 headline only) the other BASELINE configurations under
                 the same clock: config 2 (pose, 4096 and 16384), config 4 (QP,
                 16384: cold, and hot-started as the reference's solver is after
                 its first tick), config 3 at the config-5 batch (131072), each with
@@ -95,9 +104,9 @@ def parse():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--graph", type=int, default=1,
                     help="replay the K ticks from one hipGraph (1) or launch eagerly (0)")
-    ap.add_argument("--allgather", type=int, default=0,
-                    help="also time the RCCL all-gather of dq (its own bracket, and tick + all-gather; "
-                         "reported separately, never folded into `value`)")
+    ap.add_argument("--allgather", type=int, default=-1,
+                    help="1: also time the RCCL all-gather of dq (its own bracket, and tick + all-gather; "
+                         "reported separately, never folded into `value`); -1 = with --full on N > 1 GPUs; 0 = never")
     ap.add_argument("--ticks-per-launch", type=int, default=1,
                     help="K > 1: the on-device rollout (K ticks of solve -> clamp -> Euler per launch, "
                          "SURVEY.md 8(d) 'launch-amortised'); steps must be a multiple of K")
@@ -112,7 +121,8 @@ def parse():
                     help="no effect (the headline times exactly --steps); accepted for older command lines")
     ap.add_argument("--replays", type=int, default=0,
                     help="no effect (the headline times exactly --steps); accepted for older command lines")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--cpu-baseline", type=int, default=-1,
+                    help="1: time the C restatement on the host cores (N = 1 only); -1 = with --full; 0 = never")
     ap.add_argument("--cpu-seconds", type=float, default=3.0,
                     help="bound of the cpu_baseline leg of the headline (each extras entry: a third of it, >= 1 s)")
     ap.add_argument("--ring", type=int, default=4,
@@ -120,15 +130,20 @@ def parse():
                          "each; 1 = every tick re-reads the same rows)")
     ap.add_argument("--extras", type=int, default=-1,
                     help="1: append the other BASELINE configurations (see the module text) as `extras`; "
-                         "-1 = only for the default headline invocation on one GPU; 0 = never")
+                         "-1 = with --full, for the default headline invocation only; 0 = never")
     ap.add_argument("--extras-timed-ms", type=float, default=400.0)
-    ap.add_argument("--full", type=int, default=0,
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: cpu_baseline, the check against the "
+                         "oracle, extras (N = 1), the strong and big-batch lines and the all-gather (N > 1)")
+    ap.add_argument("--long", type=int, default=0,
                     help="1: print the long form of the line (every timing detail and source text) instead of the "
                          "compact one; the compact line names where each number comes from by file")
     ap.add_argument("--strong-batch", type=int, default=131072,
-                    help="N > 1: also time ONE batch of this many instances cut over the ranks (BASELINE config 5; 0 = skip)")
+                    help="N > 1 with extras: also time ONE batch of this many instances cut over the ranks (BASELINE "
+                         "config 5; 0 = skip)")
     ap.add_argument("--big-batch", type=int, default=131072,
-                    help="N > 1: also time this many instances PER GPU (the regime where a GPU is busy; 0 = skip)")
+                    help="N > 1 with extras: also time this many instances PER GPU (the regime where a GPU is busy; "
+                         "0 = skip)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="write what the headline's last timed step computed as DIR/<name>.npy (float64; a fixed "
                          "sample of rows beyond 64 MB)")
@@ -443,10 +458,12 @@ def dump_outputs(out_dir, arrays, rank=0, world=1):
 
 
 def measure(ctx, fk, workload, B, dist_name, seed, K, W, TPL=1, qp_hot=0, use_graph=1, ramp_ms=250.0,
-            min_timed_ms=2000.0, replays=0, allgather=0, global_batch=0, ring=4, exact_steps=False, dump_dir=None):
+            min_timed_ms=2000.0, replays=0, allgather=0, global_batch=0, ring=4, exact_steps=False, dump_dir=None,
+            check=True):
     """One timed configuration.  Returns (entry dict, (spec, opts, Q, Y)) on every rank; the entry is
     complete on rank 0.  exact_steps: the timed bracket holds exactly K steps (otherwise as many as fill
-    min_timed_ms); dump_dir: every rank writes what the last timed step computed there (dump_outputs)."""
+    min_timed_ms); dump_dir: every rank writes what the last timed step computed there (dump_outputs);
+    check: rank 0 holds one output slot to the oracle (check_outputs)."""
     import torch
     from casclik_amd import skills
     from casclik_amd.distributed import shard_bounds
@@ -752,7 +769,7 @@ def measure(ctx, fk, workload, B, dist_name, seed, K, W, TPL=1, qp_hot=0, use_gr
     }
     if global_batch:
         entry["config"]["global_batch"] = global_batch
-    if rank == 0 and TPL == 1:
+    if check and rank == 0 and TPL == 1:
         # the bracket's own output (slot 0 holds the answers of the last tick that ran on the drawn batch)
         try:
             torch.cuda.synchronize()
@@ -948,7 +965,8 @@ def compact_entry(e):
 NOTES = ("us = wall per tick; roofline.achieved = ALGORITHMIC bytes (172 B/instance-step, QP 220) / tick vs 8 TB/s, not DRAM traffic "
          "(ticks rotate through --ring buffers; `traffic` = PMC bytes per launch, RECORDED in profiles/r6_counters.json); fp64_frac: executed "
          "flops (PMC) vs 78.6 TF; cpu_M_per_s: C port on cpu_baseline.cores threads (quota_cores: cgroup), a baseline not a "
-         "speed-up; cost model: profiles/r5_tick_cost_model.md, r6_load_placement.md; --full 1: details")
+         "speed-up; cost model: profiles/r5_tick_cost_model.md, r6_load_placement.md; --full: cpu_baseline, check and "
+         "extras; --long 1: details")
 
 
 def device_uuid(index):
@@ -1046,14 +1064,16 @@ def main():
     from casclik_amd import skills
     fk = skills.iiwa()
     phase("headline: %s, %d instances per GPU, %d GPU(s)" % (args.workload, args.batch, world))
+    # (what a plain run leaves out: each of these is on with --full, and an explicit 0 / 1 overrides that)
+    want = lambda opt: opt == 1 or (opt == -1 and args.full)          # noqa: E731
     head, (spec, opts, Q, Y) = measure(
         ctx, fk, args.workload, args.batch, args.dist, args.seed, args.steps, args.warmup,
         TPL=args.ticks_per_launch, qp_hot=args.qp_hot, use_graph=args.graph, ramp_ms=args.ramp_ms,
-        allgather=args.allgather or (1 if world > 1 else 0), global_batch=args.global_batch, ring=args.ring,
-        exact_steps=True, dump_dir=args.dump_outputs or None)
+        allgather=1 if (want(args.allgather) and world > 1) else 0, global_batch=args.global_batch, ring=args.ring,
+        exact_steps=True, dump_dir=args.dump_outputs or None, check=args.full)
 
     head_cpu = None
-    if rank == 0 and args.cpu_baseline and world == 1:
+    if rank == 0 and want(args.cpu_baseline) and world == 1:
         phase("cpu_baseline (C restatement on the host cores)")
         try:
             head_cpu = cpu_baseline(args.workload, spec, opts, Q, Y, args.cpu_seconds)
@@ -1062,9 +1082,9 @@ def main():
 
     default_headline = (args.workload == "stack" and args.batch == 16384 and args.ticks_per_launch == 1
                         and not args.global_batch and not args.qp_hot and not args.lanes and args.graph == 1)
-    want_extras = args.extras == 1 or (args.extras == -1 and default_headline and world == 1)
+    want_extras = args.extras == 1 or (want(args.extras) and default_headline and world == 1)
     extras = []
-    if default_headline and world > 1 and args.extras != 0:
+    if default_headline and world > 1 and want(args.extras):
         # N > 1: next to the weak line (16384 instances per GPU: a tick is one wave per SIMD long whatever N is), the
         # STRONG line BASELINE config 5 names (ONE batch of 131072 cut over the ranks) and the regime in which a GPU is
         # worth a GPU (131072 instances PER GPU); the all-gather of dq is timed apart in each
@@ -1107,7 +1127,7 @@ def main():
                 extras.append({"name": name, "error": repr(exc)})
                 continue
             ent = dict({"name": name, "n_gpus": world, "dtype": "f64"}, **ent)
-            if rank == 0 and args.cpu_baseline and world == 1 and not hot and tpl == 1 and b <= 131072:
+            if rank == 0 and want(args.cpu_baseline) and world == 1 and not hot and tpl == 1 and b <= 131072:
                 try:
                     ent["cpu_baseline"] = cpu_baseline(wl, sp, op, q_, y_, max(1.0, args.cpu_seconds / 3))
                 except Exception as exc:
@@ -1151,7 +1171,8 @@ def main():
                 out["process_group_errors"] = dist_errors
         if "allgather" in head:
             out["allgather"] = head["allgather"]
-        out["cpu_baseline"] = head_cpu
+        if head_cpu is not None:
+            out["cpu_baseline"] = head_cpu
         if "check" in head:
             out["check"] = head["check"]
         if "outputs" in head:
@@ -1160,12 +1181,12 @@ def main():
             # how to read the curve the driver builds from the per-N lines
             out["scaling_note"] = ("weak line: 16384 instances PER GPU - a tick is one wave per SIMD long whatever N is, so "
                                    "value scales ~N by construction (shards are independent, no data-path collective). "
-                                   "The STRONG line of BASELINE config 5 is extras.strong_B131072: one GPU runs 131072 "
+                                   "The STRONG line of BASELINE config 5 is extras.strong_B131072 (--full): one GPU runs 131072 "
                                    "instances in ~9.6 us, eight GPUs at 16384 each take ~3.7 us - expect ~2.6x from 8 GPUs "
                                    "on that batch, not 8x; extras.weak_B131072_per_gpu is the regime where every GPU is full")
         if extras:
             out["extras"] = extras
-        if not args.full:
+        if not args.long:
             c = out["config"]
             out = dict({"notes": NOTES}, **out)
             out["config"] = {"workload": c["workload"], "batch_per_gpu": c["batch_per_gpu"], "inputs": c["inputs"],
@@ -1178,7 +1199,8 @@ def main():
             if "check" in out:
                 out["check"] = {k: out["check"].get(k) for k in ("ok", "instances", "rule", "worst_err_over_tol", "error")
                                 if k in out["check"]}
-            out["cpu_baseline"] = compact_cpu(head_cpu)
+            if head_cpu is not None:
+                out["cpu_baseline"] = compact_cpu(head_cpu)
             out["devices"] = [d.split(" pid ")[0] + " " + d.split(" ", 4)[-1] if " pid " in d else d for d in devices][:8]
             uu = [d.split(" uuid ")[-1] for d in devices if " uuid " in d]
             out["distinct_gpus"] = len(set(uu)) if uu and "unknown" not in uu else None

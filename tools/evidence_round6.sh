@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."
 OUT=gpurun_out/r6ev
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py > $OUT/bench_default_line.json 2> $OUT/bench_default_line.err
+python bench.py --full > $OUT/bench_default_line.json 2> $OUT/bench_default_line.err
 bash tools/profile_round6_launched.sh > $OUT/profile_launched.log 2>&1
 python tools/stamp_body.py 300 --light > $OUT/stamp_body.txt 2>&1
 rm -rf /tmp/prof_moe
@@ -17,6 +17,6 @@ python3 tools/rocprof_summary.py /tmp/prof_moe $OUT/moe_rollout_kernel_stats.csv
 python tools/notebook_bench.py > $OUT/notebook_bench.txt 2> $OUT/notebook_bench.err
 bash tools/floor_probe_r6.sh > $OUT/floor.log 2>&1
 CLIK_BENCH_SHARED_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-    bench.py --gpus 2 --cpu-baseline 0 > $OUT/bench_2ranks_shared_gpu.json 2> $OUT/bench_2ranks_shared_gpu.err
+    bench.py --gpus 2 --full --cpu-baseline 0 > $OUT/bench_2ranks_shared_gpu.json 2> $OUT/bench_2ranks_shared_gpu.err
 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_like.json 2> $OUT/bench_driver_like.err
 ls -la $OUT

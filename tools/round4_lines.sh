@@ -1,6 +1,6 @@
 #!/bin/bash
 # The bench lines kept under profiles/r4_bench_lines.jsonl (one MI355X box, end of round 4), each preceded by its command;
-# `--full 1`: the long form (every entry with its roofline, counters source, cpu_baseline).
+# `--long 1`: the long form (every entry with its roofline, counters source, cpu_baseline).
 #   gpurun -- bash tools/round4_lines.sh        -> gpurun_out/r4lines/
 set -u
 cd "$(dirname "$0")/.."
@@ -10,11 +10,11 @@ mkdir -p $OUT
 line () {   # [ENV=..]... bench args...
     envs=()
     while [[ "${1:-}" == *=* && "${1:-}" != --* ]]; do envs+=("$1"); shift; done
-    echo "# ${envs[*]} python bench.py $*" >> $OUT/r4_bench_lines.jsonl
-    env "${envs[@]}" python bench.py "$@" 2>> $OUT/err.log | grep '^{' | tail -1 >> $OUT/r4_bench_lines.jsonl
+    echo "# ${envs[*]} python bench.py --full $*" >> $OUT/r4_bench_lines.jsonl
+    env "${envs[@]}" python bench.py --full "$@" 2>> $OUT/err.log | grep '^{' | tail -1 >> $OUT/r4_bench_lines.jsonl
 }
 line
-line --full 1
+line --long 1
 line --steps 20 --warmup 5
 line --workload qp --cpu-baseline 0 --extras 0
 line CLIK_QP_FOLIO=0 --workload qp --cpu-baseline 0 --extras 0

@@ -8,7 +8,7 @@ set -u
 cd "$(dirname "$0")/.."
 OUT=gpurun_out/r6sched
 mkdir -p $OUT
-B="--extras 0 --cpu-baseline 0 --min-timed-ms 500 --ramp-ms 150"
+B="--full --extras 0 --cpu-baseline 0 --min-timed-ms 500 --ramp-ms 150"
 line () {   # label, defines, bench args...
     label=$1; defs=$2; shift; shift
     us=$(CLIK_JIT_DEFINES="$defs" python bench.py $B "$@" 2>$OUT/last.err | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.3f us  %s  check %s' % (d['ms_per_step']*1e3, d['config']['kernel'], d.get('check',{}).get('ok')))")
