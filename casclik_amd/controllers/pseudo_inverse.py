@@ -234,7 +234,7 @@ class PseudoInverseController(BaseController):
         env_jv = os.environ.get("CLIK_JIT_VALUES", "1")
         variant1 = self._lib.clik_pinv_kernel_variant(handle, 1).decode()
         dd = self.descriptor
-        single_mode = (dd.n_x == 0 and dd.n_sets == 0 and variant1 in ("lane", "split"))
+        single_mode = (dd.n_x == 0 and dd.n_sets == 0 and variant1 == "lane")
         wanted = (variant1 == "team4" or single_mode) and jv is not False
         if want_jit and wanted and env_jv != "0":
             from .. import jit
@@ -262,7 +262,8 @@ class PseudoInverseController(BaseController):
 
     def kernel_variant(self, batch):
         """``<kernel>/<variant>`` serving a batch of that many instances: ``team4`` (four lanes per
-        instance), ``mp2`` / ``mp4`` (one wave per mode), ``split``, ``lane`` (one instance per lane)."""
+        instance), ``mp2`` / ``mp4`` (one wave per mode), ``lane`` (one instance per lane), ``lane/occ2`` (its
+        two-waves-per-SIMD build); ``team4v`` / ``quadv`` / ``lanev`` with the skill's numbers compiled in."""
         return "%s/%s" % (self.kernel_name, self._lib.clik_pinv_kernel_variant(self._handle, int(batch)).decode())
 
     def setup_solver(self):

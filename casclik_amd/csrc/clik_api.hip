@@ -21,28 +21,12 @@
 #include <utility>
 #include <vector>
 #include "clik_device.hpp"
+#include "clik_pinv_select.hpp"
 #include "clik_workspace.hpp"
 
 namespace clik {
-struct LaunchArgs {
-    const DevSkill* dS;
-    const void*     dImg;
-    const WarmArgs* warm;
-    int nq, nx, ny;
-    int mode_parallel;
-    double* roll_x;         // (mirror of clik_pinv_kernels.hpp)
-    double* roll_dx;
-    int roll_stages;
-    const double* t_inst;
-};
 int pinv_pick_kernel(const DevSkill& S, int allow_static);
 const char* pinv_kernel_name(int k);
-const char* pinv_static_variant(const ShapeDesc& sd, int mode_parallel, long long B);
-bool shape_team_ok_rt(const ShapeDesc& sd);
-bool shape_quad_front_ok_rt(const ShapeDesc& sd);
-long long pinv_team_max_batch();
-bool shape_value_lane_ok_rt(const ShapeDesc& sd);
-long long pinv_value_lane_max_batch();
 int pinv_kernel_width(int k);
 int pinv_kernel_is_static(int k);
 hipError_t pinv_launch_solve(int k, const LaunchArgs& a, const TickArgs& tk, long long B, const double* q,
@@ -97,7 +81,7 @@ struct clik_pinv {
     DevSkill* dev;
     clik::WarmArgs warm;
     void*     d_img;        // static kernels: device copy of the compact skill image
-    int       mode_parallel; // speculative two-wave kernel for small batches (CLIK_MODE_PARALLEL=0 disables)
+    clik::PinvPolicy policy; // the switches pinv_select reads
     // shape-specialised kernel attached at run time (clik_pinv_attach_kernel)
     clik_jit_solve_fn   jit_solve;
     clik_jit_rollout_fn jit_rollout;
@@ -827,33 +811,26 @@ extern "C" int clik_pinv_create(const clik_skill_desc* desc, const clik_pinv_opt
         }
     }
     {
-        // Small batches (fewer wavefronts than SIMDs) put more than one wave on the same 64
-        // instances.  mode_parallel bit 0: speculative two-wave evaluation of both modes
-        // (pinv_solve_static_mp_kernel; measured 8.0 -> 7.2 us on the config-3 stack, "mixed").
-        // Bit 1: role split (pinv_solve_static_split_kernel: main + helper wave per mode, 4 waves);
-        // it shortens the critical wave by 11 % in cycles but measures the same wall time as the
-        // two-wave kernel (6.42 vs 6.47 us), so it is opt-in: CLIK_ROLE_SPLIT=1.
-        // CLIK_MODE_PARALLEL=0 disables both.
+        // The measuring switches of the kernel choice (pinv_select, clik_pinv_select.hpp), each off with a leading '0'.
+        // CLIK_MODE_PARALLEL: small batches (fewer wavefronts than SIMDs) evaluate the modes of a skill with one or two
+        // SetConstraints speculatively, one wave per mode on the same 64 instances (pinv_solve_static_mp_kernel;
+        // measured 8.0 -> 7.2 us on the config-3 stack, "mixed").
+        // CLIK_LANES: unset / empty / 0 = the library's choice, 4 = the team kernel (four lanes per instance) of the
+        // config-3 family at every batch size (head-to-head runs), anything else = the lane-per-instance kernels.
+        // CLIK_LARGE_BATCH: the two-waves-per-SIMD lane kernel from kOcc2MinBatch instances on, which only the
+        // ahead-of-time table carries.  CLIK_QUAD_FRONT: four lanes per instance for small batches of single-mode skills.
         const char* mp = getenv("CLIK_MODE_PARALLEL");
-        const char* rs = getenv("CLIK_ROLE_SPLIT");
-        h->mode_parallel = (mp && mp[0] == '0') ? 0 : 1;
-        if (h->mode_parallel && rs && rs[0] == '1') h->mode_parallel |= 2;
-        // Bit 2: team kernel, four lanes per instance (pinv_solve_static_team_kernel) for the config-3
-        // family up to kTeamMaxBatch instances; bit 3: at any batch size.  CLIK_LANES=1 keeps the
-        // lane-per-instance kernels, CLIK_LANES=4 forces the team kernel (head-to-head runs), unset / 0 =
-        // the library's choice.
-        // Bit 4: CLIK_LARGE_BATCH=0 keeps the one-wave-per-SIMD lane kernel at every batch size; bit 5 marks
-        // handles served by the ahead-of-time table (the only ones that carry the large-batch build)
-        const char* lb = getenv("CLIK_LARGE_BATCH");
-        if (lb && lb[0] == '0') h->mode_parallel |= 16;
-        if (clik::pinv_kernel_is_static(h->kernel)) h->mode_parallel |= 32;
-        {
-            const char* qf = getenv("CLIK_QUAD_FRONT");      // 0: single-mode skills keep one lane per instance at small batches
-            if (qf && qf[0] == '0') h->mode_parallel |= 128;
-        }
         const char* ln = getenv("CLIK_LANES");
-        if (!ln || ln[0] == '0' || ln[0] == '\0') h->mode_parallel |= 4;
-        else if (ln[0] == '4') h->mode_parallel |= 4 | 8;
+        const char* lb = getenv("CLIK_LARGE_BATCH");
+        const char* qf = getenv("CLIK_QUAD_FRONT");
+        h->policy.mode_waves = !(mp && mp[0] == '0');
+        h->policy.lanes = (!ln || ln[0] == '0' || ln[0] == '\0') ? clik::PinvLanes::choice
+                          : ln[0] == '4'                         ? clik::PinvLanes::team
+                                                                 : clik::PinvLanes::lane;
+        h->policy.large_batch = !(lb && lb[0] == '0');
+        h->policy.aot_large_batch_build = clik::pinv_kernel_is_static(h->kernel) != 0;
+        h->policy.values_attached = false;
+        h->policy.quad_front = !(qf && qf[0] == '0');
     }
     *out = h;
     return CLIK_OK;
@@ -889,13 +866,12 @@ extern "C" int clik_pinv_attach_kernel(clik_pinv* h, void* solve_fn, void* rollo
 extern "C" int clik_pinv_attach_value_kernel(clik_pinv* h, void* solve_fn, void* rollout_fn)
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
-    if (solve_fn && !clik::shape_team_ok_rt(h->host.shape) && !clik::shape_value_lane_ok_rt(h->host.shape))
+    if (solve_fn && !clik::shape_team_ok(h->host.shape) && !clik::shape_value_lane_ok(h->host.shape))
         return fail(CLIK_EUNSUPPORTED, "value-specialised kernels exist for the four-lanes-per-instance family and for "
                                        "single-mode skills without virtual variables");
     h->val_solve = (clik_jit_value_fn)solve_fn;
     h->val_rollout = solve_fn ? (clik_jit_rollout_fn)rollout_fn : nullptr;
-    if (solve_fn) h->mode_parallel |= 64;
-    else h->mode_parallel &= ~64;
+    h->policy.values_attached = solve_fn != nullptr;
     return CLIK_OK;
 }
 
@@ -904,7 +880,7 @@ static int fill_tick(const DevSkill& S, const double* tterms, TickArgs* tk);
 extern "C" int clik_pinv_attach_resident_kernel(clik_pinv* h, void* resident_fn)
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
-    if (resident_fn && !clik::shape_team_ok_rt(h->host.shape) && !clik::shape_quad_front_ok_rt(h->host.shape))
+    if (resident_fn && !clik::shape_team_ok(h->host.shape) && !clik::shape_quad_front_ok(h->host.shape))
         return fail(CLIK_EUNSUPPORTED, "resident ticks exist for the four-lanes-per-instance kernels only (the config-3 family, "
                                        "single-mode skills with forward kinematics)");
     h->val_resident = (decltype(h->val_resident))resident_fn;
@@ -915,7 +891,7 @@ extern "C" int clik_pinv_resident_waves(const clik_pinv* h, int64_t B)
 {
     if (!h || B <= 0) return fail(CLIK_EINVAL, "bad arguments");
     // (the config-3 family runs four waves per 64 instances, the single-mode skills one wave per 16: one slot per wave)
-    if (!clik::shape_team_ok_rt(h->host.shape) && clik::shape_quad_front_ok_rt(h->host.shape)) return (int)((B + 15) / 16);
+    if (!clik::shape_team_ok(h->host.shape) && clik::shape_quad_front_ok(h->host.shape)) return (int)((B + 15) / 16);
     return clik::team_waves_rt((long long)B);
 }
 
@@ -1042,7 +1018,7 @@ extern "C" const char* clik_pinv_kernel_variant(const clik_pinv* h, int64_t B)
 {
     if (!h) return "none";
     if (!h->jit_solve && !(h->kernel >= 0 && clik::pinv_kernel_is_static(h->kernel))) return "dynamic";
-    return clik::pinv_static_variant(h->host.shape, h->mode_parallel, (long long)B);
+    return clik::kPinvVariantName[(int)clik::pinv_select(h->host.shape, h->policy, (long long)B, clik::PinvOp::tick)];
 }
 
 static int fill_tick(const DevSkill& S, const double* tterms, TickArgs* tk)
@@ -1079,19 +1055,14 @@ static int pinv_solve_common(const clik_pinv* h, int64_t B, const double* tterms
         return fail(CLIK_EUNSUPPORTED, "clik_pinv_solve_batch_t: per-instance time needs a shape-specialised kernel "
                                        "for the skill (none built in, none attached)");
     }
-    const clik::LaunchArgs la = {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->mode_parallel, nullptr, nullptr, 1,
+    const clik::LaunchArgs la = {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->policy, nullptr, nullptr, 1,
                                  t_inst};
-    // a value-specialised kernel serves the batches the image-reading team kernel would serve (config-3 family), or
-    // the small batches of a single-mode skill
-    const bool lane_values = clik::shape_value_lane_ok_rt(S.shape) && B <= clik::pinv_value_lane_max_batch();
-    const bool team_batch = clik::shape_team_ok_rt(S.shape)
-                                ? ((h->mode_parallel & 8) || ((h->mode_parallel & 4) && B <= clik::pinv_team_max_batch()) || lane_values)
-                                : lane_values;
     // (the value-specialised library evaluates its own batch limits - it may have been built with other
     // CLIK_VALUE_LANE_* settings than this one: hipErrorNotSupported means "not mine", and the image-reading
     // kernels take the call)
     hipError_t e = hipErrorNotSupported;
-    if (h->val_solve && team_batch && t_inst == nullptr)
+    if (h->val_solve && t_inst == nullptr &&
+        clik::pinv_value_variant(clik::pinv_select(S.shape, h->policy, (long long)B, clik::PinvOp::tick)))
         e = h->val_solve(&la, &tk, (long long)B, q, y, dq, mode, (hipStream_t)stream);
     if (e == hipErrorNotSupported)
         e = h->jit_solve
@@ -1223,14 +1194,10 @@ extern "C" int clik_pinv_rollout_batch_m(const clik_pinv* h, int64_t B, int32_t 
     double* d_tt = nullptr;
     int rc = stage_tterms(tterms, (size_t)n_ticks * stages * 2 * (size_t)S.d.n_tslots, (hipStream_t)stream, &d_tt);
     if (rc) return rc;
-    const clik::LaunchArgs la = {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->mode_parallel, x, dx, stages, nullptr};
-    // the value-specialised rollout serves the batches its per-tick kernel serves (see pinv_solve_common)
-    const bool lane_values = clik::shape_value_lane_ok_rt(S.shape) && B <= clik::pinv_value_lane_max_batch();
-    const bool team_batch = clik::shape_team_ok_rt(S.shape)
-                                ? ((h->mode_parallel & 8) || ((h->mode_parallel & 4) && B <= clik::pinv_team_max_batch()) || lane_values)
-                                : lane_values;
+    const clik::LaunchArgs la = {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->policy, x, dx, stages, nullptr};
     hipError_t e = hipErrorNotSupported;
-    if (h->val_rollout && team_batch && S.d.n_x == 0)
+    if (h->val_rollout && S.d.n_x == 0 &&
+        clik::pinv_value_variant(clik::pinv_select(S.shape, h->policy, (long long)B, clik::PinvOp::rollout)))
         e = h->val_rollout(&la, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, mode, (hipStream_t)stream);
     if (e == hipErrorNotSupported)          // (see pinv_solve_common)
         e = h->jit_rollout

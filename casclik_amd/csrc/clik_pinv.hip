@@ -35,7 +35,7 @@ static_assert(Plan<kStackIiwa, 0u>::mode.dup_task == 1 && Plan<kStackIiwa, 0u>::
 static_assert(Plan<kStackIiwa, 1u>::mode.t[0].push_times == 1 && !Plan<kStackIiwa, 1u>::mode.t[0].gram_after, "set rows explicit");
 static_assert(!Plan<kStackIiwa, 1u>::mode.t[1].quirk && Plan<kStackIiwa, 1u>::mode.t[1].wide_const_task == 0, "pose behind the set");
 static_assert(Plan<kStackIiwa, 1u>::mode.t[2].gram_before && Plan<kStackIiwa, 1u>::mode.dup_task == -1, "Gram consumer");
-static_assert(Plan<kStackIiwa, 1u>::mode.helper_ok && shape_split_ok<kStackIiwa>(), "role split applies");
+static_assert(Plan<kStackIiwa, 1u>::mode.single_gram_consumer, "one Gram consumer");
 static_assert(shape_unit(kStackIiwa, 0) && !shape_unit(kStackIiwa, 1) && shape_unit(kStackIiwa, 2), "joint-space tasks");
 // mode order of pseudo_inverse.py:107-130 for two sets: 00, 10, 01, 11 with set 0 = bit 0
 static_assert(shape_mode_act(shapes::kStackUr5, 0) == 0u && shape_mode_act(shapes::kStackUr5, 1) == 1u, "one set: 0, 1");
@@ -80,12 +80,6 @@ int pinv_pick_kernel(const DevSkill& S, int allow_static)
 }
 
 const char* pinv_kernel_name(int k) { return (k >= 0 && k < kNumShapes) ? kShapes[k].name : "none"; }
-const char* pinv_static_variant(const ShapeDesc& sd, int mode_parallel, long long B) { return static_variant(sd, mode_parallel, B); }
-bool shape_team_ok_rt(const ShapeDesc& sd) { return shape_team_ok(sd); }
-bool shape_quad_front_ok_rt(const ShapeDesc& sd) { return shape_quad_front_ok(sd); }
-long long pinv_team_max_batch() { return kTeamMaxBatch; }
-bool shape_value_lane_ok_rt(const ShapeDesc& sd) { return shape_value_lane_ok(sd); }
-long long pinv_value_lane_max_batch() { return kValueLaneMaxBatch; }
 int pinv_kernel_width(int k) { return (k >= 0 && k < kNumShapes) ? kShapes[k].N : 0; }
 int pinv_kernel_is_static(int k) { return (k >= 0 && k < kNumShapes && kShapes[k].sd) ? 1 : 0; }
 

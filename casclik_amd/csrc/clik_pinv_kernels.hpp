@@ -29,6 +29,7 @@
 #pragma once
 #include "clik_device.hpp"
 #include "clik_pinv_static.hpp"
+#include "clik_pinv_select.hpp"
 
 namespace clik {
 
@@ -461,13 +462,6 @@ __device__ __forceinline__ bool pinv_mode(const DevSkill* __restrict__ S, const 
         for (int ti = 0; ti < n_tasks; ++ti) cones(ti);
     }
     return ok;
-}
-
-constexpr int shape_n_sets(const ShapeDesc& sd)
-{
-    int k = 0;
-    for (int q = 0; q < sd.n_tasks; ++q) k += sd.cls[q] == CLIK_CLS_SET;
-    return k;
 }
 
 // activation mask of the k-th mode in the reference's scan order (pseudo_inverse.py:107-130:
@@ -1096,153 +1090,6 @@ __global__ __launch_bounds__((1 << shape_n_sets(SD)) * WAVE) CLIK_OCC_ATTR void 
     }
 }
 
-// ---- role-split kernel for small batches -----------------------------------------------------
-// With fewer wavefronts than SIMDs (<= 16384 instances on 1024 SIMDs) a tick is the serial fp64
-// chain of ONE wave.  This variant spends the idle SIMDs of the CU on the same 64 instances:
-// per mode a MAIN wave (task solves) and a HELPER wave (builds and factors the Gram-form stack
-// lam I + Ja'Ja that the last task projects through, which depends only on the Jacobians), and
-// with one SetConstraint both modes speculatively (as pinv_solve_static_mp_kernel): 2 or 4 waves
-// per block.  Eligible when every mode has exactly one Gram consumer (ModePlan::helper_ok).
-template <const ShapeDesc& SD, int K = 0>
-constexpr bool shape_split_ok()
-{
-    constexpr int ns = shape_n_sets(SD);
-    if constexpr (ns > 1) return false;
-    else if constexpr (K >= (1 << ns)) return true;
-    else return Plan<SD, shape_mode_act(SD, K)>::mode.helper_ok && shape_split_ok<SD, K + 1>();
-}
-
-template <const ShapeDesc& SD>
-struct SplitLayout {
-    static constexpr int N = SD.n;
-    static constexpr int NM = 1 << shape_n_sets(SD);          // modes (1 or 2)
-    static constexpr int NW = 2 * NM;                          // waves per block
-    static constexpr int XCH = N * (N + 1) / 2 + N;            // slots of one published factor
-    static constexpr int SLOTS = N + (SD.n_y > 0 ? SD.n_y : 0) + NM * XCH + (NM > 1 ? N + 1 : 0);
-    static constexpr size_t LDS_BYTES = ((size_t)StaticLayout<SD>::IMG_DOUBLES + (size_t)SLOTS * WAVE) * sizeof(double);
-};
-
-template <const ShapeDesc& SD>
-__global__ __launch_bounds__(SplitLayout<SD>::NW * WAVE) void pinv_solve_static_split_kernel(
-    const void* __restrict__ img_g, const double* __restrict__ q, const double* __restrict__ y,
-    double* __restrict__ dq, int32_t* __restrict__ mode_out, const long long B, const TickArgs tk)
-{
-    extern __shared__ double lds[];
-    CLIK_STAMP_W(0, 0);
-    using LY = SplitLayout<SD>;
-    constexpr int N = SD.n;
-    constexpr int NM = LY::NM, NW = LY::NW;
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long long b0 = (long long)blockIdx.x * WAVE;
-    const long long left = B - b0;
-    const int rows_valid = left < WAVE ? (int)left : WAVE;
-    const bool valid = lane < rows_valid;
-    double* zs = lds + StaticLayout<SD>::IMG_DOUBLES;
-    double* ys = zs + N * WAVE;
-    double* xch = ys + (SD.n_y > 0 ? SD.n_y : 0) * WAVE;      // NM published factors
-    double* res = xch + NM * LY::XCH * WAVE;                  // mode 1 result: v (N slots) + ok (1 slot)
-    typedef double d2 __attribute__((ext_vector_type(2)));
-    {
-        // the waves share the prologue loads: image chunks round-robin, q by wave 0, y by the last wave
-        constexpr int CH = StaticLayout<SD>::IMG_CHUNKS;
-        constexpr int PER = (CH + NW - 1) / NW;
-        const d2* src = (const d2*)img_g;
-        d2* dst = (d2*)lds;
-        d2 img[PER];
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int ck = k * NW + wave;
-            img[k] = src[(ck < CH ? ck : CH - 1) * WAVE + lane];
-        }
-        double qv[N], yv[SD.n_y > 0 ? SD.n_y : 1];
-        if (wave == 0) stage_load<N>(q + b0 * N, N, rows_valid, lane, qv);
-        if constexpr (SD.n_y > 0) {
-            if (wave == NW - 1) stage_load<SD.n_y>(y + b0 * SD.n_y, SD.n_y, rows_valid, lane, yv);
-        }
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int ck = k * NW + wave;
-            if (ck < CH) dst[ck * WAVE + lane] = img[k];
-        }
-        if (wave == 0) rows_to_lds<N>(qv, zs, lane);
-        if constexpr (SD.n_y > 0) {
-            if (wave == NW - 1) rows_to_lds<SD.n_y>(yv, ys, lane);
-        }
-    }
-    __syncthreads();
-    CLIK_STAMP_W(0, 1);
-    const Img<SD> Sreg = *(const Img<SD>*)lds;       // register copy, see pinv_solve_static_kernel
-    const Img<SD>* __restrict__ S = &Sreg;
-    const double* ysl = ys + lane * SD.n_y;
-    double z[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) z[j] = zs[lane * N + j];
-    __builtin_amdgcn_sched_barrier(0);
-    TaskCache<SD> tc;
-    {
-        Kin<N> K;
-        if constexpr (SD.uses_fk != 0) {
-            forward_kinematics_s<SD>(S, z, K);
-            if constexpr (SD.quat_src != 0) orientation_feature_s<SD>(S, ysl, lane, K);
-        }
-        cache_task<SD, 0>(S, tk, K, z, ysl, lane, tc);
-    }
-    CLIK_STAMP_W(0, 2);
-    CLIK_STAMP_W(1, 6);
-    double v[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) v[j] = 0.0;
-    bool ok = false;
-    const int my_mode = wave >> 1;
-    const bool helper = (wave & 1) != 0;
-    static_for<0, NM>([&](auto mc) __attribute__((always_inline)) {
-        constexpr int m = decltype(mc)::value;
-        constexpr unsigned ACT = shape_mode_act(SD, m);
-        if (my_mode == m) {
-            double* mx = xch + m * LY::XCH * WAVE;
-            if (helper) {
-                helper_mode_static<SD, ACT>(S, tk, tc, z, ysl, lane, mx);
-                CLIK_STAMP_W(1, 7);
-                __syncthreads();                    // (matches the barrier inside the main wave's projection)
-            } else {
-                ok = pinv_mode_static<SD, ACT, ROLE_MAIN>(S, tk, tc, z, ysl, lane, v, mx);
-            }
-        }
-    });
-    CLIK_STAMP_W(0, 3);
-    if constexpr (NM > 1) {
-        if (wave == 2) {
-#pragma unroll
-            for (int j = 0; j < N; ++j) res[j * WAVE + lane] = v[j];
-            res[N * WAVE + lane] = ok ? 1.0 : 0.0;
-        }
-        __syncthreads();
-    }
-    if (wave == 0) {
-        int acc_mode = 0;
-        if (!ok) {
-            if constexpr (NM > 1) {
-                const bool ok1 = res[N * WAVE + lane] != 0.0;
-                acc_mode = ok1 ? 1 : -1;
-#pragma unroll
-                for (int j = 0; j < N; ++j) v[j] = ok1 ? res[j * WAVE + lane] : 0.0;
-            } else {
-                acc_mode = -1;
-#pragma unroll
-                for (int j = 0; j < N; ++j) v[j] = 0.0;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < N; ++j) zs[lane * N + j] = v[j];
-        // (single wave from here on: LDS writes above are read back by the same wave)
-        __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0)
-        rows_from_lds<N>(dq + b0 * N, rows_valid, zs, lane);
-        if (mode_out != nullptr && valid) mode_out[b0 + lane] = acc_mode;
-    }
-    CLIK_STAMP_W(0, 5);
-}
-
 // (one wave per SIMD, stated: the register copy of the skill image lives across the tick loop, and without the
 // statement the allocator parks a few of its values in scratch although the wave could use all 512 registers)
 #ifndef CLIK_ROLL_ATTR
@@ -1368,33 +1215,6 @@ namespace clik {
 #ifndef CLIK_DEFER_INPUT_ROWS
 #define CLIK_DEFER_INPUT_ROWS 1
 #endif
-// value-specialised lane kernel (pinv_solve_static_values_kernel): single-mode skills, and the config-3 family
-// (whose lane evaluation, solo_tick, beats the one-wave-per-mode kernel once the numbers are compiled in: 5.19 / 5.26 /
-// 5.44 us against 5.87 / 5.89 / 5.98 us at 20480 / 24576 / 32768 instances); other skills with up to
-// CLIK_VALUE_LANE_MAX_SETS SetConstraints as an experiment switch (plan-driven sequential modes: 0-6 % over mp2)
-#ifndef CLIK_VALUE_LANE_MAX_SETS
-#define CLIK_VALUE_LANE_MAX_SETS 0
-#endif
-// ... at every batch size: without an image in LDS or registers the kernel fits two waves per SIMD with no spill,
-// and the rows a lane loads / stores itself cost nothing measurable - config 3: 6.18 against 7.19 us at 65536
-// instances, 10.2 against 13.3 us at 131072, 67.7 against 87.2 us at 1 M (CLIK_VALUE_LANE_MAX_BATCH caps it)
-#ifndef CLIK_VALUE_LANE_MAX_BATCH
-#define CLIK_VALUE_LANE_MAX_BATCH (1ll << 40)
-#endif
-
-// common launcher signature of the kernel table
-struct LaunchArgs {
-    const DevSkill* dS;        // dynamic kernels
-    const void*     dImg;      // static kernels: device copy of the skill image
-    const WarmArgs* warm;
-    int nq, nx, ny;
-    int mode_parallel;         // small batches: bit 0 two-wave mode scan, bit 1 role-split kernel,
-                               // bit 2 team kernel (four lanes per instance) where the shape allows, bit 3 ... at any batch
-    double* roll_x;            // rollout of a skill with virtual variables: their state (in/out) and last rates
-    double* roll_dx;
-    int roll_stages;           // rollout: controller evaluations per tick (0 / 1 explicit Euler, 4 Runge-Kutta)
-    const double* t_inst;      // solve: one time-slot record per instance ([B][2 * n_tslots], device) or null
-};
 typedef hipError_t (*solve_fn)(const LaunchArgs&, const TickArgs&, long long, const double*, const double*,
                                const double*, double*, double*, int32_t*, hipStream_t);
 typedef hipError_t (*rollout_fn)(const LaunchArgs&, const double*, int, double, double, long long, double*,
@@ -1431,57 +1251,6 @@ inline size_t static_lds_bytes(int ny)
     return ((size_t)StaticLayout<SD>::IMG_DOUBLES + (size_t)(SD.n + ny) * WAVE) * sizeof(double);
 }
 
-// batches up to this many instances leave SIMDs idle (1024 SIMDs x 64 lanes / 2 waves per block)
-constexpr long long kModeParallelMaxBatch = 32768;
-// the role-split kernel runs 2-4 waves per 64 instances: up to one block per CU
-constexpr long long kRoleSplitMaxBatch = 16384;
-// the team kernel runs four lanes per instance: up to 16384 instances its waves have a SIMD each; beyond,
-// two of them share a SIMD's fp64 pipe and the tick doubles (measured: 5.1 us at 16384, 9.2 us at 32768 against
-// 6.0 us of the two-wave kernel, profiles/r2_lanes_head_to_head.md)
-constexpr long long kTeamMaxBatch = 16384;
-// from this many instances on every SIMD has several waves queued and the two-waves-per-SIMD build of the
-// lane-per-instance kernel wins (pinv_solve_static_occ2_kernel)
-constexpr long long kOcc2MinBatch = 524288;
-
-// The skills the value-specialised lane-per-instance kernel serves: single-mode skills without virtual variables (skills
-// with SetConstraints keep the one-wave-per-mode kernels at small batches, the config-3 family its four lanes per
-// instance) ...
-constexpr bool shape_value_lane_ok(const ShapeDesc& sd)
-{
-    return sd.n_x == 0 && !sd.qp && (shape_n_sets(sd) <= CLIK_VALUE_LANE_MAX_SETS || shape_team_ok(sd));
-}
-// ... and those whose small batches run four lanes per instance with the sin / cos evaluations split over the quad
-// (pinv_solve_static_values_quad_kernel).  ONE predicate for the launcher and for the label.
-constexpr bool shape_quad_front_ok(const ShapeDesc& sd)
-{
-    return shape_value_lane_ok(sd) && !shape_team_ok(sd) && sd.uses_fk != 0 && sd.n >= 3 && sd.n <= 2 * TEAM;
-}
-
-// Which kernel variant serves a batch of B instances of a static shape (the label bench.py and the
-// tests report): the same conditions launch_solve_static evaluates, on the run-time copy of the shape.
-inline const char* static_variant(const ShapeDesc& sd, int mode_parallel, long long B)
-{
-    if (shape_team_ok(sd) && ((mode_parallel & 8) || ((mode_parallel & 4) && B <= kTeamMaxBatch)))
-        return (mode_parallel & 64) ? "team4v" : "team4";       // bit 6: a value-specialised team kernel is attached
-    const int ns = shape_n_sets(sd);
-    if ((mode_parallel & 64) && shape_value_lane_ok(sd) && B <= CLIK_VALUE_LANE_MAX_BATCH) {
-        // value-specialised kernels attached: four lanes per instance (split sin / cos) at small batches of single-mode
-        // skills with forward kinematics, one lane per instance otherwise
-        if (shape_quad_front_ok(sd) && B <= kTeamMaxBatch && !(mode_parallel & 128))
-            return "quadv";
-        return "lanev";
-    }
-    if (sd.n_x == 0 && ns <= 1 && B <= kRoleSplitMaxBatch && (mode_parallel & 2)) {
-        bool ok = true;
-        for (int k = 0; k < (1 << ns); ++k) ok = ok && make_plan(sd, shape_mode_act(sd, k)).helper_ok;
-        if (ok) return "split";
-    }
-    if ((ns == 1 || ns == 2) && sd.n_x == 0 && B <= kModeParallelMaxBatch / ((1 << ns) / 2) && (mode_parallel & 1))
-        return ns == 1 ? "mp2" : "mp4";
-    if (B >= kOcc2MinBatch && (mode_parallel & 32) && !(mode_parallel & 16)) return "lane/occ2";
-    return "lane";
-}
-
 template <const ShapeDesc& SD>
 inline hipError_t launch_solve_static(const LaunchArgs& a, const TickArgs& tk, long long B, const double* q,
                                       const double* x, const double* y, double* dq, double* dx, int32_t* mode,
@@ -1493,45 +1262,39 @@ inline hipError_t launch_solve_static(const LaunchArgs& a, const TickArgs& tk, l
                            a.dImg, q, y, dq, mode, B, x, dx, a.t_inst);
         return hipGetLastError();
     }
-    if constexpr (shape_team_ok(SD)) {
-        // four lanes per instance, a block of four waves = 64 instances (same grid)
-        if ((a.mode_parallel & 8) || ((a.mode_parallel & 4) && B <= kTeamMaxBatch)) {
+    PinvPolicy p = a.policy;
+    p.values_attached = false;      // (this object reads the image: here when the value-specialised one declined)
+    switch (pinv_select(SD, p, B, PinvOp::tick)) {
+    case PinvVariant::team4:
+        if constexpr (shape_team_ok(SD)) {
+            // four lanes per instance, a block of four waves = 64 instances (same grid)
             hipLaunchKernelGGL((pinv_solve_static_team_kernel<SD>), dim3(grid), dim3(TEAM_WAVES * WAVE),
                                team_lds_bytes<SD>(), stream, a.dImg, q, y, dq, mode, B, tk);
             return hipGetLastError();
         }
-    }
-    if constexpr (shape_split_ok<SD>() && SD.n_x == 0) {
-        // one block per 64 instances, 2 or 4 waves each: worth it while blocks <= CUs-ish
-        if (B <= kRoleSplitMaxBatch && (a.mode_parallel & 2)) {
-            constexpr size_t shmem = SplitLayout<SD>::LDS_BYTES;
-            if (shmem > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute((const void*)pinv_solve_static_split_kernel<SD>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-                if (e != hipSuccess) return e;
-            }
-            hipLaunchKernelGGL((pinv_solve_static_split_kernel<SD>), dim3(grid), dim3(SplitLayout<SD>::NW * WAVE),
-                               shmem, stream, a.dImg, q, y, dq, mode, B, tk);
-            return hipGetLastError();
-        }
-    }
-    if constexpr ((StaticLayout<SD>::n_sets == 1 || StaticLayout<SD>::n_sets == 2) && SD.n_x == 0) {
-        // one wave per mode (2 or 4) on the same 64 instances (the multi-wave kernels stage robot_var only)
-        constexpr int NM = 1 << StaticLayout<SD>::n_sets;
-        if (B <= kModeParallelMaxBatch / (NM / 2) && (a.mode_parallel & 1)) {
+        break;
+    case PinvVariant::mp2:
+    case PinvVariant::mp4:
+        if constexpr ((StaticLayout<SD>::n_sets == 1 || StaticLayout<SD>::n_sets == 2) && SD.n_x == 0) {
+            // one wave per mode (2 or 4) on the same 64 instances (the multi-wave kernels stage robot_var only)
+            constexpr int NM = 1 << StaticLayout<SD>::n_sets;
             const size_t shmem = static_lds_bytes<SD>(a.ny) + (size_t)(NM - 1) * (SD.n + 1) * WAVE * sizeof(double);
             hipLaunchKernelGGL((pinv_solve_static_mp_kernel<SD>), dim3(grid), dim3(NM * WAVE), shmem, stream,
                                a.dImg, q, y, dq, mode, B, tk);
             return hipGetLastError();
         }
-    }
-#ifdef CLIK_LARGE_BATCH_VARIANT
-    if (B >= kOcc2MinBatch && !(a.mode_parallel & 16)) {
+        break;
+    case PinvVariant::lane_occ2:
+#ifdef CLIK_LARGE_BATCH_VARIANT     // (the ahead-of-time table's build only: the others run the lane kernel below)
         hipLaunchKernelGGL((pinv_solve_static_occ2_kernel<SD>), dim3(grid), dim3(WAVE), static_lds_bytes<SD>(a.ny), stream,
                            a.dImg, q, y, dq, mode, B, x, dx, tk);
         return hipGetLastError();
-    }
+#else
+        break;
 #endif
+    default:
+        break;
+    }
     hipLaunchKernelGGL((pinv_solve_static_kernel<SD>), dim3(grid), dim3(WAVE), static_lds_bytes<SD>(a.ny), stream,
                        a.dImg, q, y, dq, mode, B, x, dx, tk);
     return hipGetLastError();
@@ -1621,9 +1384,8 @@ inline hipError_t launch_rollout_team_values(const LaunchArgs& a, const double* 
 // The lane-per-instance kernel with the skill's numbers compiled in (IMGV::value: the skill image as a constant
 // expression, see clik_pinv_team.hpp): nothing is staged through LDS - no image copy, no barrier - every lane
 // loads its own robot_var / input_var row and stores its own velocity row.  For the small batches where a tick
-// is the latency of one wave, and - measured - for the large ones too (see CLIK_VALUE_LANE_MAX_BATCH above).
-constexpr long long kValueLaneMaxBatch = CLIK_VALUE_LANE_MAX_BATCH;
-// (which skills it serves: shape_value_lane_ok, above static_variant)
+// is the latency of one wave, and - measured - for the large ones too (see CLIK_VALUE_LANE_MAX_BATCH,
+// clik_pinv_select.hpp; which skills it serves: shape_value_lane_ok).
 template <const ShapeDesc& SD, class IMGV>
 __global__ __launch_bounds__(WAVE) CLIK_OCC_ATTR void pinv_solve_static_values_kernel(
     const double* __restrict__ q, const double* __restrict__ y, double* __restrict__ dq,
@@ -1678,7 +1440,7 @@ __global__ __launch_bounds__(WAVE) CLIK_OCC_ATTR void pinv_solve_static_values_k
 // instead of N evaluations - 170 of the 1240 instructions of the config-2 stream); everything behind is evaluated by
 // all four lanes alike (the entries of the <= 8 x 8 matrices cannot be split: clik_pinv_team.hpp) and lane 0 stores.
 // Up to kTeamMaxBatch instances (one wave per SIMD).  Same values as the lane kernel to rounding.
-// (which skills it serves: shape_quad_front_ok, above static_variant)
+// (which skills it serves: shape_quad_front_ok, clik_pinv_select.hpp)
 template <const ShapeDesc& SD, class IMGV>
 __global__ __launch_bounds__(WAVE) CLIK_OCC_ATTR void pinv_solve_static_values_quad_kernel(
     const double* __restrict__ q, const double* __restrict__ y, double* __restrict__ dq,
@@ -1948,22 +1710,18 @@ inline hipError_t launch_resident_quad_values(const TickArgs& tk, long long B, c
 // traffic is within 16 % of pure issue, and the loop costs what the prefetch saves (256 VGPRs, constants hoisted
 // out of the loop into spilled registers unless -mllvm -disable-machine-licm).
 
-// the value-specialised kernel of a skill for one tick: four lanes per instance where the family allows and the
-// batch is small, else the lane kernel above (hipErrorNotSupported beyond its batch range: the caller then uses
-// the image-reading kernels)
+// the value-specialised kernel of a skill for one tick; hipErrorNotSupported where pinv_select, with this object's
+// CLIK_VALUE_LANE_* limits, names an image-reading kernel (the caller then launches that)
 template <const ShapeDesc& SD, class IMGV>
 inline hipError_t launch_solve_values(const LaunchArgs& a, const TickArgs& tk, long long B, const double* q,
                                       const double* y, double* dq, int32_t* mode, hipStream_t stream)
 {
-    if constexpr (shape_team_ok(SD)) {
-        // (the value-specialised team kernel addresses its rows with 24-bit row numbers: CLIK_LANES=4 at more than 2^24
-        // instances falls through to the lane kernel)
-        if (((a.mode_parallel & 8) && B <= (1ll << 24)) || ((a.mode_parallel & 4) && B <= kTeamMaxBatch))
-            return launch_solve_team_values<SD, IMGV>(a, tk, B, q, y, dq, mode, stream);
-    }
-    if constexpr (shape_quad_front_ok(SD)) {
-        // (bit 7 of mode_parallel: CLIK_QUAD_FRONT=0 keeps one lane per instance - a measuring switch)
-        if (B <= kTeamMaxBatch && !(a.mode_parallel & 128)) {
+    switch (pinv_select(SD, a.policy, B, PinvOp::tick)) {
+    case PinvVariant::team4v:
+        if constexpr (shape_team_ok(SD)) return launch_solve_team_values<SD, IMGV>(a, tk, B, q, y, dq, mode, stream);
+        break;
+    case PinvVariant::quadv:
+        if constexpr (shape_quad_front_ok(SD)) {
             // one WAVE per block (16 instances): the dispatcher spreads blocks over the CUs, so up to 4096 instances every
             // wave has a CU to itself - waves that share a CU run slower each (measured: 3.02 against 3.17 us at 4096
             // instances with four waves per block, profiles/r5_quad_ab.txt)
@@ -1974,14 +1732,17 @@ inline hipError_t launch_solve_values(const LaunchArgs& a, const TickArgs& tk, l
                                stream, q, y, dq, mode, B, tk);
             return hipGetLastError();
         }
-    }
-    if constexpr (shape_value_lane_ok(SD)) {
-        if (B <= kValueLaneMaxBatch) {
+        break;
+    case PinvVariant::lanev:
+        if constexpr (shape_value_lane_ok(SD)) {
             const unsigned grid = (unsigned)((B + WAVE - 1) / WAVE);
             hipLaunchKernelGGL((pinv_solve_static_values_kernel<SD, IMGV>), dim3(grid), dim3(WAVE), 0, stream, q, y, dq,
                                mode, B, tk);
             return hipGetLastError();
         }
+        break;
+    default:
+        break;
     }
     return hipErrorNotSupported;
 }
@@ -2069,12 +1830,13 @@ inline hipError_t launch_rollout_values(const LaunchArgs& a, const double* d_tte
                                         double max_speed, long long B, double* q, const double* y, double* dq,
                                         int32_t* mode, hipStream_t stream)
 {
-    if constexpr (shape_team_ok(SD)) {
-        if ((a.mode_parallel & 8) || ((a.mode_parallel & 4) && B <= kTeamMaxBatch))
+    switch (pinv_select(SD, a.policy, B, PinvOp::rollout)) {
+    case PinvVariant::team4v:
+        if constexpr (shape_team_ok(SD))
             return launch_rollout_team_values<SD, IMGV>(a, d_tterms, n_ticks, dt, max_speed, B, q, y, dq, mode, stream);
-    }
-    if constexpr (shape_value_lane_ok(SD)) {
-        if (B <= kValueLaneMaxBatch) {
+        break;
+    case PinvVariant::lanev:
+        if constexpr (shape_value_lane_ok(SD)) {
             const unsigned grid = (unsigned)((B + WAVE - 1) / WAVE);
             if (a.roll_stages == 4)
                 hipLaunchKernelGGL((pinv_rollout_static_values_kernel<SD, IMGV, true>), dim3(grid), dim3(WAVE), 0, stream,
@@ -2084,6 +1846,9 @@ inline hipError_t launch_rollout_values(const LaunchArgs& a, const double* d_tte
                                    q, y, dq, mode, B, d_tterms, n_ticks, dt, max_speed);
             return hipGetLastError();
         }
+        break;
+    default:
+        break;
     }
     return hipErrorNotSupported;
 }
@@ -2096,7 +1861,9 @@ inline hipError_t launch_rollout_static(const LaunchArgs& a, const double* d_tte
     const unsigned grid = (unsigned)((B + WAVE - 1) / WAVE);
     if constexpr (shape_team_ok(SD)) {
         // four lanes per instance (same grid: 64 instances per block of four waves)
-        if ((a.mode_parallel & 8) || ((a.mode_parallel & 4) && B <= kTeamMaxBatch)) {
+        PinvPolicy p = a.policy;
+        p.values_attached = false;  // (see launch_solve_static)
+        if (pinv_select(SD, p, B, PinvOp::rollout) == PinvVariant::team4) {
             if (a.roll_stages == 4)
                 hipLaunchKernelGGL((pinv_rollout_static_team_kernel<SD, void, 4>), dim3(grid), dim3(TEAM_WAVES * WAVE),
                                    team_rollout_lds_bytes<SD>(), stream, a.dImg, q, y, dq, mode, B, d_tterms, n_ticks, dt, max_speed);

@@ -10,6 +10,7 @@
 // left in the instruction stream and every matrix lives in registers.
 #pragma once
 #include "clik_device.hpp"
+#include "clik_pinv_select.hpp"
 
 namespace clik {
 
@@ -45,11 +46,10 @@ struct ModePlan {
     int wide_local[CLIK_MAX_DOF];
     int wide_store[CLIK_MAX_DOF];
     int n_store;        // per-lane row slots needed
-    // role split (pinv_solve_static_split_kernel): the ONE consumer that projects through a Gram-form
-    // stack, or -1.  helper_ok: there is exactly one and it is the last consumer, so a helper wave can
-    // build and factor that stack while the main wave runs the solves that precede it.
+    // the ONE consumer that projects through a Gram-form stack, or -1.  single_gram_consumer: there is
+    // exactly one and it is the last consumer (the precondition of the duplicated-row form below).
     int gram_consumer;
-    bool helper_ok;
+    bool single_gram_consumer;
     // Duplicated-row stack: the unique Gram consumer projects through c copies of the rows of ONE
     // state-dependent task (the doubly processed first EqualityConstraint, c = 2) with m < n rows.
     // Then  (c J'J + lam I)^-1 c J'J w  =  c J' (c J J' + lam I)^-1 J w   (push-through identity,
@@ -155,11 +155,11 @@ constexpr ModePlan make_plan(const ShapeDesc& sd, unsigned act)
             const bool projects = !p.skip && p.contributes && !p.first;
             if (projects && p.gram_before) { ++n_gram; mp.gram_consumer = ti; }
         }
-        mp.helper_ok = n_gram == 1 && mp.gram_consumer == last_consumer;
-        if (!mp.helper_ok) mp.gram_consumer = -1;
+        mp.single_gram_consumer = n_gram == 1 && mp.gram_consumer == last_consumer;
+        if (!mp.single_gram_consumer) mp.gram_consumer = -1;
         mp.dup_task = -1;
         mp.dup_times = 0;
-        if (mp.helper_ok && !sd.standard) {
+        if (mp.single_gram_consumer && !sd.standard) {
             int pushed = 0, src = -1;
             for (int ti = 0; ti < mp.gram_consumer; ++ti)
                 if (!mp.t[ti].skip && mp.t[ti].push_times > 0) { ++pushed; src = ti; }
@@ -822,18 +822,13 @@ struct StackS {
 
 // mutable per-mode state: plain arrays only (no pointers / references) so that
 // scalar replacement keeps every element in a register
-// ROLE: 0 = one wave evaluates the whole mode; ROLE_MAIN = the Gram-form stack is built and
-// factored by a helper wave (helper_mode_static) and received through LDS (xch)
-constexpr int ROLE_SOLO = 0, ROLE_MAIN = 1, ROLE_HELPER = 2;   // helper: builds the stack only, always in full
-template <const ShapeDesc& SD, unsigned ACT, int ROLE = 0>
+template <const ShapeDesc& SD, unsigned ACT>
 struct ModeCtx {
     static constexpr int N = SD.n;
     double lam;
     double v[N];
     StackS<N, Plan<SD, ACT>::mode.n_store> st;
     bool ok;
-    uint32_t srows[SHAPE_MAX_TASKS];     // ROLE_MAIN: activation bits of the tasks pushed in Gram form
-    const double* xch;                   // ROLE_MAIN: factor published by the helper wave ([slot][lane])
     // duplicated-row stack (ModePlan::dup_task): J J' + lam I of that task, before factorisation
     static constexpr int DM = Plan<SD, ACT>::mode.dup_task >= 0 ? SD.m[Plan<SD, ACT>::mode.dup_task > 0 ? Plan<SD, ACT>::mode.dup_task : 0] : 1;
     double dupM[DM * (DM + 1) / 2];
@@ -870,8 +865,8 @@ __device__ __forceinline__ double jac(const Img<SD>* __restrict__ S, const TaskC
 }
 
 // element j of explicit stack row R (compile-time R)
-template <const ShapeDesc& SD, unsigned ACT, int R, int ROLE = 0>
-__device__ __forceinline__ double stack_row(const Img<SD>* __restrict__ S, const ModeCtx<SD, ACT, ROLE>& c, const int j)
+template <const ShapeDesc& SD, unsigned ACT, int R>
+__device__ __forceinline__ double stack_row(const Img<SD>* __restrict__ S, const ModeCtx<SD, ACT>& c, const int j)
 {
     constexpr ModePlan MP = Plan<SD, ACT>::mode;
     if constexpr (MP.wide_store[R] >= 0) {
@@ -936,15 +931,15 @@ __device__ __forceinline__ void task_values(const Img<SD>* __restrict__ S, const
 }
 
 // w <- w - pinv(stack) * rJa * w  for the stack state BEFORE task TI
-template <const ShapeDesc& SD, unsigned ACT, int TI, int ROLE = 0>
+template <const ShapeDesc& SD, unsigned ACT, int TI>
 __device__ __forceinline__ void project_s(const Img<SD>* __restrict__ S, const TaskCache<SD>& tc,
-                                          ModeCtx<SD, ACT, ROLE>& c, double (&w)[SD.n])
+                                          ModeCtx<SD, ACT>& c, double (&w)[SD.n])
 {
     constexpr int N = SD.n;
     constexpr ModePlan MPL = Plan<SD, ACT>::mode;
     constexpr TaskPlan P = MPL.t[TI];
     constexpr int NT = N * (N + 1) / 2;
-    if constexpr (P.gram_before && ROLE == ROLE_SOLO && MPL.dup_task >= 0) {
+    if constexpr (P.gram_before && MPL.dup_task >= 0) {
         static_assert(MPL.gram_consumer == TI, "duplicated-row projection belongs to the unique Gram consumer");
         constexpr int T0 = MPL.dup_task;
         constexpr int M0 = SD.m[T0];
@@ -974,46 +969,6 @@ __device__ __forceinline__ void project_s(const Img<SD>* __restrict__ S, const T
             for (int i = 0; i < M0; ++i) sacc = fma(-jac<SD, T0>(S, tc, i, j), t[i], sacc);
             w[j] = sacc;
         }
-    } else if constexpr (P.gram_before && ROLE == ROLE_MAIN) {
-        // The Gram matrix lam I + Ja'Ja is built and factored by the helper wave.  Here:
-        //   u = Ja' diag(s) Ja w  straight from the Jacobians of the stacked tasks,
-        //   then  w -= (lam I + Ja'Ja)^-1 u  with the factor received through LDS.
-        static_assert(MPL.helper_ok && MPL.gram_consumer == TI, "role split needs the unique Gram consumer");
-        double u[N];
-#pragma unroll
-        for (int a = 0; a < N; ++a) u[a] = 0.0;
-        static_for<0, TI>([&](auto tn) __attribute__((always_inline)) {
-            constexpr int T = decltype(tn)::value;
-            constexpr TaskPlan PT = MPL.t[T];
-            if constexpr (!PT.skip && PT.push_times > 0) {
-                constexpr int MT = SD.m[T];
-                constexpr double times = (double)PT.push_times;
-                const uint32_t sr = c.srows[T];
-                static_for<0, MT>([&](auto ic) __attribute__((always_inline)) {
-                    constexpr int i = decltype(ic)::value;
-                    if constexpr (shape_unit(SD, T)) {
-                        constexpr int col = SD.ucol[T][i] - 1;
-                        u[col] = fma(times, ((sr >> i) & 1u) ? w[col] : 0.0, u[col]);
-                    } else {
-                        double sacc = 0.0;
-#pragma unroll
-                        for (int j = 0; j < N; ++j) sacc = fma(jac<SD, T>(S, tc, i, j), w[j], sacc);
-                        sacc = ((sr >> i) & 1u) ? times * sacc : 0.0;
-#pragma unroll
-                        for (int j = 0; j < N; ++j) u[j] = fma(jac<SD, T>(S, tc, i, j), sacc, u[j]);
-                    }
-                });
-            }
-        });
-        __syncthreads();            // the helper wave has published L and 1/d
-        double L[NT], rd[N];
-#pragma unroll
-        for (int a = 0; a < NT; ++a) L[a] = c.xch[a * WAVE];
-#pragma unroll
-        for (int a = 0; a < N; ++a) rd[a] = c.xch[(NT + a) * WAVE];
-        ldl_solve_s<N>(L, rd, u);
-#pragma unroll
-        for (int a = 0; a < N; ++a) w[a] -= u[a];
     } else if constexpr (P.gram_before) {
         double u[N], L[NT], rd[N];
 #pragma unroll
@@ -1057,7 +1012,7 @@ __device__ __forceinline__ void project_s(const Img<SD>* __restrict__ S, const T
                 constexpr int i = decltype(ic)::value;
                 double sacc = 0.0;
 #pragma unroll
-                for (int j = 0; j < N; ++j) sacc = fma(stack_row<SD, ACT, i, ROLE>(S, c, j), w[j], sacc);
+                for (int j = 0; j < N; ++j) sacc = fma(stack_row<SD, ACT, i>(S, c, j), w[j], sacc);
                 u[i] = ((c.st.sbits >> i) & 1u) ? sacc : 0.0;
             });
 #pragma unroll
@@ -1071,14 +1026,14 @@ __device__ __forceinline__ void project_s(const Img<SD>* __restrict__ S, const T
             constexpr int i = decltype(ic)::value;
             double s = 0.0;
 #pragma unroll
-            for (int j = 0; j < N; ++j) s = fma(stack_row<SD, ACT, i, ROLE>(S, c, j), w[j], s);
+            for (int j = 0; j < N; ++j) s = fma(stack_row<SD, ACT, i>(S, c, j), w[j], s);
             u[i] = ((c.st.sbits >> i) & 1u) ? s : 0.0;
             static_for<0, i + 1>([&](auto kc) __attribute__((always_inline)) {
                 constexpr int k = decltype(kc)::value;
                 double acc = (k == i) ? c.lam : 0.0;
 #pragma unroll
                 for (int j = 0; j < N; ++j)
-                    acc = fma(stack_row<SD, ACT, i, ROLE>(S, c, j), stack_row<SD, ACT, k, ROLE>(S, c, j), acc);
+                    acc = fma(stack_row<SD, ACT, i>(S, c, j), stack_row<SD, ACT, k>(S, c, j), acc);
                 L[tri(i, k)] = acc;
             });
         });
@@ -1087,14 +1042,14 @@ __device__ __forceinline__ void project_s(const Img<SD>* __restrict__ S, const T
         static_for<0, R>([&](auto kc) __attribute__((always_inline)) {
             constexpr int k = decltype(kc)::value;
 #pragma unroll
-            for (int j = 0; j < N; ++j) w[j] = fma(-u[k], stack_row<SD, ACT, k, ROLE>(S, c, j), w[j]);
+            for (int j = 0; j < N; ++j) w[j] = fma(-u[k], stack_row<SD, ACT, k>(S, c, j), w[j]);
         });
     }
 }
 
 // stack the rows of task TI (plan.push_times times) following the plan
-template <const ShapeDesc& SD, unsigned ACT, int TI, int ROLE = 0>
-__device__ __forceinline__ void push_s(const Img<SD>* __restrict__ S, const TaskCache<SD>& tc, ModeCtx<SD, ACT, ROLE>& c,
+template <const ShapeDesc& SD, unsigned ACT, int TI>
+__device__ __forceinline__ void push_s(const Img<SD>* __restrict__ S, const TaskCache<SD>& tc, ModeCtx<SD, ACT>& c,
                                        const uint32_t srow)
 {
     constexpr int N = SD.n;
@@ -1102,11 +1057,7 @@ __device__ __forceinline__ void push_s(const Img<SD>* __restrict__ S, const Task
     constexpr ModePlan MP = Plan<SD, ACT>::mode;
     constexpr TaskPlan P = MP.t[TI];
     constexpr int TIMES = P.push_times;
-    if constexpr (ROLE == ROLE_MAIN) {
-        c.srows[TI] = srow;
-        if constexpr (P.gram_after) return;        // Gram form: the helper wave's job
-    }
-    if constexpr (ROLE == ROLE_SOLO && MP.dup_task >= 0 && P.gram_after) return;   // consumer uses the m x m form
+    if constexpr (MP.dup_task >= 0 && P.gram_after) return;   // consumer uses the m x m form
     if constexpr (!P.gram_after) {
         // stays wide: record the activation bits; state-dependent rows get a per-lane copy
         constexpr int r0 = P.r_after - TIMES * M;
@@ -1147,14 +1098,14 @@ __device__ __forceinline__ void push_s(const Img<SD>* __restrict__ S, const Task
                         if constexpr (!P.c_is_g_before) {
                             static_for<0, r_prev>([&](auto kc) __attribute__((always_inline)) {
                                 constexpr int k = decltype(kc)::value;
-                                const double pr = stack_row<SD, ACT, k, ROLE>(S, c, a) * stack_row<SD, ACT, k, ROLE>(S, c, b);
+                                const double pr = stack_row<SD, ACT, k>(S, c, a) * stack_row<SD, ACT, k>(S, c, b);
                                 cc += ((c.st.sbits >> k) & 1u) ? pr : 0.0;
                             });
                         }
                     } else {
                         static_for<0, r_prev>([&](auto kc) __attribute__((always_inline)) {
                             constexpr int k = decltype(kc)::value;
-                            const double pr = stack_row<SD, ACT, k, ROLE>(S, c, a) * stack_row<SD, ACT, k, ROLE>(S, c, b);
+                            const double pr = stack_row<SD, ACT, k>(S, c, a) * stack_row<SD, ACT, k>(S, c, b);
                             g += pr;
                             if constexpr (!P.c_is_g_before) cc += ((c.st.sbits >> k) & 1u) ? pr : 0.0;
                         });
@@ -1193,8 +1144,8 @@ __device__ __forceinline__ void push_s(const Img<SD>* __restrict__ S, const Task
     }
 }
 
-template <const ShapeDesc& SD, unsigned ACT, int TI, int ROLE = 0>
-__device__ __forceinline__ void step_s(CLIK_MODE_IN_RAW, ModeCtx<SD, ACT, ROLE>& c)
+template <const ShapeDesc& SD, unsigned ACT, int TI>
+__device__ __forceinline__ void step_s(CLIK_MODE_IN_RAW, ModeCtx<SD, ACT>& c)
 {
     constexpr int N = SD.n;
     constexpr int M = SD.m[TI];
@@ -1212,7 +1163,7 @@ __device__ __forceinline__ void step_s(CLIK_MODE_IN_RAW, ModeCtx<SD, ACT, ROLE>&
                 srow |= (uint32_t)((e[i] - t.set_max[i] > 0.0) | (e[i] - t.set_min[i] < 0.0)) << i;     // (bitwise: no branch per row)
         }
         if constexpr (!P.contributes) {
-            if constexpr (P.push_times > 0) push_s<SD, ACT, TI, ROLE>(S, tc, c, srow);
+            if constexpr (P.push_times > 0) push_s<SD, ACT, TI>(S, tc, c, srow);
         } else {
             double des[M];
             if constexpr (SD.cls[TI] == CLIK_CLS_EQ) {
@@ -1287,7 +1238,7 @@ __device__ __forceinline__ void step_s(CLIK_MODE_IN_RAW, ModeCtx<SD, ACT, ROLE>&
                         for (int j = 0; j < N; ++j) acc = fma(jac<SD, TI>(S, tc, i, j), jac<SD, TI>(S, tc, k, j), acc);
                         L[tri(i, k)] = acc;
                     }
-                if constexpr (ROLE == ROLE_SOLO && Plan<SD, ACT>::mode.dup_task == TI) {
+                if constexpr (Plan<SD, ACT>::mode.dup_task == TI) {
 #pragma unroll
                     for (int a = 0; a < M * (M + 1) / 2; ++a) c.dupM[a] = L[a];
                 }
@@ -1351,23 +1302,23 @@ __device__ __forceinline__ void step_s(CLIK_MODE_IN_RAW, ModeCtx<SD, ACT, ROLE>&
             if constexpr (P.quirk) {
                 // (w already holds the sum of both passes, see above; it was added as the first task)
                 static_assert(P.first, "the doubly processed EqualityConstraint is the first contribution");
-                if constexpr (P.push_times > 0) push_s<SD, ACT, TI, ROLE>(S, tc, c, 0xffffffffu);
+                if constexpr (P.push_times > 0) push_s<SD, ACT, TI>(S, tc, c, 0xffffffffu);
             } else {
                 if constexpr (!P.first) {
-                    project_s<SD, ACT, TI, ROLE>(S, tc, c, w);
+                    project_s<SD, ACT, TI>(S, tc, c, w);
 #pragma unroll
                     for (int j = 0; j < N; ++j) c.v[j] += w[j];
                 }
                 if constexpr (P.push_times > 0)
-                    push_s<SD, ACT, TI, ROLE>(S, tc, c, (P.conv && SD.multidim) ? srow : 0xffffffffu);
+                    push_s<SD, ACT, TI>(S, tc, c, (P.conv && SD.multidim) ? srow : 0xffffffffu);
             }
         }
     }
 }
 
 // in-tangent-cone test of the inactive SetConstraint TI (pseudo_inverse.py:162-185, :222-252)
-template <const ShapeDesc& SD, unsigned ACT, int TI, int ROLE = 0>
-__device__ __forceinline__ void cone_s(CLIK_MODE_IN_RAW, ModeCtx<SD, ACT, ROLE>& c)
+template <const ShapeDesc& SD, unsigned ACT, int TI>
+__device__ __forceinline__ void cone_s(CLIK_MODE_IN_RAW, ModeCtx<SD, ACT>& c)
 {
     constexpr int N = SD.n;
     constexpr int M = SD.m[TI];
@@ -1439,37 +1390,35 @@ __device__ __forceinline__ void cone_s(CLIK_MODE_IN_RAW, ModeCtx<SD, ACT, ROLE>&
 // computes (cur = register copy for step TI), so their latency hides behind that step's
 // arithmetic - a lone wave has nothing else to hide it behind.  (When S already points to a
 // register copy, as in the one-wave kernel, these copies are free.)
-template <const ShapeDesc& SD, unsigned ACT, int TI, int ROLE = 0>
-__device__ __forceinline__ void steps_s(CLIK_MODE_IN, ModeCtx<SD, ACT, ROLE>& c, const Img<SD>* cur)
+template <const ShapeDesc& SD, unsigned ACT, int TI>
+__device__ __forceinline__ void steps_s(CLIK_MODE_IN, ModeCtx<SD, ACT>& c, const Img<SD>* cur)
 {
     if constexpr (TI < SD.n_tasks) {
         const Img<SD> nxt = *S;
         __builtin_amdgcn_sched_barrier(0);
-        step_s<SD, ACT, TI, ROLE>(cur, tk, tc, z, ys, lane, c);
-        steps_s<SD, ACT, TI + 1, ROLE>(CLIK_MODE_ARGS, c, &nxt);
+        step_s<SD, ACT, TI>(cur, tk, tc, z, ys, lane, c);
+        steps_s<SD, ACT, TI + 1>(CLIK_MODE_ARGS, c, &nxt);
     }
 }
 
-template <const ShapeDesc& SD, unsigned ACT, int TI, int ROLE = 0>
-__device__ __forceinline__ void cones_s(CLIK_MODE_IN, ModeCtx<SD, ACT, ROLE>& c)
+template <const ShapeDesc& SD, unsigned ACT, int TI>
+__device__ __forceinline__ void cones_s(CLIK_MODE_IN, ModeCtx<SD, ACT>& c)
 {
     if constexpr (TI < SD.n_tasks) {
-        cone_s<SD, ACT, TI, ROLE>(CLIK_MODE_ARGS, c);
-        cones_s<SD, ACT, TI + 1, ROLE>(CLIK_MODE_ARGS, c);
+        cone_s<SD, ACT, TI>(CLIK_MODE_ARGS, c);
+        cones_s<SD, ACT, TI + 1>(CLIK_MODE_ARGS, c);
     }
 }
 
 // candidate velocity of the mode with activation mask ACT; returns whether all
 // inactive sets are in their tangent cone
-template <const ShapeDesc& SD, unsigned ACT, int ROLE = 0>
+template <const ShapeDesc& SD, unsigned ACT>
 __device__ __forceinline__ bool pinv_mode_static(const Img<SD>* __restrict__ S, const TickArgs& tk,
                                                  const TaskCache<SD>& tc, const double (&z)[SD.n],
-                                                 const double* ys, int lane, double (&v)[SD.n],
-                                                 const double* xch = nullptr)
+                                                 const double* ys, int lane, double (&v)[SD.n])
 {
     constexpr int N = SD.n;
-    ModeCtx<SD, ACT, ROLE> c;
-    c.xch = xch + lane;
+    ModeCtx<SD, ACT> c;
     c.lam = SD.standard ? 0.0 : S->lam;
 #pragma unroll
     for (int j = 0; j < N; ++j) c.v[j] = 0.0;
@@ -1478,78 +1427,15 @@ __device__ __forceinline__ bool pinv_mode_static(const Img<SD>* __restrict__ S, 
     {
         const Img<SD> first = *S;
         __builtin_amdgcn_sched_barrier(0);
-        steps_s<SD, ACT, 0, ROLE>(CLIK_MODE_ARGS, c, &first);
+        steps_s<SD, ACT, 0>(CLIK_MODE_ARGS, c, &first);
     }
-    cones_s<SD, ACT, 0, ROLE>(CLIK_MODE_ARGS, c);
+    cones_s<SD, ACT, 0>(CLIK_MODE_ARGS, c);
 #pragma unroll
     for (int j = 0; j < N; ++j) v[j] = c.v[j];
     return c.ok;
 }
 
-// Helper wave of the role split: builds the stack of mode ACT exactly as the main evaluation
-// would (same activation bits, same push order) up to the unique Gram consumer, factors
-// lam I + Ja'Ja and publishes L (packed) and 1/d through LDS ([slot][lane]).
-template <const ShapeDesc& SD, unsigned ACT>
-__device__ __forceinline__ void helper_mode_static(const Img<SD>* __restrict__ S, const TickArgs& tk,
-                                                   const TaskCache<SD>& tc, const double (&z)[SD.n],
-                                                   const double* ys, int lane, double* xch)
-{
-    constexpr int N = SD.n;
-    constexpr int NT = N * (N + 1) / 2;
-    constexpr ModePlan MP = Plan<SD, ACT>::mode;
-    static_assert(MP.helper_ok, "mode has no unique Gram consumer");
-    ModeCtx<SD, ACT, ROLE_HELPER> c;
-    c.lam = SD.standard ? 0.0 : S->lam;
-    c.st.sbits = 0u;
-    static_for<0, MP.gram_consumer>([&](auto tn) __attribute__((always_inline)) {
-        constexpr int TI = decltype(tn)::value;
-        constexpr TaskPlan P = MP.t[TI];
-        if constexpr (!P.skip && P.push_times > 0) {
-            constexpr int M = SD.m[TI];
-            uint32_t srow = 0xffffffffu;
-            if constexpr (P.set_rows) {
-                decltype(auto) t = task_consts<SD, TI>(S, tc);
-                double e[M], Jt[M];
-                task_values<SD, TI>(S, tk, tc, z, ys, lane, e, Jt);
-                srow = 0u;
-#pragma unroll
-                for (int i = 0; i < M; ++i)
-                    srow |= (uint32_t)((e[i] - t.set_max[i] > 0.0) | (e[i] - t.set_min[i] < 0.0)) << i;     // (bitwise: no branch per row)
-            }
-            // the same argument step_s passes for this kind of task
-            if constexpr (!P.contributes) push_s<SD, ACT, TI, ROLE_HELPER>(S, tc, c, srow);
-            else if constexpr (P.quirk) push_s<SD, ACT, TI, ROLE_HELPER>(S, tc, c, 0xffffffffu);
-            else push_s<SD, ACT, TI, ROLE_HELPER>(S, tc, c, (P.conv && SD.multidim) ? srow : 0xffffffffu);
-        }
-    });
-    double L[NT], rd[N];
-#pragma unroll
-    for (int a = 0; a < NT; ++a) L[a] = c.st.G[a];
-    ldl_factor_s<N>(L, rd);
-#pragma unroll
-    for (int a = 0; a < NT; ++a) xch[a * WAVE + lane] = L[a];
-#pragma unroll
-    for (int a = 0; a < N; ++a) xch[(NT + a) * WAVE + lane] = rd[a];
-}
-
-// ---- the config-3 family: [joint-limit set on every state; task with m <= n state-dependent rows; joint-space task] -----
-// Both modes of such a skill need only shifted copies of ONE Gram matrix Gm = J J' (J: the m x n Jacobian of the
-// second constraint) - see clik_pinv_team.hpp for the algebra and the four-lanes-per-instance kernel built on it.
-constexpr bool shape_team_ok(const ShapeDesc& sd)
-{
-    if (sd.qp || sd.n_tasks != 3 || sd.n_x != 0 || sd.standard || sd.conv_last || !sd.multidim) return false;
-    if (sd.cls[0] != CLIK_CLS_SET || sd.cls[1] != CLIK_CLS_EQ || sd.cls[2] != CLIK_CLS_EQ) return false;
-    if ((sd.ext[0] | sd.ext[1] | sd.ext[2]) & ~1) return false;      // (gains / bounds given as expressions)
-    // the set covers every state variable exactly once (then  lam I + Jset'Jset = (1+lam) I)
-    if (!shape_unit(sd, 0) || sd.m[0] != sd.n || sd.n < 2) return false;
-    for (int c = 0; c < sd.n; ++c)
-        if (shape_unit_row(sd, 0, c) < 0) return false;
-    if (sd.const_j[1] || sd.m[1] > sd.n || sd.m[1] < 1) return false;
-    if (!shape_unit(sd, 2)) return false;
-    return true;
-}
-
-
+// ---- the config-3 family (shape_team_ok, clik_pinv_select.hpp) ----------------------------------------------------
 // The same algebra in ONE lane (the lane-per-instance kernels of this family: large batches, rollouts): the three
 // shifted factorisations one after the other, mode 1 only when some lane of the wave needs it.
 //   A0 = Gm + lam I:      y = A0^-1 d1, y2 = A0^-1 y;  mode 0's doubly processed first equality sums to J'(y + lam y2),

@@ -40,7 +40,6 @@ namespace clik {
 // Round 2's timing ablation (-DCLIK_TEAM_ABLATE, wrong results by design) and the "front end once per quad + broadcast"
 // experiment (-DCLIK_TEAM_FRONT_ONCE, 4.25 against 3.97 us) are retired: tools/experiments/pinv_retired.patch.)
 
-constexpr int TEAM = 4;                     // lanes per instance = one DPP quad
 constexpr int TEAM_WAVES = 4;               // waves per block: 64 instances, one wave per SIMD of a CU
 constexpr int TEAM_INST = TEAM_WAVES * WAVE / TEAM;
 

@@ -136,3 +136,70 @@ def test_ticket_layout(tmp_path):
     # (int32 words 16: ring_depth; float64 words 9, 10: integrate_dt, max_speed - casclik_amd/controllers/pseudo_inverse.py)
     assert [int(v) for v in subprocess.check_output([str(exe)]).split()] == [256, 0, 4 * 32, 4 * 48, 4 * 49, 4 * 16,
                                                                                8 * 9, 8 * 10]
+
+
+# clik_pinv_kernel_variant for the stack skill (config 3: the four-lanes-per-instance family, one SetConstraint) and the
+# pose skill (single-mode, forward kinematics), at these batch sizes, with one measuring switch set at a time, for the
+# image-reading kernels and with a value-specialised kernel attached
+_SELECT_B = (1, 4096, 16384, 16385, 32768, 32769, 131072, 524287, 524288, 1 << 20, (1 << 24) + 1)
+_SELECT_TABLE = {
+    ("stack", None, False): ["team4", "team4", "team4", "mp2", "mp2", "lane", "lane", "lane", "lane/occ2", "lane/occ2", "lane/occ2"],
+    ("stack", "CLIK_LANES=1", False): ["mp2", "mp2", "mp2", "mp2", "mp2", "lane", "lane", "lane", "lane/occ2", "lane/occ2", "lane/occ2"],
+    ("stack", "CLIK_LANES=4", False): ["team4"] * 11,
+    ("stack", "CLIK_MODE_PARALLEL=0", False): ["team4", "team4", "team4", "lane", "lane", "lane", "lane", "lane", "lane/occ2", "lane/occ2", "lane/occ2"],
+    ("stack", "CLIK_LARGE_BATCH=0", False): ["team4", "team4", "team4", "mp2", "mp2", "lane", "lane", "lane", "lane", "lane", "lane"],
+    ("stack", "CLIK_QUAD_FRONT=0", False): ["team4", "team4", "team4", "mp2", "mp2", "lane", "lane", "lane", "lane/occ2", "lane/occ2", "lane/occ2"],
+    ("stack", None, True): ["team4v", "team4v", "team4v", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev"],
+    ("stack", "CLIK_LANES=1", True): ["lanev"] * 11,
+    # (the value-specialised team tick addresses its rows with 24-bit row numbers: the lane kernel beyond)
+    ("stack", "CLIK_LANES=4", True): ["team4v"] * 10 + ["lanev"],
+    ("stack", "CLIK_MODE_PARALLEL=0", True): ["team4v", "team4v", "team4v", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev"],
+    ("stack", "CLIK_LARGE_BATCH=0", True): ["team4v", "team4v", "team4v", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev"],
+    ("stack", "CLIK_QUAD_FRONT=0", True): ["team4v", "team4v", "team4v", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev"],
+    ("pose", None, False): ["lane", "lane", "lane", "lane", "lane", "lane", "lane", "lane", "lane/occ2", "lane/occ2", "lane/occ2"],
+    ("pose", "CLIK_LANES=1", False): ["lane", "lane", "lane", "lane", "lane", "lane", "lane", "lane", "lane/occ2", "lane/occ2", "lane/occ2"],
+    ("pose", "CLIK_LANES=4", False): ["lane", "lane", "lane", "lane", "lane", "lane", "lane", "lane", "lane/occ2", "lane/occ2", "lane/occ2"],
+    ("pose", "CLIK_MODE_PARALLEL=0", False): ["lane", "lane", "lane", "lane", "lane", "lane", "lane", "lane", "lane/occ2", "lane/occ2", "lane/occ2"],
+    ("pose", "CLIK_LARGE_BATCH=0", False): ["lane"] * 11,
+    ("pose", "CLIK_QUAD_FRONT=0", False): ["lane", "lane", "lane", "lane", "lane", "lane", "lane", "lane", "lane/occ2", "lane/occ2", "lane/occ2"],
+    ("pose", None, True): ["quadv", "quadv", "quadv", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev"],
+    ("pose", "CLIK_LANES=1", True): ["quadv", "quadv", "quadv", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev"],
+    ("pose", "CLIK_LANES=4", True): ["quadv", "quadv", "quadv", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev"],
+    ("pose", "CLIK_MODE_PARALLEL=0", True): ["quadv", "quadv", "quadv", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev"],
+    ("pose", "CLIK_LARGE_BATCH=0", True): ["quadv", "quadv", "quadv", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev", "lanev"],
+    ("pose", "CLIK_QUAD_FRONT=0", True): ["lanev"] * 11,
+}
+
+
+@pytest.mark.parametrize("skill", ["stack", "pose"])
+@pytest.mark.parametrize("env", [None, "CLIK_LANES=1", "CLIK_LANES=4", "CLIK_MODE_PARALLEL=0", "CLIK_LARGE_BATCH=0",
+                                 "CLIK_QUAD_FRONT=0"])
+def test_kernel_variant_selection_table(lib, monkeypatch, skill, env):
+    """The kernel choice of the pseudo-inverse path (pinv_select, clik_pinv_select.hpp) against a written-out table, on
+    host-only handles.  The switches are read at creation; the value-specialised kernel attached is a stand-in that is
+    never called (a host-only handle launches nothing)."""
+    import casclik_amd as cc
+    for name in ("CLIK_LANES", "CLIK_MODE_PARALLEL", "CLIK_LARGE_BATCH", "CLIK_QUAD_FRONT"):
+        monkeypatch.delenv(name, raising=False)
+    if env:
+        monkeypatch.setenv(*env.split("="))
+    fk = skills.iiwa()
+    spec = skills.stack_skill(fk) if skill == "stack" else skills.pose_skill(fk)
+    opts = dict(skills.STACK_OPTIONS) if skill == "stack" else {}
+    desc = _capi.desc_to_c(lower_skill(spec))
+    copts = _capi.pinv_opts_to_c(cc.PseudoInverseController(skill_spec=spec, options=opts).options)
+    h = C.c_void_p()
+    assert lib.clik_pinv_create_host(C.byref(desc), C.byref(copts), C.byref(h)) == 0
+    try:
+        assert lib.clik_pinv_kernel_name(h).decode() == ("kStackIiwa" if skill == "stack" else "kPose6Iiwa")
+        got = [lib.clik_pinv_kernel_variant(h, B).decode() for B in _SELECT_B]
+        assert got == _SELECT_TABLE[(skill, env, False)]
+
+        def never(*args):
+            raise AssertionError("the stand-in value kernel was called")
+        stand_in = C.CFUNCTYPE(C.c_int)(never)
+        assert lib.clik_pinv_attach_value_kernel(h, C.cast(stand_in, C.c_void_p), None) == 0
+        got = [lib.clik_pinv_kernel_variant(h, B).decode() for B in _SELECT_B]
+        assert got == _SELECT_TABLE[(skill, env, True)]
+    finally:
+        assert lib.clik_pinv_destroy(h) == 0
