@@ -221,7 +221,6 @@ class ReactiveQPController(BaseController):
         # against 7.4); for other skills on request (function_opts["jit_values"] = True or CLIK_JIT_VALUES=2: it keeps
         # the LDS work area and gains about 1 %); function_opts["jit_values"] = False or CLIK_JIT_VALUES=0: never.
         self.value_kernel = None
-        self._value_variant_fn = None
         jv, env_jv = fopts.get("jit_values", None), os.environ.get("CLIK_JIT_VALUES", "1")
         # (skills with more than ten state variables - two arms - keep the image-reading kernel unless asked: the
         # value-specialised one holds its n x n factor in registers)
@@ -232,10 +231,6 @@ class ReactiveQPController(BaseController):
             with torch.cuda.device(self._device):
                 try:
                     self.value_kernel = jit.attach_qp_values(self._lib, handle, cdesc, extern=d.extern_source())
-                    if self.value_kernel:
-                        fn = jit.attach_qp_values.last_library.clik_jit_qp_value_variant
-                        fn.restype, fn.argtypes = C.c_char_p, [C.c_longlong, C.c_int]
-                        self._value_variant_fn = fn
                 except RuntimeError as exc:
                     import warnings
                     warnings.warn("value-specialised QP kernel could not be built, using the image-reading one: %s"
@@ -522,18 +517,10 @@ class ReactiveQPController(BaseController):
 
     # -- per tick -----------------------------------------------------------------
     def kernel_variant(self, batch, hot=False):
-        """name of the kernel a batch of ``batch`` instances gets ("/v": with the skill's numbers compiled in; ``hot``:
-        for a hot-started tick).  The suffix behind "/v" is the LAUNCHER's own decision: the instantiated library
-        exports the predicate it launches by (clik_jit_qp_value_variant, csrc/clik_qp_static.hpp::qp_values_choice) -
-        "/folio4": cold ticks of small batches, four waves per 64 instances with different starts of the passes;
-        nothing: one lane per instance."""
-        name = self.kernel_name + ("/v" if getattr(self, "value_kernel", None) else "")
-        fn = getattr(self, "_value_variant_fn", None)
-        if getattr(self, "value_kernel", None) and fn is not None:
-            torch = _torch()
-            with torch.cuda.device(self._device):
-                name += fn(int(batch), 1 if hot else 0).decode()
-        return name
+        """name of the kernel a batch of ``batch`` instances gets (``hot``: for a hot-started tick): ``kernel_name``, then
+        "/v" with the skill's numbers compiled in and "/v/folio4" for its cold ticks of small batches (four waves per 64
+        instances with different starts of the passes) - the launcher's own predicate (clik_qp_kernel_variant)."""
+        return self.kernel_name + self._lib.clik_qp_kernel_variant(self._handle, int(batch), 1 if hot else 0).decode()
 
     # -- resident ticks ----------------------------------------------------------------------------------------
     def workspace_bytes(self):

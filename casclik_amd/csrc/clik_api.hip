@@ -22,6 +22,7 @@
 #include <vector>
 #include "clik_device.hpp"
 #include "clik_pinv_select.hpp"
+#include "clik_qp_select.hpp"
 #include "clik_workspace.hpp"
 
 namespace clik {
@@ -48,9 +49,6 @@ int qp_variant_width(int k);
 size_t qp_variant_lds(int k, int ny);
 int qp_pick_static(const ShapeDesc& sd);
 const char* qp_static_name(int k);
-bool qp_box_family_rt(const ShapeDesc& sd);
-int qp_plan_rows_rt(const ShapeDesc& sd);
-int qp_layout_slots_rt(const ShapeDesc& sd);
 int team_waves_rt(long long B);                 // (clik_pinv.hip)
 hipError_t launch_ticket_feed(void* ticket, const unsigned* done, int n_ticks, int closed_loop, unsigned waves_per_tick,
                               unsigned long long timeout_ticks, hipStream_t stream);
@@ -96,20 +94,6 @@ struct clik_pinv {
                                unsigned*, int, unsigned long long, hipStream_t);
 };
 
-typedef hipError_t (*clik_jit_qp_fn)(const void*, const TickArgs*, long long, const double*, const double*,
-                                     const double*, double*, double*, double*, int32_t*, int32_t*, int, hipStream_t,
-                                     const double*);
-
-typedef hipError_t (*clik_jit_qp_rollout_fn)(const void*, const double*, int, double, double, long long, double*,
-                                             const double*, double*, double*, int32_t*, double*, double*,
-                                             hipStream_t, int);
-
-typedef hipError_t (*clik_jit_qp_value_fn)(const TickArgs*, long long, const double*, const double*, const double*,
-                                           double*, double*, double*, int32_t*, int32_t*, int, hipStream_t);
-
-typedef hipError_t (*clik_jit_qp_value_rollout_fn)(const double*, int, double, double, long long, double*, const double*,
-                                                   double*, double*, int32_t*, double*, double*, hipStream_t, int);
-
 struct clik_qp {
     DevSkill  host;
     DevSkill* dev;
@@ -118,13 +102,12 @@ struct clik_qp {
                             // the shape-specialised kernels
     void*     d_img;        // shape-specialised kernels: skill image + QP options
     int       static_k;     // AOT shape-specialised kernel, -1 none
-    clik_jit_qp_fn jit_solve;
-    clik_jit_qp_rollout_fn jit_rollout;
-    clik_jit_qp_value_fn val_solve;     // per-tick kernel with this skill's numbers and QP options compiled in
-    clik_jit_qp_value_rollout_fn val_rollout;   // ... and its on-device rollout (box family), or null
-    // ... and its resident form (clik_qp_attach_resident_kernel), or null
-    hipError_t (*val_resident)(const TickArgs*, long long, const double*, const double*, double*, double*, int32_t*, void*,
-                               unsigned*, int, unsigned long long, hipStream_t);
+    clik::QpPolicy policy;  // the switches qp_select reads
+    clik::qp_jit_fn jit_solve;
+    clik::qp_static_rollout_fn jit_rollout;
+    clik::qp_value_fn val_solve;     // per-tick kernel with this skill's numbers and QP options compiled in
+    clik::qp_value_rollout_fn val_rollout;   // ... and its on-device rollout (box family), or null
+    clik::qp_value_resident_fn val_resident; // ... and its resident form (clik_qp_attach_resident_kernel), or null
     char      jit_name[64];
     // work area of the global-workspace kernels (clik_workspace.hpp): belongs to this handle, released by clik_qp_destroy
     clik::GwsOwner* gws;
@@ -510,19 +493,6 @@ static void finish_qp_shape(DevSkill& S)
         S.shape.soft[ti] = (ti < S.d.n_tasks && S.d.tasks[ti].soft) ? 1 : 0;
 }
 
-// rows handed to the active-set solver by the shape-specialised QP kernel (clik_qp_static.hpp,
-// make_qp_plan): everything but the soft equalities
-static int qp_static_rows(const DevSkill& S)
-{
-    int nr = 0;
-    for (int ti = 0; ti < S.d.n_tasks; ++ti) {
-        const clik_task& t = S.d.tasks[ti];
-        const bool folded = t.soft && (t.cls == CLIK_CLS_EQ || t.cls == CLIK_CLS_VELEQ);
-        if (!folded) nr += t.m;
-    }
-    return nr;
-}
-
 // can a shape-specialised QP kernel serve the skill?  (image layout, row budget, LDS)
 static bool qp_static_eligible(const DevSkill& S)
 {
@@ -532,12 +502,11 @@ static bool qp_static_eligible(const DevSkill& S)
     if (!build_skill_image(S, img, &image_bytes, sizeof(clik::QpTail))) return false;
     // (the kernels' own count: a joint-limit row and a speed-limit row on the same state are ONE active-set row -
     // a skill with walls, joint limits and speed limits on every joint of a 7-DoF arm has 10 such rows, not 17)
-    const int nr = clik::qp_plan_rows_rt(S.shape);
-    if (nr > 16) return false;
+    if (clik::make_qp_plan(S.shape).nr > clik::QPS_MAX_ROWS) return false;
     // (the layout's own slot count: the primal families - bound-constrained, mixed - keep no dual Hessian in LDS, so a
     // two-arm skill with 14 merged box rows fits where the dual form's 14 x 14 + 14 x 14 slots would not)
-    const size_t slots = (size_t)clik::qp_layout_slots_rt(S.shape);
-    return img.size() + slots * 64 * sizeof(double) <= 160u * 1024u;
+    const size_t slots = (size_t)clik::qp_slot_layout(S.shape).slots;
+    return img.size() + slots * clik::WAVE * sizeof(double) <= clik::kLdsBytesPerCu;
 }
 
 static bool build_qp_image(const DevSkill& S, std::vector<char>& out)
@@ -781,7 +750,7 @@ extern "C" int clik_pinv_create(const clik_skill_desc* desc, const clik_pinv_opt
     compute_warm(S, S.lds_slots, h->warm);
     S.zero_token = 0;
     S.lds_slots = clik::pinv_lds_slots_host(clik::pinv_kernel_width(h->kernel), S.d.n_y);
-    if ((size_t)S.lds_slots * clik::WAVE * sizeof(double) > 160u * 1024u) {
+    if ((size_t)S.lds_slots * clik::WAVE * sizeof(double) > clik::kLdsBytesPerCu) {
         delete h;
         return fail(CLIK_EUNSUPPORTED, "skill needs %d LDS slots per lane (input_var too large)", S.lds_slots);
     }
@@ -1263,15 +1232,16 @@ extern "C" int clik_qp_create(const clik_skill_desc* desc, const clik_qp_opts* o
         h->variant = clik::qp_pick_variant(need, S.n_qp_vars, S.n_qp_rows);
     }
     finish_qp_shape(S);
+    const bool eligible = qp_static_eligible(S);
     {
         // The built-in (dynamic) kernel keeps every row, soft equalities included, in its active set;
         // the shape-specialised kernels eliminate those and fit larger skills.  A skill only they can
         // serve gets a handle without a built-in kernel (variant -1): it solves once a kernel is
         // attached (clik_qp_attach_kernel) or the AOT table has one.
         const bool dyn_rows = h->variant >= 0;
-        const bool dyn_lds = dyn_rows && clik::qp_variant_lds(h->variant, S.d.n_y) <= 160u * 1024u;
+        const bool dyn_lds = dyn_rows && clik::qp_variant_lds(h->variant, S.d.n_y) <= clik::kLdsBytesPerCu;
         if (!dyn_lds) {
-            if (!qp_static_eligible(S)) {
+            if (!eligible) {
                 delete h;
                 if (!dyn_rows)
                     return fail(CLIK_EUNSUPPORTED,
@@ -1286,12 +1256,23 @@ extern "C" int clik_qp_create(const clik_skill_desc* desc, const clik_qp_opts* o
     S.zero_token = 0;
     S.lds_slots = 0;
     h->d_img = nullptr;
-    h->static_k = -1;
     h->jit_solve = nullptr;
     h->jit_rollout = nullptr;
     h->val_resident = nullptr;
     h->jit_name[0] = 0;
     h->dev = nullptr;
+    {
+        // the switches of the kernel choice (qp_select, clik_qp_select.hpp): CLIK_FORCE_DYNAMIC=1 / CLIK_NO_AOT=1 skip
+        // the AOT table (the Python layer may still attach a run-time instantiated kernel)
+        const char* force = getenv("CLIK_FORCE_DYNAMIC");
+        const char* noaot = getenv("CLIK_NO_AOT");
+        h->policy.aot = !((force && force[0] == '1') || (noaot && noaot[0] == '1'));
+        h->policy.values_attached = false;
+        h->policy.folio = clik::qp_env().folio;
+        h->policy.cus = 0;
+    }
+    // shape-specialised kernel from the AOT table (a host-only handle picks it too, and uploads nothing)
+    h->static_k = (h->policy.aot && eligible) ? clik::qp_pick_static(S.shape) : -1;
     if (host_only_mode()) {
         *out = h;
         return CLIK_OK;
@@ -1300,22 +1281,35 @@ extern "C" int clik_qp_create(const clik_skill_desc* desc, const clik_qp_opts* o
     if (e != hipSuccess) { delete h; return hipfail(e, "hipMalloc(skill)"); }
     e = hipMemcpy(h->dev, &S, sizeof(DevSkill), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(h->dev); delete h; return hipfail(e, "hipMemcpy(skill)"); }
-    {
-        // shape-specialised kernel from the AOT table (CLIK_FORCE_DYNAMIC=1 / CLIK_NO_AOT=1 skip it)
-        const char* force = getenv("CLIK_FORCE_DYNAMIC");
-        const char* noaot = getenv("CLIK_NO_AOT");
-        const bool allow = !((force && force[0] == '1') || (noaot && noaot[0] == '1'));
-        if (allow && qp_static_eligible(S)) {
-            const int k = clik::qp_pick_static(S.shape);
-            if (k >= 0) {
-                int rc2 = qp_upload_image(h);
-                if (rc2) { (void)hipFree(h->dev); delete h; return rc2; }
-                h->static_k = k;
-            }
-        }
+    if (h->static_k >= 0) {
+        int rc2 = qp_upload_image(h);
+        if (rc2) { (void)hipFree(h->dev); delete h; return rc2; }
     }
+    h->policy.cus = clik::current_device_cus();
     *out = h;
     return CLIK_OK;
+}
+
+// what the handle holds, as qp_select sees it
+static clik::QpKernels qp_kernels(const clik_qp* h)
+{
+    clik::QpKernels k;
+    k.aot = h->static_k >= 0;
+    k.jit_solve = h->jit_solve != nullptr;
+    k.jit_rollout = h->jit_rollout != nullptr;
+    k.value_rollout = h->val_rollout != nullptr;
+    k.dyn_width = clik::qp_variant_width(h->variant);
+    k.generated = skill_has_extern(h->host);
+    k.wide = skill_has_wide_task(h->host);
+    return k;
+}
+
+// a shape-specialised kernel (AOT or attached) serves the handle's ticks: what a value-specialised one stands in for
+static bool qp_shape_served(const clik_qp* h)
+{
+    clik::QpPolicy image = h->policy;
+    image.values_attached = false;
+    return clik::qp_shape_kernel(clik::qp_select(h->host.shape, image, qp_kernels(h), 1, false, clik::QpOp::tick));
 }
 
 // ShapeDesc initialiser of a QP skill (see clik_shape_describe); returns 1 when a
@@ -1347,8 +1341,8 @@ extern "C" int clik_qp_attach_kernel(clik_qp* h, void* solve_fn, void* rollout_f
         return fail(CLIK_EUNSUPPORTED, "skill is outside the shape-specialised QP family");
     int rc = qp_upload_image(h);
     if (rc) return rc;
-    h->jit_solve = (clik_jit_qp_fn)solve_fn;
-    h->jit_rollout = (clik_jit_qp_rollout_fn)rollout_fn;
+    h->jit_solve = (clik::qp_jit_fn)solve_fn;
+    h->jit_rollout = (clik::qp_static_rollout_fn)rollout_fn;
     snprintf(h->jit_name, sizeof(h->jit_name), "%s", name ? name : "jit");
     return CLIK_OK;
 }
@@ -1386,17 +1380,18 @@ extern "C" int clik_qp_rollout_batch_m(const clik_qp* hc, int64_t B, int32_t n_t
     const DevSkill& S = h->host;
     if (S.d.n_x > 0 && (!x || !dx))
         return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required (clik_qp_rollout_batch_x)");
-    if (!h->jit_rollout && h->static_k < 0)
+    const clik::QpKernel k = clik::qp_select(S.shape, h->policy, qp_kernels(h), (long long)B, false, clik::QpOp::rollout);
+    if (k == clik::QpKernel::none)
         return fail(CLIK_EUNSUPPORTED, "the QP rollout needs a shape-specialised kernel (none attached for this skill)");
     if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
     if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
     double* d_tt = nullptr;
     int rc = stage_tterms(tterms, (size_t)n_ticks * stages * 2 * (size_t)S.d.n_tslots, (hipStream_t)stream, &d_tt);
     if (rc) return rc;
-    hipError_t e = h->val_rollout
+    hipError_t e = k == clik::QpKernel::value
                        ? h->val_rollout(d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, slack, status, x, dx,
                                         (hipStream_t)stream, stages)
-                   : h->jit_rollout
+                   : k == clik::QpKernel::jit
                        ? h->jit_rollout(h->d_img, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, slack,
                                         status, x, dx, (hipStream_t)stream, stages)
                        : clik::qp_launch_rollout_static(h->static_k, h->d_img, d_tt, n_ticks, dt, max_speed,
@@ -1432,26 +1427,25 @@ extern "C" int clik_qp_image_words(const clik_qp* h, uint64_t* buf, int cap)
 extern "C" int clik_qp_is_box_family(const clik_qp* h)
 {
     if (!h) return 0;
-    if (!h->jit_solve && h->static_k < 0) return 0;
-    return clik::qp_box_family_rt(h->host.shape) ? 1 : 0;
+    return (qp_shape_served(h) && CLIK_QP_BOX_OK(h->host.shape)) ? 1 : 0;
 }
 
 extern "C" int clik_qp_attach_value_kernel(clik_qp* h, void* solve_fn, void* rollout_fn)
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
-    if (solve_fn && !h->jit_solve && h->static_k < 0)
+    if (solve_fn && !qp_shape_served(h))
         return fail(CLIK_EUNSUPPORTED, "value-specialised QP kernels exist for skills a shape-specialised kernel serves");
-    h->val_solve = (clik_jit_qp_value_fn)solve_fn;
+    h->val_solve = (clik::qp_value_fn)solve_fn;
     // (the value-specialised rollout exists for the box family only)
-    h->val_rollout = (solve_fn && clik::qp_box_family_rt(h->host.shape)) ? (clik_jit_qp_value_rollout_fn)rollout_fn : nullptr;
+    h->val_rollout = (solve_fn && CLIK_QP_BOX_OK(h->host.shape)) ? (clik::qp_value_rollout_fn)rollout_fn : nullptr;
+    h->policy.values_attached = solve_fn != nullptr;
     return CLIK_OK;
 }
 
 extern "C" int clik_qp_attach_resident_kernel(clik_qp* h, void* resident_fn)
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
-    if (resident_fn && !(clik::qp_box_family_rt(h->host.shape) && h->host.d.n_x == 0 && h->host.shape.uses_fk != 0 &&
-                         h->host.n >= 3 && h->host.n <= 8))
+    if (resident_fn && !clik::qp_resident_ok(h->host.shape))
         return fail(CLIK_EUNSUPPORTED, "resident QP ticks exist for bound-constrained skills with forward kinematics and "
                                        "without virtual variables");
     h->val_resident = (decltype(h->val_resident))resident_fn;
@@ -1499,6 +1493,13 @@ extern "C" const char* clik_qp_kernel_name(const clik_qp* h)
     return h->variant >= 0 ? "dynamic" : "none";
 }
 
+extern "C" const char* clik_qp_kernel_variant(const clik_qp* h, int64_t B, int32_t hot)
+{
+    if (!h) return "";
+    return clik::kQpVariantName[(int)clik::qp_select(h->host.shape, h->policy, qp_kernels(h), (long long)B, hot != 0,
+                                                     clik::QpOp::tick)];
+}
+
 extern "C" int clik_qp_destroy(clik_qp* h)
 {
     if (!h) return CLIK_OK;
@@ -1543,31 +1544,32 @@ static int qp_solve_common(const clik_qp* h, int64_t B, const double* tterms, co
     if (!dq) return fail(CLIK_EINVAL, "dq must be a device pointer");
     // (a constraint with more than eight rows is fine for the dynamic QP kernels twelve rows wide - the variant picked at
     // create time covers the widest constraint; only generated constraint code needs an instantiated kernel)
-    if (!h->jit_solve && h->static_k < 0 &&
-        (skill_has_extern(h->host) || (skill_has_wide_task(h->host) && (h->variant < 0 || clik::qp_variant_width(h->variant) <= CLIK_DYN_MAX_M))))
-        return extern_needs_kernel("clik_qp_solve_batch");
+    const clik::QpKernel k = clik::qp_select(h->host.shape, h->policy, qp_kernels(h), (long long)B, use_hot != 0,
+                                             t_inst ? clik::QpOp::tick_t : clik::QpOp::tick);
+    if (k == clik::QpKernel::needs_instance) return extern_needs_kernel("clik_qp_solve_batch");
     TickArgs tk;
     if (t_inst == nullptr) {
         rc = fill_tick(h->host, tterms, &tk);
         if (rc) return rc;
-    } else if (!h->jit_solve && h->static_k < 0) {
+    } else if (k == clik::QpKernel::none) {
         return fail(CLIK_EUNSUPPORTED, "clik_qp_solve_batch_t: per-instance time needs a shape-specialised kernel "
                                        "for the skill (none built in, none attached)");
     }
     hipError_t e;
-    if (h->val_solve && t_inst == nullptr)
+    switch (k) {
+    case clik::QpKernel::value_folio:
+    case clik::QpKernel::value:
         e = h->val_solve(&tk, (long long)B, q, x, y, dq, dx, slack, status, hot_set, use_hot, (hipStream_t)stream);
-    else if (h->jit_solve)
+        break;
+    case clik::QpKernel::jit:
         e = h->jit_solve(h->d_img, &tk, (long long)B, q, x, y, dq, dx, slack, status, hot_set, use_hot,
                          (hipStream_t)stream, t_inst);
-    else if (h->static_k >= 0)
+        break;
+    case clik::QpKernel::aot:
         e = clik::qp_launch_static(h->static_k, h->d_img, tk, (long long)B, q, x, y, dq, dx, slack, status, hot_set,
                                    use_hot, (hipStream_t)stream, t_inst);
-    else if (h->variant < 0)
-        return fail(CLIK_EUNSUPPORTED, "clik_qp_solve_batch: this skill needs a shape-specialised kernel and none "
-                                       "is attached (casclik_amd.jit needs hipcc)");
-    else
-    {
+        break;
+    case clik::QpKernel::dynamic:
         if (clik::qp_variant_uses_workspace(h->variant) && (hipStream_t)stream == hipStreamPerThread)
             return fail(CLIK_EUNSUPPORTED, "clik_qp_solve_batch: this skill's kernel keeps its work area in global memory, "
                                            "owned by the handle and ordered per stream - hipStreamPerThread is not supported "
@@ -1577,6 +1579,10 @@ static int qp_solve_common(const clik_qp* h, int64_t B, const double* tterms, co
         if (e == hipErrorStreamCaptureUnsupported)
             return fail(CLIK_EHIP, "qp_solve_kernel launch: the work area of this skill's kernel must grow for this batch "
                                    "size, which cannot be captured - run one tick of this batch size before capturing");
+        break;
+    default:
+        return fail(CLIK_EUNSUPPORTED, "clik_qp_solve_batch: this skill needs a shape-specialised kernel and none "
+                                       "is attached (casclik_amd.jit needs hipcc)");
     }
     if (e != hipSuccess) return hipfail(e, "qp_solve_kernel launch");
     return CLIK_OK;
@@ -1608,11 +1614,11 @@ extern "C" int clik_qp_data_batch(const clik_qp* h, int64_t B, const double* tte
     if (rc) return rc;
     if (B == 0) return CLIK_OK;
     if (!Hdiag || !A || !lbA || !ubA) return fail(CLIK_EINVAL, "output pointers required");
-    if (skill_has_extern(h->host) ||
-        (skill_has_wide_task(h->host) && (h->variant < 0 || clik::qp_variant_width(h->variant) <= CLIK_DYN_MAX_M)))
+    const clik::QpKernel k = clik::qp_select(h->host.shape, h->policy, qp_kernels(h), (long long)B, false, clik::QpOp::data);
+    if (k == clik::QpKernel::needs_instance)
         return fail(CLIK_EUNSUPPORTED, "clik_qp_data_batch: not available for skills that only the "
                                        "shape-specialised kernels serve (generated rows, > 8 rows per constraint)");
-    if (h->variant < 0)
+    if (k == clik::QpKernel::none)
         return fail(CLIK_EUNSUPPORTED, "clik_qp_data_batch: the skill exceeds the built-in kernel's limits");
     TickArgs tk;
     rc = fill_tick(h->host, tterms, &tk);

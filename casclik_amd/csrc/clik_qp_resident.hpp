@@ -14,8 +14,6 @@ namespace clik {
 // every instance's working set stays in a register from tick to tick: every tick after the first is hot-started, as the
 // reference's qpOASES instance is (reactive_qp.py:491-513).  Lane r of a quad requests elements 2r, 2r + 1 of its
 // instance's robot_var / input_var rows and stores the same elements of the velocity and slack rows; lane 0 the status.
-template <const ShapeDesc& SD>
-constexpr bool qp_resident_ok() { return qp_front4_ok<SD>() && SD.n_x == 0; }
 template <const ShapeDesc& SD, class IMGV>
 __global__ __launch_bounds__(WAVE) void qp_resident_box_front4_kernel(
     const double* q, const double* y, double* dq, double* slack_out, int32_t* status_out, const long long B,
@@ -193,7 +191,7 @@ inline hipError_t launch_qp_resident_values(const TickArgs& tk, long long B, con
                                             double* slack, int32_t* status, void* ticket, unsigned* done, int n_ticks,
                                             unsigned long long budget, hipStream_t stream)
 {
-    if constexpr (qp_resident_ok<SD>()) {
+    if constexpr (qp_resident_ok(SD)) {
         const unsigned grid = (unsigned)((B + 15) / 16);
         int dev = 0, cus = 0, per_cu = 0;
         hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, qp_resident_box_front4_kernel<SD, IMGV>, WAVE, 0);

@@ -1,5 +1,5 @@
 // Ahead-of-time instantiations of the shape-specialised ReactiveQPController kernels (clik_qp_static.hpp) for the
-// BASELINE skill structures of clik_shapes_gen.hpp, and the run-time copies of the shape predicates the API asks.
+// BASELINE skill structures of clik_shapes_gen.hpp.
 // Its own translation unit: it compiles beside clik_qp.hip (the dynamic-shape kernels) instead of behind it - together
 // they were one 13-minute compile.
 #include "clik_qp_static.hpp"
@@ -33,19 +33,6 @@ int qp_pick_static(const ShapeDesc& sd)
     return -1;
 }
 const char* qp_static_name(int k) { return (k >= 0 && k < kNumQpShapes) ? kQpShapes[k].name : "none"; }
-bool qp_box_family_rt(const ShapeDesc& sd) { return CLIK_QP_BOX_OK(sd); }
-// rows the shape-specialised kernels hand to their active set: soft equalities folded, hard bounds on the same state merged
-int qp_plan_rows_rt(const ShapeDesc& sd) { return make_qp_plan(sd).nr; }
-// 64-double LDS slots a shape-specialised QP kernel keeps behind the skill image (QpLayout<SD>::SLOTS on the run-time
-// copy of the shape): the primal families (bound-constrained, mixed) keep no dual Hessian there
-int qp_layout_slots_rt(const ShapeDesc& sd)
-{
-    const QpPlanS p = make_qp_plan(sd);
-    const bool primal = CLIK_QP_BOX_OK(sd) || CLIK_QP_MIXED_OK(sd);
-    const int n = sd.n, ny = sd.n_y > 0 ? sd.n_y : 0, nra = p.nr > 0 ? p.nr : 1, nsa = p.ns > 0 ? p.ns : 1;
-    const int nt = nra * (nra + 1) / 2;
-    return n + ny + (primal ? 0 : nt) + 2 * nra + (primal ? 0 : nra) + (primal ? 0 : nra * n) + nsa;
-}
 hipError_t qp_launch_static(int k, const void* d_img, const TickArgs& tk, long long B, const double* q,
                             const double* x, const double* y, double* dq, double* dx, double* slack,
                             int32_t* status, int32_t* hot_set, int use_hot, hipStream_t stream,

@@ -21,6 +21,7 @@
 // oracle, tolerance QP_RTOL).
 #pragma once
 #include "clik_pinv_kernels.hpp"
+#include "clik_qp_select.hpp"
 
 namespace clik {
 
@@ -466,148 +467,6 @@ __device__ __forceinline__ int gi_solve(const double* Qs, const double* lbs, con
     return status;
 }
 
-// ---- compile-time plan of the reduced QP ---------------------------------------------
-constexpr int QPS_MAX_ROWS = 16;       // active-set rows a static QP kernel carries in registers
-
-struct QpPlanS {
-    int  nr;                               // rows handed to the active-set solver
-    int  row_task[CLIK_MAX_QPROWS];
-    int  row_local[CLIK_MAX_QPROWS];
-    int  ns;                               // slack variables (= soft rows, in row order)
-    int  slack_base[SHAPE_MAX_TASKS];      // first slack of a soft task
-    bool folded[SHAPE_MAX_TASKS];          // soft equality: eliminated into P, g
-    // active-set row of output i of a task that is not folded, and whether it shares that row with an
-    // earlier constraint: two hard joint-space rows on the same state (joint limits  lb <= dq_i <= ub  from a
-    // SetConstraint on q and the speed limit  -v <= dq_i <= v  of a VelocitySetConstraint on q - the pair
-    // every UR5 notebook stacks, e.g. ur5_dual_quaternion_vs_transformation_matrix.ipynb cell 14) are ONE
-    // row  max(lb) <= dq_i <= min(ub): same feasible set, same minimiser, half the active-set size.
-    int  row_of[SHAPE_MAX_TASKS][CLIK_MAX_M];
-    bool merged[SHAPE_MAX_TASKS][CLIK_MAX_M];
-};
-
-constexpr QpPlanS make_qp_plan(const ShapeDesc& sd)
-{
-    QpPlanS p{};
-    for (int ti = 0; ti < sd.n_tasks; ++ti) {
-        const int cls = sd.cls[ti];
-        const bool soft = sd.soft[ti] != 0;
-        p.slack_base[ti] = p.ns;
-        if (soft) p.ns += sd.m[ti];
-        p.folded[ti] = soft && (cls == CLIK_CLS_EQ || cls == CLIK_CLS_VELEQ);
-        if (!p.folded[ti]) {
-            const bool box = !soft && shape_unit(sd, ti) && (cls == CLIK_CLS_SET || cls == CLIK_CLS_VELSET);
-            for (int i = 0; i < sd.m[ti]; ++i) {
-                int same = -1;
-                if (box)
-                    for (int r = 0; r < p.nr && r < CLIK_MAX_QPROWS && same < 0; ++r) {
-                        const int t2 = p.row_task[r];
-                        const bool box2 = sd.soft[t2] == 0 && shape_unit(sd, t2) &&
-                                          (sd.cls[t2] == CLIK_CLS_SET || sd.cls[t2] == CLIK_CLS_VELSET);
-                        if (box2 && sd.ucol[t2][p.row_local[r]] == sd.ucol[ti][i]) same = r;
-                    }
-                if (same >= 0) {
-                    p.row_of[ti][i] = same;
-                    p.merged[ti][i] = true;
-                    continue;
-                }
-                p.row_of[ti][i] = p.nr;
-                if (p.nr < CLIK_MAX_QPROWS) {
-                    p.row_task[p.nr] = ti;
-                    p.row_local[p.nr] = i;
-                }
-                ++p.nr;
-            }
-        }
-    }
-    return p;
-}
-
-// Box family: after the soft equalities are folded into P and g, every remaining row is a HARD bound on one
-// state variable (joint-limit SetConstraint / speed-limit VelocitySetConstraint on q, merged per state):
-//     min 1/2 v'P v - g'v   s.t.  lb_c <= v_c <= ub_c  on the bounded states c
-// (BASELINE config 4 and the QP stacks of the UR5 notebooks).  Such a QP is solved by a primal active-set
-// iteration on the states (qp_box_pas) instead of the dual active-set iteration over rows.
-constexpr bool qp_box_family(const ShapeDesc& sd)
-{
-    const QpPlanS p = make_qp_plan(sd);
-    if (p.nr <= 0 || p.nr > CLIK_MAX_DOF) return false;
-    for (int r = 0; r < p.nr; ++r) {
-        const int ti = p.row_task[r];
-        if (sd.soft[ti] != 0 || !shape_unit(sd, ti)) return false;
-        if (sd.cls[ti] != CLIK_CLS_SET && sd.cls[ti] != CLIK_CLS_VELSET) return false;
-    }
-    return true;
-}
-// Solvers measured for this family on config 4 (16384 instances, cold / hot start per tick, same box):
-//   dual active-set iteration over rows (gi_solve, what every other QP shape runs)      38.7 / 10.4 us
-//   projected Newton (round 2, tools/experiments/qp_retired.patch)                      38.5 / 25.8 us
-//   block principal pivoting (first attempt, history)                                   93   /  7.4 us
-//   primal active set from the vertex the linear term points to, qp_box_pas (default)   see DESIGN.md section 5
-// The tick is the slowest instance of the batch (every wave has a SIMD to itself), i.e. its pass count times the
-// instructions of a pass: the dual iteration needs 11-13 passes of ~1000 instructions on the worst instance, the
-// projected Newton 10 of ~1500, the primal active set up to 19 of ~350 (mean 3.3): only 0-3 of the 7 states are
-// free at the optimum, so a method that starts from a vertex and frees one state per pass is there quickly, and
-// a pass is one masked 7 x 7 factorisation with everything in registers.  -DCLIK_QP_BOX_OFF: this family runs the
-// dual iteration like the others (regression switch).
-#if defined(CLIK_QP_BOX_OFF)
-#define CLIK_QP_BOX_OK(SD) false
-#else
-#define CLIK_QP_BOX_OK(SD) qp_box_family(SD)
-#endif
-
-// Mixed family (round 3): the rows left after folding are hard bounds on single states (the box), a few HARD
-// GENERAL rows (a SetConstraint on a task-space expression - the wall sets of ur5_moe2016_example2.ipynb cell 6 -
-// reactive_qp.py:221-225; hard equalities), and SOFT inequality rows.  A soft inequality row  lb <= a v - s <= ub
-// with cost 1/2 h s^2  is exactly a bounded variable  w = a v - s in [lb, ub]  with cost  1/2 h (a v - w)^2: it is
-// LIFTED into the box (z = [v; w]).  The hard general rows enter a primal active set next to the held states
-// (qp_mixed_pas).  Row kinds, in plan order:
-constexpr int QPK_BOX = 0, QPK_HARD = 1, QPK_LIFT = 2;
-#ifndef CLIK_QP_MIXED_MAX_Z
-#define CLIK_QP_MIXED_MAX_Z 8          // states + lifted rows carried in registers
-#endif
-#ifndef CLIK_QP_MIXED_MAX_H
-#define CLIK_QP_MIXED_MAX_H 3          // hard general rows
-#endif
-constexpr int qp_row_kind(const ShapeDesc& sd, const QpPlanS& p, int r)
-{
-    const int ti = p.row_task[r];
-    if (sd.soft[ti] != 0) return QPK_LIFT;
-    if (shape_unit(sd, ti) && (sd.cls[ti] == CLIK_CLS_SET || sd.cls[ti] == CLIK_CLS_VELSET)) return QPK_BOX;
-    return QPK_HARD;
-}
-constexpr int qp_kind_count(const ShapeDesc& sd, int kind)
-{
-    const QpPlanS p = make_qp_plan(sd);
-    int n = 0;
-    for (int r = 0; r < p.nr && r < CLIK_MAX_QPROWS; ++r) n += qp_row_kind(sd, p, r) == kind;
-    return n;
-}
-// index of row r among the rows of its kind
-constexpr int qp_kind_index(const ShapeDesc& sd, int r)
-{
-    const QpPlanS p = make_qp_plan(sd);
-    const int kind = qp_row_kind(sd, p, r);
-    int n = 0;
-    for (int q = 0; q < r; ++q) n += qp_row_kind(sd, p, q) == kind;
-    return n;
-}
-constexpr bool qp_mixed_family(const ShapeDesc& sd)
-{
-    const QpPlanS p = make_qp_plan(sd);
-    if (p.nr <= 0 || p.nr > CLIK_MAX_QPROWS || qp_box_family(sd)) return false;
-    const int nl = qp_kind_count(sd, QPK_LIFT), nh = qp_kind_count(sd, QPK_HARD);
-    if (nl + nh == 0) return false;
-    // (skills with generated attribute code keep the dual iteration: its row bounds come through another path)
-    // (registers: the packed matrix and its factor dominate - without hard rows one more variable fits;
-    // measured on the 6-DoF + 3 soft walls skill: 256 VGPRs + 155 AGPRs, no scratch)
-    return sd.n + nl <= CLIK_QP_MIXED_MAX_Z + (nh == 0 ? 1 : 0) && nh <= CLIK_QP_MIXED_MAX_H;
-}
-#if defined(CLIK_QP_MIXED_OFF) || defined(CLIK_QP_BOX_OFF)
-#define CLIK_QP_MIXED_OK(SD) false
-#else
-#define CLIK_QP_MIXED_OK(SD) qp_mixed_family(SD)
-#endif
-
 template <const ShapeDesc& SD>
 struct QpLayout {
     static constexpr QpPlanS P = make_qp_plan(SD);
@@ -625,17 +484,17 @@ struct QpLayout {
     static constexpr size_t TAIL_OFF = (sizeof(Img<SD>) + 15) & ~(size_t)15;
     static constexpr int IMG_CHUNKS = (int)((TAIL_OFF + sizeof(QpTail) + 1023) / 1024);
     static constexpr int IMG_DOUBLES = IMG_CHUNKS * 128;
-    // 64-double slots behind the image
-    static constexpr int O_Z = 0;
-    static constexpr int O_Y = O_Z + N;
-    static constexpr int O_Q = O_Y + NY;
-    static constexpr bool PRIMAL = BOX || MIXED;            // (the primal solvers keep no Q / Y / c0 in LDS)
-    static constexpr int O_LB = O_Q + (PRIMAL ? 0 : NT);
-    static constexpr int O_UB = O_LB + NRA;
-    static constexpr int O_C0 = O_UB + NRA;
-    static constexpr int O_YS = O_C0 + (PRIMAL ? 0 : NRA);      // P^-1 a_r'  (NR x N)
-    static constexpr int O_SL = O_YS + (PRIMAL ? 0 : NRA * N);  // folded right-hand sides, then the slack output rows
-    static constexpr int SLOTS = O_SL + NSA;
+    // 64-double slots behind the image (qp_slot_layout)
+    static constexpr QpSlotLayout L = qp_slot_layout(SD);
+    static constexpr int O_Z = L.o_z;
+    static constexpr int O_Y = L.o_y;
+    static constexpr int O_Q = L.o_q;
+    static constexpr int O_LB = L.o_lb;
+    static constexpr int O_UB = L.o_ub;
+    static constexpr int O_C0 = L.o_c0;
+    static constexpr int O_YS = L.o_ys;
+    static constexpr int O_SL = L.o_sl;
+    static constexpr int SLOTS = L.slots;
     static constexpr size_t LDS_BYTES = ((size_t)IMG_DOUBLES + (size_t)SLOTS * WAVE) * sizeof(double);
 };
 
@@ -1990,10 +1849,7 @@ __global__ __launch_bounds__(WAVE) void qp_solve_static_box_values_hot_kernel(
 // tick with different relaxation factors - "quad4", profiles/r3_qp_portfolio_study.md -; and launched ticks with four
 // lanes per instance that share the sin / cos evaluations - "front4": cold ticks +1.5 - 2 %, hot ticks 0.25 - 0.7 us SLOWER
 // although each wave issues 266 instructions fewer, profiles/r5_quad_ab.txt.  The RESIDENT kernel below keeps that
-// four-lane front end: there nobody pays for launching four times the waves.)
-template <const ShapeDesc& SD>
-constexpr bool qp_front4_ok() { return QpLayout<SD>::BOX && SD.uses_fk != 0 && SD.n >= 3 && SD.n <= 8; }
-
+// four-lane front end (qp_front4_ok, clik_qp_select.hpp): there nobody pays for launching four times the waves.)
 }  // namespace clik
 #include "clik_qp_resident.hpp"     // resident ticks of the bound-constrained family (qp_resident_box_front4_kernel)
 namespace clik {
@@ -2259,42 +2115,13 @@ inline hipError_t launch_qp_rollout_static_values(const double* d_tterms, int n_
     }
 }
 
-// which value-specialised QP kernel serves a batch (ONE predicate: the launcher below and the label
-// clik_jit_qp_value_variant hands to the controllers / bench.py both call it)
-enum QpValueKernel { QPV_GENERAL = 0, QPV_LONE, QPV_FOLIO };
-inline int current_device_cus()
-{
-    // (per CURRENT device: a process may drive several, or a partition of one)
-    static int cached[16] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (dev >= 0 && dev < 16 && cached[dev] > 0) return cached[dev];
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (dev >= 0 && dev < 16) cached[dev] = cus;
-    return cus;
-}
+// the launcher's side of qp_value_select (the CU count is asked only where it can decide)
 template <const ShapeDesc& SD>
 inline QpValueKernel qp_values_choice(long long B, int use_hot)
 {
-    if constexpr (!QpLayout<SD>::BOX) {
-        return QPV_GENERAL;
-    } else {
-        const long long grid = (B + WAVE - 1) / WAVE;
-        // (CLIK_QP_FOLIO=0 / 1: the four-waves-per-64-instances kernel for cold ticks of small batches)
-        // default: up to ONE block per CU (16384 instances on 256 CUs) - measured per tick against the lone-wave kernel:
-        // 10.2 / 11.0 us at 1024 instances, 10.4 / 12.0 at 4096, 11.0 / 12.0 at 8192, 11.2 / 12.1 at 12288, the same at 256
-        // and 2048, 11.0 - 11.1 / 11.3 at 16384 (four identical waves cost 12.2 - 12.5 us there - slower waves, not a slower dispatch:
-        // tools/stamp_folio.py - and the different starts win 1.3 - 1.6 back, 0.4 of it through the second look half-way
-        // through a pass; six input seeds: -7 % on average, every one a gain); CLIK_QP_FOLIO=0 never
-        // (profiles/r4_qp_wave_portfolio.txt)
-        static const int folio = []() {
-            const char* e = getenv("CLIK_QP_FOLIO");
-            return e ? ((e[0] == '1') ? 2 : 0) : 1;
-        }();
-        if (folio != 0 && !use_hot && grid <= (long long)current_device_cus()) return QPV_FOLIO;
-        return QPV_LONE;
-    }
+    constexpr bool box = QpLayout<SD>::BOX;
+    const bool folio = qp_env().folio;
+    return qp_value_select(box, folio, B, use_hot != 0, (box && folio && !use_hot) ? current_device_cus() : 0);
 }
 template <const ShapeDesc& SD>
 inline const char* qp_values_variant(long long B, int use_hot)
@@ -2312,11 +2139,10 @@ inline hipError_t launch_qp_static_values(const TickArgs& tk, long long B, const
 {
     const unsigned grid = (unsigned)((B + WAVE - 1) / WAVE);
     if constexpr (QpLayout<SD>::BOX) {
-        static const int folio_same = []() { const char* e = getenv("CLIK_QP_FOLIO_SAME"); return (e && e[0] == '1') ? 1 : 0; }();
         switch (qp_values_choice<SD>(B, use_hot)) {
         case QPV_FOLIO:
             hipLaunchKernelGGL((qp_solve_static_box_folio_values_kernel<SD, IMGV>), dim3(grid), dim3(kFolioWaves * WAVE), 0,
-                               stream, q, y, dq, slack, status, B, x, dx, hot_set, tk, folio_same);
+                               stream, q, y, dq, slack, status, B, x, dx, hot_set, tk, qp_env().folio_same ? 1 : 0);
             return hipGetLastError();
         default:
             break;
@@ -2492,11 +2318,6 @@ __global__ __launch_bounds__(WAVE) void qp_rollout_static_kernel(
     if (status_out != nullptr && valid) status_out[b0 + lane] = worst;
 }
 
-// stages: controller evaluations per tick (1 explicit Euler, 4 classical Runge-Kutta)
-typedef hipError_t (*qp_static_rollout_fn)(const void*, const double*, int, double, double, long long, double*,
-                                           const double*, double*, double*, int32_t*, double*, double*, hipStream_t,
-                                           int);
-
 template <const ShapeDesc& SD>
 inline hipError_t launch_qp_rollout_static(const void* d_img, const double* d_tterms, int n_ticks, double dt,
                                            double max_speed, long long B, double* q, const double* y, double* dq,
@@ -2507,7 +2328,7 @@ inline hipError_t launch_qp_rollout_static(const void* d_img, const double* d_tt
     const unsigned grid = (unsigned)((B + WAVE - 1) / WAVE);
     if (stages == 4) {
         constexpr size_t shmem = QpLayout<SD>::LDS_BYTES + (size_t)2 * SD.n * WAVE * sizeof(double);
-        static_assert(shmem <= 160u * 1024u, "Runge-Kutta QP rollout needs more LDS than a CU has");
+        static_assert(shmem <= kLdsBytesPerCu, "Runge-Kutta QP rollout needs more LDS than a CU has");
         if (shmem > 64 * 1024) {
             hipError_t e = hipFuncSetAttribute((const void*)qp_rollout_static_kernel<SD, true>,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
@@ -2528,11 +2349,6 @@ inline hipError_t launch_qp_rollout_static(const void* d_img, const double* d_tt
     return hipGetLastError();
 }
 
-// t_inst: null (tk serves the whole batch) or one time-slot record per instance ([B][2 * n_tslots], device)
-typedef hipError_t (*qp_static_fn)(const void*, const TickArgs&, long long, const double*, const double*,
-                                   const double*, double*, double*, double*, int32_t*, int32_t*, int, hipStream_t,
-                                   const double*);
-
 template <const ShapeDesc& SD>
 inline hipError_t launch_qp_static(const void* d_img, const TickArgs& tk, long long B, const double* q,
                                    const double* x, const double* y, double* dq, double* dx, double* slack,
@@ -2541,7 +2357,7 @@ inline hipError_t launch_qp_static(const void* d_img, const TickArgs& tk, long l
 {
     const unsigned grid = (unsigned)((B + WAVE - 1) / WAVE);
     constexpr size_t shmem = QpLayout<SD>::LDS_BYTES;
-    static_assert(shmem <= 160u * 1024u, "static QP kernel needs more LDS than a CU has");
+    static_assert(shmem <= kLdsBytesPerCu, "static QP kernel needs more LDS than a CU has");
     if (shmem > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)qp_solve_static_kernel<SD>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);

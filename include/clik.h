@@ -215,9 +215,9 @@ int clik_pinv_n_modes(const clik_pinv* h);
  * instantiation for the skill's structure) or "dynamic" (run-time guards).   */
 const char* clik_pinv_kernel_name(const clik_pinv* h);
 /* which variant of that kernel a batch of B instances gets: "team4" (four lanes per instance,
- * small batches of the priority-stack family), "mp2"/"mp4" (one wave per mode), "split", "lane"
- * (one instance per lane), "lane/occ2" (its large-batch build), "team4v" (team4 with the skill's
- * numbers compiled in) or "dynamic".                                                    */
+ * small batches of the priority-stack family), "mp2"/"mp4" (one wave per mode), "lane" (one
+ * instance per lane), "lane/occ2" (its large-batch build), "team4v" / "quadv" / "lanev" (with the
+ * skill's numbers compiled in) or "dynamic".                                            */
 const char* clik_pinv_kernel_variant(const clik_pinv* h, int64_t B);
 /* developer aid (host only, no GPU needed): writes the C++ ShapeDesc initialiser
  * this skill maps to into buf; returns 1 if the skill is eligible for an AOT
@@ -368,8 +368,14 @@ int clik_qp_n_rows(const clik_qp* h);
  * so far needed, at most the device's resident blocks; grown by retiring the smaller area (captured graphs stay
  * valid); released by clik_qp_destroy.  See INTEGRATION.md. */
 int64_t clik_qp_workspace_bytes(const clik_qp* h);
-/* kernel serving the skill: an AOT shape name, "jit_<hash>" or "dynamic"       */
+/* kernel serving the skill: an AOT shape name, "jit_<hash>", "dynamic" or "none" (only an instantiated kernel
+ * can serve it; none is attached)                                                                             */
 const char* clik_qp_kernel_name(const clik_qp* h);
+/* what follows that name for a tick of B instances (hot != 0: hot-started): "" (the kernel named), "/v" (the
+ * value-specialised tick, clik_qp_attach_value_kernel) or "/v/folio4" (its cold tick of up to one block of 64
+ * instances per CU of the device the handle was created on: four waves per 64 instances; CLIK_QP_FOLIO=0 never).
+ * The launcher decides by the same predicate.  A host-only handle counts no CUs.                              */
+const char* clik_qp_kernel_variant(const clik_qp* h, int64_t B, int32_t hot);
 /* as clik_shape_describe / clik_pinv_attach_kernel, for the QP controller: the
  * shape-specialised QP kernel (soft equalities eliminated, active set over the
  * remaining rows) is instantiated per skill structure; reactive_qp.py:283-298

@@ -124,6 +124,78 @@ def test_host_only_handles_answer_queries_and_refuse_to_solve(lib, monkeypatch):
     assert words and len(words) > 100
 
 
+# kernel_name + clik_qp_kernel_variant of the config-4 skill on the iiwa and on the UR5 (shape-specialised kernels from
+# the ahead-of-time table, box family) and of a hard pose task (no AOT shape: the built-in kernel), with one switch set at
+# a time, for the image-reading kernels and with a value-specialised kernel attached.  A host-only handle counts no CUs, so no batch gets the four-waves cold tick
+# (the GPU tests pin that one); every batch size and start gets the same label.
+_QP_SELECT_B = (1, 64, 4096, 16384, 16385, 131072, 1 << 20)
+_QP_SELECT_ENV = (None, "CLIK_FORCE_DYNAMIC=1", "CLIK_NO_AOT=1", "CLIK_QP_FOLIO=0")
+_QP_SELECT_TABLE = {
+    # (skill, switch, value kernel attached): label
+    ("config4_iiwa", None, False): "qp_static_kQpPoseIiwa",
+    ("config4_iiwa", None, True): "qp_static_kQpPoseIiwa/v",
+    ("config4_iiwa", "CLIK_FORCE_DYNAMIC=1", False): "dynamic",
+    ("config4_iiwa", "CLIK_FORCE_DYNAMIC=1", True): "dynamic",
+    ("config4_iiwa", "CLIK_NO_AOT=1", False): "dynamic",
+    ("config4_iiwa", "CLIK_NO_AOT=1", True): "dynamic",
+    ("config4_iiwa", "CLIK_QP_FOLIO=0", False): "qp_static_kQpPoseIiwa",
+    ("config4_iiwa", "CLIK_QP_FOLIO=0", True): "qp_static_kQpPoseIiwa/v",
+    ("config4_ur5", None, False): "qp_static_kQpPoseUr5",
+    ("config4_ur5", None, True): "qp_static_kQpPoseUr5/v",
+    ("config4_ur5", "CLIK_FORCE_DYNAMIC=1", False): "dynamic",
+    ("config4_ur5", "CLIK_FORCE_DYNAMIC=1", True): "dynamic",
+    ("config4_ur5", "CLIK_NO_AOT=1", False): "dynamic",
+    ("config4_ur5", "CLIK_NO_AOT=1", True): "dynamic",
+    ("config4_ur5", "CLIK_QP_FOLIO=0", False): "qp_static_kQpPoseUr5",
+    ("config4_ur5", "CLIK_QP_FOLIO=0", True): "qp_static_kQpPoseUr5/v",
+    ("hard_pose_iiwa", None, False): "dynamic",
+    ("hard_pose_iiwa", None, True): "dynamic",
+    ("hard_pose_iiwa", "CLIK_FORCE_DYNAMIC=1", False): "dynamic",
+    ("hard_pose_iiwa", "CLIK_FORCE_DYNAMIC=1", True): "dynamic",
+    ("hard_pose_iiwa", "CLIK_NO_AOT=1", False): "dynamic",
+    ("hard_pose_iiwa", "CLIK_NO_AOT=1", True): "dynamic",
+    ("hard_pose_iiwa", "CLIK_QP_FOLIO=0", False): "dynamic",
+    ("hard_pose_iiwa", "CLIK_QP_FOLIO=0", True): "dynamic",
+}
+
+
+@pytest.mark.parametrize("skill", ["config4_iiwa", "config4_ur5", "hard_pose_iiwa"])
+@pytest.mark.parametrize("env", _QP_SELECT_ENV)
+def test_qp_kernel_selection_table(lib, monkeypatch, skill, env):
+    """The kernel choice of the QP path (qp_select, clik_qp_select.hpp) against a written-out table, on host-only handles:
+    a host-only handle picks its ahead-of-time shape as a device handle does and reports the same kernel name.  The
+    switches are read at creation; the value-specialised kernel is a stand-in that is never called, and a handle that no
+    shape-specialised kernel serves refuses it."""
+    import casclik_amd as cc
+    for name in ("CLIK_FORCE_DYNAMIC", "CLIK_NO_AOT", "CLIK_QP_FOLIO", "CLIK_HOST_ONLY"):
+        monkeypatch.delenv(name, raising=False)
+    if env:
+        monkeypatch.setenv(*env.split("="))
+    fk = skills.ur5() if skill == "config4_ur5" else skills.iiwa()
+    spec = skills.pose_skill(fk) if skill == "hard_pose_iiwa" else skills.qp_skill(fk)
+    d = lower_skill(spec)
+    qc = cc.ReactiveQPController(skill_spec=spec)
+    state_w = list(qc._robot_var_weights) + list(qc._virtual_var_weights[:d.n_x])
+    copts = _capi.qp_opts_to_c(qc.weight_shifter, state_w, list(qc._slack_var_weights))
+    desc = _capi.desc_to_c(d)
+    h = C.c_void_p()
+    assert lib.clik_qp_create_host(C.byref(desc), C.byref(copts), C.byref(h)) == 0
+    try:
+        def labels():
+            name = lib.clik_qp_kernel_name(h).decode()
+            return {name + lib.clik_qp_kernel_variant(h, B, hot).decode() for B in _QP_SELECT_B for hot in (0, 1)}
+        assert labels() == {_QP_SELECT_TABLE[(skill, env, False)]}
+
+        def never(*args):
+            raise AssertionError("the stand-in value kernel was called")
+        stand_in = C.CFUNCTYPE(C.c_int)(never)
+        shape_served = _QP_SELECT_TABLE[(skill, env, False)].startswith("qp_static_")
+        assert lib.clik_qp_attach_value_kernel(h, C.cast(stand_in, C.c_void_p), None) == \
+            (0 if shape_served else _capi.CLIK_EUNSUPPORTED)
+        assert labels() == {_QP_SELECT_TABLE[(skill, env, True)]}
+    finally:
+        assert lib.clik_qp_destroy(h) == 0
+
 def test_ticket_layout(tmp_path):
     """clik_ticket (resident ticks): 256 bytes, the words the Python layer indexes"""
     src = tmp_path / "tk.c"

@@ -10,7 +10,7 @@
     with an independent solve (scipy SLSQP) of the same problem."""
 import numpy as np
 import pytest
-from hypothesis import given, settings, strategies as st
+from hypothesis import example, given, settings, strategies as st
 
 import casclik_amd as cc
 from casclik_amd import sym as cs
@@ -73,6 +73,8 @@ def test_accepted_mode_is_the_first_whose_inactive_sets_are_in_their_tangent_con
 
 @settings(max_examples=25, deadline=None)
 @given(seed=st.integers(0, 10 ** 6))
+@example(seed=13)           # (SLSQP leaves a row by 2.7e-8 and undercuts the oracle's cost by 1.3e-6: see below)
+@example(seed=482)
 def test_qp_answers_are_kkt_points_and_agree_with_an_independent_solver(seed):
     from scipy.optimize import minimize
     rng = np.random.default_rng(seed)
@@ -100,8 +102,17 @@ def test_qp_answers_are_kkt_points_and_agree_with_an_independent_solver(seed):
         # (SLSQP sometimes stops with "positive directional derivative" AT the minimum: its point is judged by its rows
         # and its cost - no feasible point may undercut the oracle's, and SLSQP's own should not be worse by much)
         rows = Am[b].dot(res.x)
-        feasible = (rows >= np.clip(lb[b], -1e9, 1e9) - 1e-7).all() and (rows <= np.clip(ub[b], -1e9, 1e9) + 1e-7).all()
-        if feasible:
-            assert fun(x) <= fun(res.x) + 1e-7 * (1.0 + fun(x)), (fun(res.x), fun(x))
+        lo, hi = np.clip(lb[b], -1e9, 1e9), np.clip(ub[b], -1e9, 1e9)
+        viol = np.maximum(np.maximum(lo - rows, rows - hi), 0.0)
+        if (viol <= 1e-7).all():
+            # (a point counted as feasible may still leave a row by up to 1e-7, and leaving row i by d lowers the cost
+            # by at most 2 |lam_i| d - convexity, lam: the oracle's multipliers of 1/2 v'Hv on its active rows; with
+            # multipliers of 50 that is 1e-5, above the tolerance: only exactly feasible points are held to it alone)
+            Ax = Am[b].dot(x)
+            scale = np.maximum(1.0, np.maximum(np.abs(lo), np.abs(hi)))
+            act = np.where((np.abs(Ax - lo) <= 1e-8 * scale) | (np.abs(Ax - hi) <= 1e-8 * scale))[0]
+            lam = np.linalg.lstsq(Am[b][act].T, H[b] * x, rcond=None)[0] if act.size else np.zeros(0)
+            slack_of_rows = 2.0 * float(np.abs(lam).dot(viol[act]))
+            assert fun(x) <= fun(res.x) + slack_of_rows + 1e-7 * (1.0 + fun(x)), (fun(res.x), fun(x), slack_of_rows)
         if res.success:
             assert abs(fun(res.x) - fun(x)) < 1e-6 * (1.0 + fun(x)), (fun(res.x), fun(x))
