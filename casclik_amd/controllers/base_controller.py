@@ -1,22 +1,23 @@
 """Shared plumbing of the device controllers.
 
 ``BaseController`` keeps the reference's ``controller_type<label>`` repr
-(reference: casclik/controllers/base_controller.py:1-6).  The helpers move
-batches between numpy / torch and the device pointers the C ABI takes; torch
-is used purely as the device allocator and stream provider.
+(reference: casclik/controllers/base_controller.py:1-6) and carries everything
+of a device controller that is not controller mathematics: the handle's
+lifetime, set-up, batch marshalling, per-instance time, rollout times, resident
+ticks and the staging of ``solve()``.  The helpers move batches between numpy /
+torch and the device pointers the C ABI takes; torch is used purely as the
+device allocator and stream provider.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
+import warnings
 
 import numpy as np
 
-
-class BaseController(object):
-    controller_type = "BaseController"
-
-    def __repr__(self):
-        return self.controller_type + "<" + self.skill_spec.label + ">"
+from .. import _capi
+from ..lowering import lower_skill
 
 
 def _torch():
@@ -156,7 +157,6 @@ class SingleSlot(object):
     (pinned -> device copy, launch, device -> pinned copy)."""
 
     def __init__(self, device, n_in, n_out, n_int):
-        import os
         torch = _torch()
         self.device = device
         self.zero_copy = os.environ.get("CLIK_SOLVE_STAGED", "0") != "1"
@@ -210,3 +210,245 @@ class SingleSlot(object):
         st = self._stream if self._stream is not None else torch.cuda.current_stream(self.device)
         self._stream = None
         st.synchronize()
+
+
+def scalar_of(v):
+    if hasattr(v, "toarray"):
+        v = v.toarray()
+    return np.asarray(v, dtype=float).reshape(-1)[0]
+
+
+def flat_vector(v, n, what):
+    if hasattr(v, "toarray"):
+        v = v.toarray()
+    arr = np.asarray(v, dtype=np.float64).reshape(-1)
+    if arr.size != n:
+        raise ValueError("%s must have %d entries, got %d" % (what, n, arr.size))
+    return arr
+
+
+class BaseController(object):
+    """What a device controller is apart from its mathematics.  A controller class names the C entry points that make
+    and free its handle (``_create_fn`` / ``_destroy_fn``), returns their options structure from ``_c_options()``, says
+    in ``_slot_results()`` how many doubles and int32 its ``solve()`` brings back, and has ``skill_spec`` and
+    ``options``; ``_create_handle()`` then gives it ``_lib``, ``_handle``, ``_device`` and ``descriptor``, which every
+    other helper here works from."""
+    controller_type = "BaseController"
+    _create_fn = _destroy_fn = None
+
+    def __repr__(self):
+        return self.controller_type + "<" + self.skill_spec.label + ">"
+
+    # -- handle lifetime ----------------------------------------------------------------------------------------
+    def __del__(self):
+        self._release()
+
+    def _release(self):
+        if getattr(self, "_handle", None) is not None and self._lib is not None:
+            try:
+                getattr(self._lib, self._destroy_fn)(self._handle)
+            except Exception:
+                pass
+            self._handle = None
+        self._slot = None
+
+    def _require_handle(self):
+        if self._handle is None:
+            raise RuntimeError("call setup_problem_functions() / setup_solver() first")
+
+    # -- set-up -------------------------------------------------------------------------------------------------
+    def _create_handle(self):
+        """Lower the skill and create its handle on the controller's device (``options["device"]``, by default the
+        current one).  Returns the C descriptor and options, which the ``jit.attach*`` calls take as well."""
+        self._release()
+        self._lib = _capi.load_library()
+        self.descriptor = lower_skill(self.skill_spec)
+        cdesc = _capi.desc_to_c(self.descriptor)
+        copts = self._c_options()
+        self._device = device_of(self.options.get("device"))
+        handle = C.c_void_p()
+        with _torch().cuda.device(self._device):
+            rc = getattr(self._lib, self._create_fn)(C.byref(cdesc), C.byref(copts), C.byref(handle))
+        _capi.check(self._lib, rc)
+        self._handle = handle
+        return cdesc, copts
+
+    def _want_jit(self):
+        """May kernels be instantiated for this skill at set-up (the reference JIT-compiles at this point too,
+        function_opts["jit"])?  ``CLIK_JIT=0`` and ``CLIK_FORCE_DYNAMIC=1`` say no for the whole process."""
+        fopts = self.options.get("function_opts") or {}
+        return fopts.get("jit", True) and os.environ.get("CLIK_JIT", "1") != "0" \
+            and os.environ.get("CLIK_FORCE_DYNAMIC", "0") != "1"
+
+    def _attach_or_warn(self, attach, instead, limit):
+        """One ``jit.attach*`` call on the controller's device.  A failed instantiation is not fatal when another
+        kernel serves the skill: warn (``instead`` says which one runs, then the first ``limit`` characters of the
+        compiler's message) and return None - still the GPU path; skills only instantiated kernels can serve are
+        refused afterwards (``_require_generated_code_kernel``)."""
+        with _torch().cuda.device(self._device):
+            try:
+                return attach()
+            except RuntimeError as exc:
+                warnings.warn("%s: %s" % (instead, str(exc)[:limit]))
+                return None
+
+    def _require_generated_code_kernel(self):
+        """Constraints outside the row-table family exist only as generated code inside a run-time instantiated
+        kernel; there is no other path (and no CPU fallback)."""
+        d = self.descriptor
+        if d.extern_code and not self.kernel_name.startswith("jit_"):
+            raise NotImplementedError(
+                "the skill has constraint expressions that need generated device code (%s), but no "
+                "kernel could be instantiated for it (jit disabled, hipcc missing, or the skill is "
+                "outside the shape-specialised family)" % ", ".join(
+                    repr(d.tasks[k]["label"]) for k in sorted(d.extern_code)))
+
+    # -- batches in and out -------------------------------------------------------------------------------------
+    def _batch_inputs(self, robot_var, virtual_var=None, input_var=None, clone=False):
+        """The inputs of a batch call as contiguous float64 tensors on the controller's device: ``Q [B, n_q]``,
+        ``X [B, n_x] | None``, ``Y [B, n_y] | None``, the batch size (``robot_var``'s) and whether ``robot_var`` came as
+        numpy (the container type of what the call returns).  Tensors that already are what the kernels read are used
+        in place; ``clone`` copies those of ``Q`` and ``X`` (a rollout overwrites them with the final state)."""
+        d, dev = self.descriptor, self._device
+        Q, was_np = to_device_matrix(robot_var, d.n_q, dev, "robot_var")
+        B = Q.shape[0]
+        X = Y = None
+        x_np = True
+        if d.n_x > 0:
+            if virtual_var is None:
+                raise ValueError("skill has virtual_var: pass virtual_var")
+            X, x_np = to_device_matrix(virtual_var, d.n_x, dev, "virtual_var", B)
+        if d.n_y > 0:
+            if input_var is None:
+                raise ValueError("skill has input_var: pass input_var")
+            Y, _ = to_device_matrix(input_var, d.n_y, dev, "input_var", B)
+        if clone:
+            Q = Q if was_np else Q.clone()
+            X = X if x_np else X.clone()
+        return Q, X, Y, B, was_np
+
+    @staticmethod
+    def _to_caller(outs, was_np):
+        """A tuple of result tensors (or None) in the container type the inputs came in."""
+        return tuple(None if o is None else o.cpu().numpy() for o in outs) if was_np else outs
+
+    # -- per-instance time --------------------------------------------------------------------------------------
+    def _instance_times(self, time_var, B):
+        """``time_var`` of a batch tick -> ``(t, T, stamps)``.  One stamp for the batch: ``(t, None, None)``.  One per
+        instance (robots at different phases of a trajectory): the time-only sub-expressions are evaluated on the host
+        per distinct stamp and travel as the device tensor ``T [B, 2 * n_tslots]`` of the ``*_solve_batch_t`` entry
+        points; ``stamps = (uniq, inverse)`` serves ``_solve_per_stamp``.  A skill without time slots gives the same
+        tick at every stamp: ``(first stamp, None, None)``, the ordinary launch."""
+        if not (np.ndim(time_var) > 0 and np.size(time_var) > 1):
+            return (float(np.asarray(time_var).reshape(-1)[0]) if np.ndim(time_var) > 0 else time_var), None, None
+        d = self.descriptor
+        times = np.asarray(time_var, dtype=float).reshape(-1)
+        if times.size != B:
+            raise ValueError("time_var has %d entries, the batch %d instances" % (times.size, B))
+        if d.n_tslots == 0:
+            return float(times[0]), None, None
+        uniq, inverse = np.unique(times, return_inverse=True)
+        terms = np.stack([d.time_terms(float(tv)) for tv in uniq])
+        T = _torch().from_numpy(np.ascontiguousarray(terms[inverse])).to(self._device)
+        return float(times[0]), T, (uniq, inverse)
+
+    def _solve_per_stamp(self, stamps, solve_one, ins, outs):
+        """Per-instance time for a skill on the dynamic fallback kernel, which has no per-instance-time variant
+        (``CLIK_EUNSUPPORTED``): the batch grouped by distinct time stamp, one launch per group.  ``solve_one(t, *rows
+        of ins)`` is the controller's own single-stamp call; its results land in the same rows of ``outs`` (None
+        entries on either side are skipped)."""
+        torch = _torch()
+        uniq, inverse = stamps
+        for k, tv in enumerate(uniq):
+            rows = torch.from_numpy(np.nonzero(inverse == k)[0]).to(self._device)
+            res = solve_one(float(tv), *[None if t is None else t.index_select(0, rows) for t in ins])
+            for o, r in zip(outs, res):
+                if o is not None:
+                    o.index_copy_(0, rows, r)
+
+    # -- rollouts -----------------------------------------------------------------------------------------------
+    def _rollout_times(self, time_vars, dt, method):
+        """``(n_ticks, stages, tterms)`` of a rollout: ``stages`` is 1 for ``method="rk4"`` (the right-hand side at t,
+        t + dt/2, t + dt/2, t + dt of every tick), 0 for ``"euler"`` (at t); ``tterms`` the ``_capi.tterms_arg`` pair
+        of the time terms of all stage times, one after the other."""
+        if method not in ("euler", "rk4"):
+            raise ValueError("method must be 'euler' or 'rk4'")
+        d = self.descriptor
+        times = np.asarray(time_vars, dtype=float).reshape(-1)
+        stage_times = times
+        if method == "rk4":
+            stage_times = np.stack([times, times + 0.5 * dt, times + 0.5 * dt, times + dt], axis=1).reshape(-1)
+        tt = np.concatenate([d.time_terms(t) for t in stage_times]) if d.n_tslots else np.zeros(0)
+        return int(times.size), 1 if method == "rk4" else 0, _capi.tterms_arg(tt)
+
+    # -- resident ticks -----------------------------------------------------------------------------------------
+    def _resident_setup(self, waves, ring_depth, publish_ahead, stream, time_var):
+        """What a resident launch needs beside its tensors: the ``ticket`` (64 int32 words: [0] in_seq, [16] ring
+        depth, [32] stop, [48] waves, [49] ticks_done), one ``done`` slot per wave, the launch stream (a new one by
+        default) and the time terms.  Returns once they, and the outputs the caller initialised on the current stream,
+        are in place."""
+        torch = _torch()
+        dev = self._device
+        ticket = torch.zeros(64, dtype=torch.int32, device=dev)
+        ticket[16] = ring_depth if ring_depth > 1 else 0
+        if publish_ahead:
+            # tickets 1 .. publish_ahead are valid before the kernel starts (the inputs of those ticks are in place):
+            # no producer has to run next to it - what a profiler that serialises kernels needs
+            ticket[0] = int(publish_ahead)
+        done = torch.zeros(max(waves, 1), dtype=torch.int32, device=dev)
+        stream = stream if stream is not None else torch.cuda.Stream(device=dev)
+        tterms = _capi.tterms_arg(self.descriptor.time_terms(time_var))
+        torch.cuda.current_stream(dev).synchronize()       # (ticket / outputs are initialised before the kernel starts)
+        return ticket, done, stream, tterms
+
+    def resident_wait(self, run):
+        """Wait for a resident run to leave; ticks finished, or ``ResidentWatchdog`` (``base_controller.resident_wait``)."""
+        return resident_wait(run)
+
+    def resident_feed_stream(self):
+        """A stream for whoever feeds a resident run that is ALREADY launched (copies, producer kernels): one whose work
+        makes progress beside the resident kernel (``base_controller.free_stream``; the runtime may have put a new stream
+        onto the resident kernel's hardware queue, where it would wait for the kernel's watchdog)."""
+        return free_stream(self._device)
+
+    def resident_feed(self, run, n_ticks, closed_loop=False, timeout_s=2.0, stream=None):
+        """The reference producer of resident ticks (clik_ticket_feed): one device thread that publishes tickets
+        1 .. n_ticks on ``stream`` (by default one that makes progress beside the kernel, ``resident_feed_stream``),
+        back to back or - ``closed_loop`` - each only after every wave has finished the previous tick."""
+        dev = self._device
+        stream = stream if stream is not None else free_stream(dev)
+        with _torch().cuda.device(dev):
+            rc = self._lib.clik_ticket_feed(ptr(run["ticket"]), ptr(run["done"]), int(n_ticks), 1 if closed_loop else 0,
+                                            int(run["waves"]), float(timeout_s), C.c_void_p(stream.cuda_stream))
+        _capi.check(self._lib, rc)
+        return stream
+
+    # -- solve() ------------------------------------------------------------------------------------------------
+    def _stage_solve(self, robot_var, virtual_var, input_var):
+        """The inputs of a single-instance ``solve()`` into the persistent ``SingleSlot`` (made at the first call, with
+        room for the ``(doubles, int32)`` of results the controller's ``_slot_results()`` asks for): returns the slot
+        and the pointers of q, x, y as the launch takes them (None for a block the skill does not have).  The
+        reference forwards ``virtual_var`` / ``input_var`` only when they are used (pseudo_inverse.py:521-525); the
+        device descriptor always carries the full vectors, so a missing one is zeros."""
+        spec = self.skill_spec
+        q = flat_vector(robot_var, spec.n_robot_var, "robot_var")
+        x = y = None
+        if spec.n_virtual_var > 0:
+            x = flat_vector(virtual_var if virtual_var is not None
+                            else np.zeros(spec.n_virtual_var), spec.n_virtual_var, "virtual_var")
+        if spec.n_input_var > 0:
+            y = flat_vector(input_var if input_var is not None
+                            else np.zeros(spec.n_input_var), spec.n_input_var, "input_var")
+        if self._handle is None:        # (inline: this runs on every solve())
+            self._require_handle()
+        d = self.descriptor
+        nq, nx, ny = d.n_q, d.n_x, d.n_y
+        slot = getattr(self, "_slot", None)
+        if slot is None:
+            slot = self._slot = SingleSlot(self._device, nq + nx + ny, *self._slot_results())
+        slot.in_np[:nq] = q
+        if nx:
+            slot.in_np[nq:nq + nx] = x
+        if ny:
+            slot.in_np[nq + nx:nq + nx + ny] = y
+        return slot, slot.in_ptr(0), slot.in_ptr(nq) if nx else None, slot.in_ptr(nq + nx) if ny else None

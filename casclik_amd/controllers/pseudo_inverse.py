@@ -11,14 +11,14 @@ of scanning modes in Python (:512-556).
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
 from .. import _capi
 from .. import sym as cs
-from ..lowering import lower_skill, DYN_MAX_M
-from .base_controller import (BaseController, SingleSlot, current_stream, device_of, ptr,
-                              to_device_matrix, check_out_tensor, free_stream, resident_wait, ResidentWatchdog,
+from ..lowering import DYN_MAX_M
+from .base_controller import (BaseController, current_stream, ptr, to_device_matrix, check_out_tensor, scalar_of,
                               _torch)
 
 
@@ -34,6 +34,7 @@ class PseudoInverseController(BaseController):
     converge_final_set_to_max (bool, False), pinv_method ("damped"|"standard"),
     damping_factor (float, 1e-7), function_opts (dict, accepted and ignored:
     there is no CasADi JIT on this path), device (torch device, optional)"""
+    _create_fn, _destroy_fn = "clik_pinv_create", "clik_pinv_destroy"
 
     def __init__(self, skill_spec, options=None):
         self._handle = None
@@ -42,18 +43,6 @@ class PseudoInverseController(BaseController):
         self.options = options
         self.current_mode = None
         self.modes = None
-
-    def __del__(self):
-        self._release()
-
-    def _release(self):
-        if getattr(self, "_handle", None) is not None and self._lib is not None:
-            try:
-                self._lib.clik_pinv_destroy(self._handle)
-            except Exception:
-                pass
-            self._handle = None
-        self._slot = None
 
     # -- options (pseudo_inverse.py:42-66) --------------------------------
     @property
@@ -191,37 +180,16 @@ class PseudoInverseController(BaseController):
         """Lower the skill and create the device handle (replaces the
         per-mode ``cs.Function`` JIT of pseudo_inverse.py:453-483)."""
         self.get_problem_expressions()
-        self._release()
-        self._lib = _capi.load_library()
-        self.descriptor = lower_skill(self.skill_spec)
-        cdesc = _capi.desc_to_c(self.descriptor)
-        copts = _capi.pinv_opts_to_c(self.options)
-        self._device = device_of(self.options.get("device"))
-        handle = C.c_void_p()
-        torch = _torch()
-        with torch.cuda.device(self._device):
-            rc = self._lib.clik_pinv_create(C.byref(cdesc), C.byref(copts), C.byref(handle))
-        _capi.check(self._lib, rc)
-        self._handle = handle
+        cdesc, copts = self._create_handle()
+        handle, d = self._handle, self.descriptor
         self.kernel_name = self._lib.clik_pinv_kernel_name(handle).decode()
         # no AOT shape for this skill: instantiate the static templates for it
-        # (the reference JIT-compiles at this point too, function_opts["jit"])
-        import os
-        want_jit = self.options["function_opts"].get("jit", True) and os.environ.get("CLIK_JIT", "1") != "0" \
-            and os.environ.get("CLIK_FORCE_DYNAMIC", "0") != "1"
+        want_jit = self._want_jit()
         if self.kernel_name in ("dynamic", "none") and want_jit:
             from .. import jit
-            with torch.cuda.device(self._device):
-                try:
-                    name = jit.attach(self._lib, handle, cdesc, copts, extern=self.descriptor.extern_source())
-                except RuntimeError as exc:
-                    # (a failed instantiation is not fatal when a built-in kernel serves the skill: say so
-                    # and run that one - still the GPU path; skills only instantiated kernels can serve
-                    # fail below)
-                    import warnings
-                    warnings.warn("run-time kernel instantiation failed, using the built-in dynamic-shape "
-                                  "kernel: %s" % str(exc)[:400])
-                    name = None
+            name = self._attach_or_warn(
+                lambda: jit.attach(self._lib, handle, cdesc, copts, extern=d.extern_source()),
+                "run-time kernel instantiation failed, using the built-in dynamic-shape kernel", 400)
             if name:
                 self.kernel_name = name
         # The skill's kernels with its own numbers compiled in (the reference's JIT compiles its functions with the
@@ -233,32 +201,22 @@ class PseudoInverseController(BaseController):
         jv = self.options["function_opts"].get("jit_values", None)
         env_jv = os.environ.get("CLIK_JIT_VALUES", "1")
         variant1 = self._lib.clik_pinv_kernel_variant(handle, 1).decode()
-        dd = self.descriptor
-        single_mode = (dd.n_x == 0 and dd.n_sets == 0 and variant1 == "lane")
+        single_mode = (d.n_x == 0 and d.n_sets == 0 and variant1 == "lane")
         wanted = (variant1 == "team4" or single_mode) and jv is not False
         if want_jit and wanted and env_jv != "0":
             from .. import jit
-            with torch.cuda.device(self._device):
-                try:
-                    self.value_kernel = jit.attach_values(self._lib, handle, cdesc, copts,
-                                                          extern=self.descriptor.extern_source())
-                except RuntimeError as exc:
-                    import warnings
-                    warnings.warn("value-specialised kernel could not be built, using the image-reading one: %s"
-                                  % str(exc)[:300])
+            self.value_kernel = self._attach_or_warn(
+                lambda: jit.attach_values(self._lib, handle, cdesc, copts, extern=d.extern_source()),
+                "value-specialised kernel could not be built, using the image-reading one", 300)
         if self.kernel_name == "none":
             raise NotImplementedError(
                 "a constraint of this skill has more rows than the built-in kernels are wide (%d) and no "
                 "shape-specialised kernel could be instantiated for it (jit disabled, hipcc missing, or the "
                 "skill is outside the shape-specialised family)" % DYN_MAX_M)
-        if self.descriptor.extern_code and not self.kernel_name.startswith("jit_"):
-            # constraints outside the row-table family exist only as generated code inside a
-            # run-time instantiated kernel; there is no other path (and no CPU fallback)
-            raise NotImplementedError(
-                "the skill has constraint expressions that need generated device code (%s), but no "
-                "kernel could be instantiated for it (jit disabled, hipcc missing, or the skill is "
-                "outside the shape-specialised family)" % ", ".join(
-                    repr(self.descriptor.tasks[k]["label"]) for k in sorted(self.descriptor.extern_code)))
+        self._require_generated_code_kernel()
+
+    def _c_options(self):
+        return _capi.pinv_opts_to_c(self.options)
 
     def kernel_variant(self, batch):
         """``<kernel>/<variant>`` serving a batch of that many instances: ``team4`` (four lanes per
@@ -283,10 +241,6 @@ class PseudoInverseController(BaseController):
         return res_virt, res_slack
 
     # -- per-tick -------------------------------------------------------------
-    def _require_handle(self):
-        if self._handle is None:
-            raise RuntimeError("call setup_problem_functions() / setup_solver() first")
-
     def solve_batch(self, time_var, robot_var, virtual_var=None, input_var=None,
                     out=None, return_mode=True):
         """One controller tick for a batch.
@@ -294,96 +248,38 @@ class PseudoInverseController(BaseController):
         robot_var [B, n_q], virtual_var [B, n_x], input_var [B, n_y] as numpy
         arrays or torch tensors (tensors on the controller's device are used
         in place).  ``time_var``: one time stamp for the batch, or an array with one per
-        instance (then one launch per distinct time stamp).  Returns (robot_vel [B,n_q], virtual_vel | None, mode [B])
-        in the container type of ``robot_var``.  The launch is asynchronous on
+        instance (robots at different phases of a trajectory): ONE launch of the per-instance-time kernel
+        (clik_pinv_solve_batch_t); a skill served by the dynamic fallback kernel has no such variant, its batch is
+        grouped by distinct time stamps, one launch per group.  Returns (robot_vel [B,n_q], virtual_vel | None,
+        mode [B]) in the container type of ``robot_var``.  The launch is asynchronous on
         torch's current stream when tensors are passed."""
         self._require_handle()
         torch = _torch()
         d = self.descriptor
         dev = self._device
-        if np.ndim(time_var) > 0 and np.size(time_var) > 1:
-            return self._solve_batch_per_instance_time(time_var, robot_var, virtual_var, input_var, out, return_mode)
-        time_var = float(np.asarray(time_var).reshape(-1)[0]) if np.ndim(time_var) > 0 else time_var
-        Q, was_np = to_device_matrix(robot_var, d.n_q, dev, "robot_var")
-        B = Q.shape[0]
-        X = None
-        if d.n_x > 0:
-            if virtual_var is None:
-                raise ValueError("skill has virtual_var: pass virtual_var")
-            X, _ = to_device_matrix(virtual_var, d.n_x, dev, "virtual_var", B)
-        Y = None
-        if d.n_y > 0:
-            if input_var is None:
-                raise ValueError("skill has input_var: pass input_var")
-            Y, _ = to_device_matrix(input_var, d.n_y, dev, "input_var", B)
-        if out is not None:
-            check_out_tensor(out, (B, d.n_q), "float64", dev, "out")
-            dQ = out
-        else:
-            dQ = torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
-        dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
-        mode = torch.empty((B,), dtype=torch.int32, device=dev) if return_mode else None
-        tt, ttp = _capi.tterms_arg(d.time_terms(time_var))
-        with torch.cuda.device(dev):
-            rc = self._lib.clik_pinv_solve_batch(
-                self._handle, B, ttp, ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX),
-                ptr(mode), current_stream(dev))
-        _capi.check(self._lib, rc)
-        if was_np:
-            return (dQ.cpu().numpy(), None if dX is None else dX.cpu().numpy(),
-                    None if mode is None else mode.cpu().numpy())
-        return dQ, dX, mode
-
-    def _solve_batch_per_instance_time(self, times, robot_var, virtual_var, input_var, out, return_mode):
-        """``time_var`` with one entry per instance (robots at different phases of a trajectory): ONE launch of the
-        per-instance-time kernel (clik_pinv_solve_batch_t: the time-only sub-expressions are evaluated on the host
-        per distinct time stamp and travel as a [B, 2 * n_tslots] device array).  A skill served by the dynamic
-        fallback kernel has no such variant: its batch is grouped by distinct time stamps, one launch per group."""
-        torch = _torch()
-        d = self.descriptor
-        dev = self._device
-        Q, was_np = to_device_matrix(robot_var, d.n_q, dev, "robot_var")
-        B = Q.shape[0]
-        times = np.asarray(times, dtype=float).reshape(-1)
-        if times.size != B:
-            raise ValueError("time_var has %d entries, the batch %d instances" % (times.size, B))
-        X = to_device_matrix(virtual_var, d.n_x, dev, "virtual_var", B)[0] if d.n_x > 0 else None
-        Y = to_device_matrix(input_var, d.n_y, dev, "input_var", B)[0] if d.n_y > 0 else None
-        if out is not None:
-            check_out_tensor(out, (B, d.n_q), "float64", dev, "out")
+        Q, X, Y, B, was_np = self._batch_inputs(robot_var, virtual_var, input_var)
+        time_var, T, stamps = self._instance_times(time_var, B)
+        check_out_tensor(out, (B, d.n_q), "float64", dev, "out")
         dQ = out if out is not None else torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
         dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
         mode = torch.empty((B,), dtype=torch.int32, device=dev) if return_mode else None
-        uniq, inverse = np.unique(times, return_inverse=True)
-        terms = np.asarray([np.asarray(d.time_terms(float(tv)), dtype=float).reshape(-1) for tv in uniq])
-        rc = _capi.CLIK_EUNSUPPORTED
-        if terms.shape[1] == 0:
-            # no time-dependent sub-expression: every time stamp gives the same tick - the ordinary single launch
-            res = self.solve_batch(float(times[0]), Q, virtual_var=X, input_var=Y, out=out, return_mode=return_mode)
-            if was_np:
-                return tuple(None if r is None else r.cpu().numpy() for r in res)
-            return res
-        if terms.shape[1] > 0:
-            T = torch.from_numpy(np.ascontiguousarray(terms[inverse])).to(dev)
-            with torch.cuda.device(dev):
+        with torch.cuda.device(dev):
+            if T is not None:
                 rc = self._lib.clik_pinv_solve_batch_t(self._handle, B, ptr(T), ptr(Q), ptr(X), ptr(Y), ptr(dQ),
                                                        ptr(dX), ptr(mode), current_stream(dev))
-            if rc != _capi.CLIK_EUNSUPPORTED:
-                _capi.check(self._lib, rc)
-        for k, tv in enumerate(uniq if rc == _capi.CLIK_EUNSUPPORTED else ()):
-            rows = torch.from_numpy(np.nonzero(inverse == k)[0]).to(dev)
-            res = self.solve_batch(float(tv), Q.index_select(0, rows),
-                                   virtual_var=None if X is None else X.index_select(0, rows),
-                                   input_var=None if Y is None else Y.index_select(0, rows), return_mode=return_mode)
-            dQ.index_copy_(0, rows, res[0])
-            if dX is not None:
-                dX.index_copy_(0, rows, res[1])
-            if mode is not None:
-                mode.index_copy_(0, rows, res[2])
-        if was_np:
-            return (dQ.cpu().numpy(), None if dX is None else dX.cpu().numpy(),
-                    None if mode is None else mode.cpu().numpy())
-        return dQ, dX, mode
+            else:
+                tt, ttp = _capi.tterms_arg(d.time_terms(time_var))
+                rc = self._lib.clik_pinv_solve_batch(
+                    self._handle, B, ttp, ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX),
+                    ptr(mode), current_stream(dev))
+        if T is not None and rc == _capi.CLIK_EUNSUPPORTED:
+            self._solve_per_stamp(
+                stamps, lambda tv, Qk, Xk, Yk: self.solve_batch(tv, Qk, virtual_var=Xk, input_var=Yk,
+                                                                return_mode=return_mode),
+                (Q, X, Y), (dQ, dX, mode))
+            rc = 0
+        _capi.check(self._lib, rc)
+        return self._to_caller((dQ, dX, mode), was_np)
 
     def bind_batch(self, robot_var, input_var=None, virtual_var=None, out=None,
                    mode_out=None, stream=None):
@@ -395,13 +291,7 @@ class PseudoInverseController(BaseController):
         torch = _torch()
         d = self.descriptor
         dev = self._device
-        Q, _ = to_device_matrix(robot_var, d.n_q, dev, "robot_var")
-        B = Q.shape[0]
-        X = Y = None
-        if d.n_x > 0:
-            X, _ = to_device_matrix(virtual_var, d.n_x, dev, "virtual_var", B)
-        if d.n_y > 0:
-            Y, _ = to_device_matrix(input_var, d.n_y, dev, "input_var", B)
+        Q, X, Y, B, _ = self._batch_inputs(robot_var, virtual_var, input_var)
         check_out_tensor(out, (B, d.n_q), "float64", dev, "out")
         check_out_tensor(mode_out, (B,), "int32", dev, "mode_out")
         dQ = out if out is not None else torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
@@ -488,18 +378,8 @@ class PseudoInverseController(BaseController):
         check_out_tensor(mode_out, mode_shape, "int32", dev, "mode_out")
         dQ = out if out is not None else torch.zeros(out_shape, dtype=torch.float64, device=dev)
         mode = mode_out if mode_out is not None else torch.full(mode_shape, -1, dtype=torch.int32, device=dev)
-        ticket = torch.zeros(64, dtype=torch.int32, device=dev)
-        ticket[16] = D if D > 1 else 0
-        if publish_ahead:
-            # tickets 1 .. publish_ahead are valid before the kernel starts (the inputs of those ticks are in place):
-            # no producer has to run next to it - what a profiler that serialises kernels needs
-            ticket[0] = int(publish_ahead)
-
         waves = self._lib.clik_pinv_resident_waves(self._handle, B)
-        done = torch.zeros(max(waves, 1), dtype=torch.int32, device=dev)
-        stream = stream if stream is not None else torch.cuda.Stream(device=dev)
-        tt, ttp = _capi.tterms_arg(d.time_terms(time_var))
-        torch.cuda.current_stream(dev).synchronize()       # (ticket / outputs are initialised before the kernel starts)
+        ticket, done, stream, (tt, ttp) = self._resident_setup(waves, D, publish_ahead, stream, time_var)
         with torch.cuda.device(dev):
             if integrate_dt > 0.0:
                 # the state stays in the kernel (include/clik.h): q is read at tick 1 and stepped with
@@ -515,32 +395,6 @@ class PseudoInverseController(BaseController):
         return {"ticket": ticket, "done": done, "waves": waves, "out": dQ, "mode": mode, "stream": stream,
                 "keep": (Q, Y, tt)}
 
-    def resident_wait(self, run):
-        """Wait for a resident run to leave; ticks finished, or ``ResidentWatchdog`` (``base_controller.resident_wait``)."""
-        return resident_wait(run)
-
-    def resident_feed_stream(self):
-        """A stream for whoever feeds a resident run that is ALREADY launched (copies, producer kernels): one whose work
-        makes progress beside the resident kernel (``base_controller.free_stream``; the runtime may have put a new stream
-        onto the resident kernel's hardware queue, where it would wait for the kernel's watchdog)."""
-        return free_stream(self._device)
-
-    def resident_feed(self, run, n_ticks, closed_loop=False, timeout_s=2.0, stream=None):
-        """The reference producer of resident ticks (clik_ticket_feed): one device thread that publishes tickets
-        1 .. n_ticks on ``stream`` (a stream of its own by default), back to back or - ``closed_loop`` - each only after
-        every wave has finished the previous tick."""
-        torch = _torch()
-        dev = self._device
-        # (a stream of another PRIORITY: the runtime multiplexes streams of one priority onto a few hardware queues,
-        # and a producer queued behind the resident kernel would wait for it to leave - see include/clik.h)
-        stream = stream if stream is not None else free_stream(dev)
-        with torch.cuda.device(dev):
-            rc = self._lib.clik_ticket_feed(ptr(run["ticket"]), ptr(run["done"]), int(n_ticks), 1 if closed_loop else 0,
-                                            int(run["waves"]),
-                                            float(timeout_s), C.c_void_p(stream.cuda_stream))
-        _capi.check(self._lib, rc)
-        return stream
-
     def rollout_batch(self, time_vars, robot_var, input_var=None, dt=0.008,
                       max_speed=0.0, virtual_var=None, method="euler"):
         """``len(time_vars)`` ticks of solve -> clamp(+-max_speed) -> integrate in one launch.
@@ -554,39 +408,18 @@ class PseudoInverseController(BaseController):
         torch = _torch()
         d = self.descriptor
         dev = self._device
-        if method not in ("euler", "rk4"):
-            raise ValueError("method must be 'euler' or 'rk4'")
-        Q, was_np = to_device_matrix(robot_var, d.n_q, dev, "robot_var")
-        if not was_np:
-            Q = Q.clone()
-        B = Q.shape[0]
-        X = dX = None
-        if d.n_x > 0:
-            if virtual_var is None:
-                raise ValueError("skill has virtual_var: pass virtual_var")
-            X, x_np = to_device_matrix(virtual_var, d.n_x, dev, "virtual_var", B)
-            if not x_np:
-                X = X.clone()
-            dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev)
-        Y = None
-        if d.n_y > 0:
-            Y, _ = to_device_matrix(input_var, d.n_y, dev, "input_var", B)
-        times = np.asarray(time_vars, dtype=float).reshape(-1)
-        if method == "rk4":
-            stage_times = np.stack([times, times + 0.5 * dt, times + 0.5 * dt, times + dt], axis=1).reshape(-1)
-        else:
-            stage_times = times
-        tt = np.concatenate([d.time_terms(t) for t in stage_times]) if d.n_tslots else np.zeros(0)
-        tt, ttp = _capi.tterms_arg(tt)
+        n_ticks, stages, (tt, ttp) = self._rollout_times(time_vars, dt, method)
+        Q, X, Y, B, was_np = self._batch_inputs(robot_var, virtual_var, input_var, clone=True)
         dQ = torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
+        dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
         mode = torch.empty((B,), dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
             rc = self._lib.clik_pinv_rollout_batch_m(
-                self._handle, B, int(times.size), 1 if method == "rk4" else 0, float(dt), float(max_speed), ttp,
+                self._handle, B, n_ticks, stages, float(dt), float(max_speed), ttp,
                 ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX), ptr(mode), current_stream(dev))
         _capi.check(self._lib, rc)
         outs = (Q, X, dQ, dX, mode) if d.n_x > 0 else (Q, dQ, mode)
-        return tuple(o.cpu().numpy() for o in outs) if was_np else outs
+        return self._to_caller(outs, was_np)
 
     def solve(self, time_var, robot_var, virtual_var=None, input_var=None,
               warmstart_robot_vel_var=None, warmstart_virtual_vel_var=None,
@@ -594,58 +427,26 @@ class PseudoInverseController(BaseController):
         """Single-instance tick with the reference's signature and return
         convention (pseudo_inverse.py:512-556): ``(robot_vel DM n x 1,
         virtual_vel DM | None, None)`` and ``self.current_mode``."""
-        spec = self.skill_spec
-        q = _flat(robot_var, spec.n_robot_var, "robot_var")
-        x = None
-        if spec.n_virtual_var > 0:
-            # the reference forwards virtual_var only when it is used (:521-525);
-            # the device descriptor always carries the full state vector
-            x = _flat(virtual_var if virtual_var is not None
-                      else np.zeros(spec.n_virtual_var), spec.n_virtual_var, "virtual_var")
-        y = None
-        if spec.n_input_var > 0:
-            y = _flat(input_var if input_var is not None
-                      else np.zeros(spec.n_input_var), spec.n_input_var, "input_var")
         # B = 1 through persistent pinned / device staging (one copy each way)
-        self._require_handle()
-        torch = _torch()
+        slot, pq, px, py = self._stage_solve(robot_var, virtual_var, input_var)
         d = self.descriptor
-        nq, nx, ny = d.n_q, d.n_x, d.n_y
-        slot = getattr(self, "_slot", None)
-        if slot is None:
-            slot = self._slot = SingleSlot(self._device, nq + nx + ny, nq + nx, 1)
-        slot.in_np[:nq] = q
-        if nx:
-            slot.in_np[nq:nq + nx] = x
-        if ny:
-            slot.in_np[nq + nx:nq + nx + ny] = y
-        tt, ttp = _capi.tterms_arg(d.time_terms(float(_scalar(time_var))))
+        nq, nx = d.n_q, d.n_x
+        tt, ttp = _capi.tterms_arg(d.time_terms(float(scalar_of(time_var))))
         with slot.guard():
             stream = slot.begin()
             rc = self._lib.clik_pinv_solve_batch(
-                self._handle, 1, ttp, slot.in_ptr(0), slot.in_ptr(nq) if nx else None,
-                slot.in_ptr(nq + nx) if ny else None, slot.out_ptr(0), slot.out_ptr(nq) if nx else None,
+                self._handle, 1, ttp, pq, px, py, slot.out_ptr(0), slot.out_ptr(nq) if nx else None,
                 slot.int_ptr(0), stream)
             _capi.check(self._lib, rc)
             slot.download()
         self.current_mode = int(slot.out_i[0])
         cntrl_rob = cs.DM(slot.out_f[:nq].copy())
         cntrl_virt = None
-        if spec.n_virtual_var > 0 and virtual_var is not None and spec._has_virtual:
+        if nx and virtual_var is not None and self.skill_spec._has_virtual:
             cntrl_virt = cs.DM(slot.out_f[nq:nq + nx].copy())
         return cntrl_rob, cntrl_virt, None
 
 
-def _scalar(v):
-    if hasattr(v, "toarray"):
-        v = v.toarray()
-    return np.asarray(v, dtype=float).reshape(-1)[0]
-
-
-def _flat(v, n, what):
-    if hasattr(v, "toarray"):
-        v = v.toarray()
-    arr = np.asarray(v, dtype=np.float64).reshape(-1)
-    if arr.size != n:
-        raise ValueError("%s must have %d entries, got %d" % (what, n, arr.size))
-    return arr
+    def _slot_results(self):
+        d = self.descriptor
+        return d.n_q + d.n_x, 1

@@ -14,6 +14,7 @@ ignored.
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -21,11 +22,7 @@ from .. import _capi
 from .. import sym as cs
 from ..constraints import (EqualityConstraint, SetConstraint, VelocityEqualityConstraint,
                            VelocitySetConstraint)
-from ..lowering import lower_skill
-from .base_controller import (BaseController, SingleSlot, current_stream, device_of, ptr,
-                              to_device_matrix, check_out_tensor, free_stream, resident_wait, ResidentWatchdog,
-                              _torch)
-from .pseudo_inverse import _flat, _scalar
+from .base_controller import BaseController, current_stream, ptr, check_out_tensor, scalar_of, _torch
 
 
 def _weights(weights, n, what):
@@ -66,6 +63,7 @@ class ReactiveQPController(BaseController):
     here is the device active set, clik_qp_static.hpp); function_opts: `jit` (instantiate a kernel for the skill's
     structure, default True), `jit_values` (compile the skill's numbers in), `device`."""
     weight_shifter = 0.001   # mu of the eTaSL paper (reactive_qp.py:44)
+    _create_fn, _destroy_fn = "clik_qp_create", "clik_qp_destroy"
 
     def __init__(self, skill_spec, robot_var_weights=None,
                  virtual_var_weights=None, slack_var_weights=None, options=None):
@@ -77,18 +75,6 @@ class ReactiveQPController(BaseController):
         self.virtual_var_weights = virtual_var_weights
         self.slack_var_weights = slack_var_weights
         self.options = options
-
-    def __del__(self):
-        self._release()
-
-    def _release(self):
-        if getattr(self, "_handle", None) is not None and self._lib is not None:
-            try:
-                self._lib.clik_qp_destroy(self._handle)
-            except Exception:
-                pass
-            self._handle = None
-        self._slot = None
 
     # -- weights ------------------------------------------------------------
     @property
@@ -157,58 +143,23 @@ class ReactiveQPController(BaseController):
     def setup_problem_functions(self):
         """Lower the skill, upload it with the cost weights (replaces the
         H/A/Blb/Bub ``cs.Function`` objects of reactive_qp.py:262-298)."""
-        self._release()
-        self._lib = _capi.load_library()
-        spec = self.skill_spec
-        self.descriptor = lower_skill(spec)
-        d = self.descriptor
-        cdesc = _capi.desc_to_c(d)
-        state_w = np.concatenate([self._robot_var_weights,
-                                  self._virtual_var_weights[:d.n_x]])
-        if self._slack_var_weights.size != d.n_slack:
-            raise ValueError("slack_var_weights and slack_var dimensions do not match")
-        copts = _capi.qp_opts_to_c(self.weight_shifter, state_w,
-                                   self._slack_var_weights,
-                                   int(self.options.get("max_iter", 0)))
-        self._device = device_of(self.options.get("device"))
-        handle = C.c_void_p()
-        torch = _torch()
-        with torch.cuda.device(self._device):
-            rc = self._lib.clik_qp_create(C.byref(cdesc), C.byref(copts), C.byref(handle))
-        _capi.check(self._lib, rc)
-        self._handle = handle
+        cdesc, _ = self._create_handle()
+        handle, d = self._handle, self.descriptor
+        self._slot_calls = 0        # (solve() hot-starts from its previous call: none yet on this handle)
         self.n_qp_vars = self._lib.clik_qp_n_vars(handle)
         self.n_qp_rows = self._lib.clik_qp_n_rows(handle)
         self.kernel_name = self._lib.clik_qp_kernel_name(handle).decode()
         # no AOT shape for this skill: instantiate the shape-specialised QP kernel for
         # it (the reference JIT-compiles its H/A/lbA/ubA functions here, reactive_qp.py:283-298)
-        import os
-        fopts = self.options.get("function_opts") or {}
-        want_jit = fopts.get("jit", True) and os.environ.get("CLIK_JIT", "1") != "0" \
-            and os.environ.get("CLIK_FORCE_DYNAMIC", "0") != "1"
+        want_jit = self._want_jit()
         if self.kernel_name in ("dynamic", "none") and want_jit:
             from .. import jit
-            with torch.cuda.device(self._device):
-                try:
-                    name = jit.attach_qp(self._lib, handle, cdesc, extern=d.extern_source())
-                except RuntimeError as exc:
-                    # (a failed instantiation is not fatal when a built-in kernel serves the skill: say so
-                    # and run that one - still the GPU path; skills only instantiated kernels can serve
-                    # fail below)
-                    import warnings
-                    warnings.warn("run-time kernel instantiation failed, using the built-in dynamic-shape "
-                                  "kernel: %s" % str(exc)[:400])
-                    name = None
+            name = self._attach_or_warn(
+                lambda: jit.attach_qp(self._lib, handle, cdesc, extern=d.extern_source()),
+                "run-time kernel instantiation failed, using the built-in dynamic-shape kernel", 400)
             if name:
                 self.kernel_name = name
-        if d.extern_code and not self.kernel_name.startswith("jit_"):
-            # constraints outside the row-table family exist only as generated code inside a
-            # run-time instantiated kernel; there is no other path (and no CPU fallback)
-            raise NotImplementedError(
-                "the skill has constraint expressions that need generated device code (%s), but no "
-                "kernel could be instantiated for it (jit disabled, hipcc missing, or the skill is "
-                "outside the shape-specialised family)" % ", ".join(
-                    repr(d.tasks[k]["label"]) for k in sorted(d.extern_code)))
+        self._require_generated_code_kernel()
         if self.kernel_name == "none":
             raise NotImplementedError(
                 "the QP of this skill (%d variables x %d rows) exceeds the built-in kernel and no "
@@ -221,30 +172,33 @@ class ReactiveQPController(BaseController):
         # against 7.4); for other skills on request (function_opts["jit_values"] = True or CLIK_JIT_VALUES=2: it keeps
         # the LDS work area and gains about 1 %); function_opts["jit_values"] = False or CLIK_JIT_VALUES=0: never.
         self.value_kernel = None
-        jv, env_jv = fopts.get("jit_values", None), os.environ.get("CLIK_JIT_VALUES", "1")
+        jv = (self.options.get("function_opts") or {}).get("jit_values", None)
+        env_jv = os.environ.get("CLIK_JIT_VALUES", "1")
         # (skills with more than ten state variables - two arms - keep the image-reading kernel unless asked: the
         # value-specialised one holds its n x n factor in registers)
         wanted = jv is True or env_jv == "2" or (jv is None and self._lib.clik_qp_is_box_family(handle) == 1
                                                   and d.n_state <= 10)
         if want_jit and wanted and jv is not False and env_jv != "0" and self.kernel_name not in ("dynamic", "none"):
             from .. import jit
-            with torch.cuda.device(self._device):
-                try:
-                    self.value_kernel = jit.attach_qp_values(self._lib, handle, cdesc, extern=d.extern_source())
-                except RuntimeError as exc:
-                    import warnings
-                    warnings.warn("value-specialised QP kernel could not be built, using the image-reading one: %s"
-                                  % str(exc)[:300])
+            self.value_kernel = self._attach_or_warn(
+                lambda: jit.attach_qp_values(self._lib, handle, cdesc, extern=d.extern_source()),
+                "value-specialised QP kernel could not be built, using the image-reading one", 300)
+
+    def _c_options(self):
+        d = self.descriptor
+        state_w = np.concatenate([self._robot_var_weights,
+                                  self._virtual_var_weights[:d.n_x]])
+        if self._slack_var_weights.size != d.n_slack:
+            raise ValueError("slack_var_weights and slack_var dimensions do not match")
+        return _capi.qp_opts_to_c(self.weight_shifter, state_w,
+                                  self._slack_var_weights,
+                                  int(self.options.get("max_iter", 0)))
 
     def setup_solver(self):
         """The solver lives inside the kernel; make sure the handle exists
         (reference: cs.conic construction, reactive_qp.py:248-260)."""
         if self._handle is None:
             self.setup_problem_functions()
-
-    def _require_handle(self):
-        if self._handle is None:
-            raise RuntimeError("call setup_problem_functions() / setup_solver() first")
 
     def setup_initial_problem_solver(self):
         """The reference builds a second QP over (virtual_vel, slack) with the robot velocity
@@ -444,7 +398,6 @@ class ReactiveQPController(BaseController):
         Jacobians at the initial state); the reduced QP is then a skill of its own - linear
         velocity-level rows in the ``n_virtual`` unknowns with those numbers as coefficients - and is
         solved by a second ReactiveQPController, i.e. by the same device kernels."""
-        from .. import sym as cs_
         from ..skill_specification import SkillSpecification
         spec = self.skill_spec
         nq, nx, ns = spec.n_robot_var, spec.n_virtual_var, spec.n_slack_var
@@ -467,7 +420,7 @@ class ReactiveQPController(BaseController):
             host_rows, _ = self._host_rows(time_var0, q0, x0, robot_vel_var0, y0)
             w_virt = np.asarray(self._virtual_var_weights, dtype=float).reshape(-1)[:nx]
             w_slack = np.asarray(self._slack_var_weights, dtype=float).reshape(-1)
-        xs = cs_.MX.sym("dx_init", nx)
+        xs = cs.MX.sym("dx_init", nx)
         cns, slack_w, row = [], [], 0
         sl = 0
         for ci, cn in enumerate(spec.constraints):
@@ -475,7 +428,7 @@ class ReactiveQPController(BaseController):
             rows = slice(row, row + m)
             row += m
             soft = cn.constraint_type == "soft"
-            found_virt = cs_.depends_on(cn.expression, spec.virtual_var)       # structural, as J_virt.nnz() (:346-347)
+            found_virt = cs.depends_on(cn.expression, spec.virtual_var)       # structural, as J_virt.nnz() (:346-347)
             if soft:
                 wk = w_slack[sl:sl + m]
                 sl += m
@@ -490,7 +443,7 @@ class ReactiveQPController(BaseController):
                 Jv = Jx if Jx is not None else np.zeros((m, nx))
                 shift = Jq(dq0) if dq0.any() else 0.0
                 lo, hi = lbr - shift, ubr - shift
-            kw = dict(label="init_" + cn.label, expression=cs_.mtimes(Jv, xs), priority=len(cns),
+            kw = dict(label="init_" + cn.label, expression=cs.mtimes(Jv, xs), priority=len(cns),
                       constraint_type="soft" if soft else "hard")
             if np.array_equal(lo, hi):
                 cns.append(VelocityEqualityConstraint(target=lo, **kw))
@@ -503,7 +456,7 @@ class ReactiveQPController(BaseController):
                 slack_w.extend(wd.tolist())
         if not cns:
             return None, None
-        t_ = cs_.MX.sym("t_init")
+        t_ = cs.MX.sym("t_init")
         sub = SkillSpecification(label=spec.label + "_initial", time_var=t_, robot_var=xs, constraints=cns)
         ctrl = ReactiveQPController(sub, robot_var_weights=list(w_virt), slack_var_weights=slack_w or None,
                                     options={"device": self.options.get("device")} if self.options.get("device") is not None else None)
@@ -570,17 +523,8 @@ class ReactiveQPController(BaseController):
         dQ = torch.zeros(lead + (B, d.n_q), dtype=torch.float64, device=dev)
         slack = torch.zeros(lead + (B, d.n_slack), dtype=torch.float64, device=dev) if d.n_slack > 0 else None
         status = torch.full(lead + (B,), -1, dtype=torch.int32, device=dev)
-        ticket = torch.zeros(64, dtype=torch.int32, device=dev)
-        ticket[16] = D if D > 1 else 0
-        if publish_ahead:
-            # tickets 1 .. publish_ahead are valid before the kernel starts (their inputs are in place): no producer
-            # kernel has to run beside it (tools/resident_once.py under a counter run, which serialises kernels)
-            ticket[0] = int(publish_ahead)
         waves = self._lib.clik_qp_resident_waves(self._handle, B)
-        done = torch.zeros(max(waves, 1), dtype=torch.int32, device=dev)
-        stream = stream if stream is not None else torch.cuda.Stream(device=dev)
-        tt, ttp = _capi.tterms_arg(d.time_terms(time_var))
-        torch.cuda.current_stream(dev).synchronize()       # (ticket / outputs are initialised before the kernel starts)
+        ticket, done, stream, (tt, ttp) = self._resident_setup(waves, D, publish_ahead, stream, time_var)
         with torch.cuda.device(dev):
             rc = self._lib.clik_qp_resident_run(self._handle, B, int(n_ticks), ttp, ptr(robot_var),
                                                 ptr(input_var) if d.n_y > 0 else None, ptr(dQ), ptr(slack), ptr(status),
@@ -590,25 +534,6 @@ class ReactiveQPController(BaseController):
         _capi.check(self._lib, rc)
         return {"ticket": ticket, "done": done, "waves": waves, "out": dQ, "slack": slack, "status": status,
                 "stream": stream, "keep": (robot_var, input_var, tt)}
-
-    def resident_wait(self, run):
-        """Wait for a resident run to leave; ticks finished, or ``ResidentWatchdog`` (``base_controller.resident_wait``)."""
-        return resident_wait(run)
-
-    def resident_feed_stream(self):
-        """see PseudoInverseController.resident_feed_stream"""
-        return free_stream(self._device)
-
-    def resident_feed(self, run, n_ticks, closed_loop=False, timeout_s=2.0, stream=None):
-        """The reference producer of resident ticks (clik_ticket_feed, see PseudoInverseController.resident_feed)."""
-        torch = _torch()
-        dev = self._device
-        stream = stream if stream is not None else free_stream(dev)
-        with torch.cuda.device(dev):
-            rc = self._lib.clik_ticket_feed(ptr(run["ticket"]), ptr(run["done"]), int(n_ticks), 1 if closed_loop else 0,
-                                            int(run["waves"]), float(timeout_s), C.c_void_p(stream.cuda_stream))
-        _capi.check(self._lib, rc)
-        return stream
 
     def solve_batch(self, time_var, robot_var, virtual_var=None, input_var=None,
                     return_status=True, hot_set=None, use_hot=True):
@@ -628,73 +553,36 @@ class ReactiveQPController(BaseController):
         torch = _torch()
         d = self.descriptor
         dev = self._device
-        Q, was_np = to_device_matrix(robot_var, d.n_q, dev, "robot_var")
-        B = Q.shape[0]
-        times = None
-        if np.ndim(time_var) > 0 and np.size(time_var) > 1:
-            times = np.asarray(time_var, dtype=float).reshape(-1)
-            if times.size != B:
-                raise ValueError("time_var has %d entries, the batch %d instances" % (times.size, B))
-            time_var = float(times[0])
-        elif np.ndim(time_var) > 0:
-            time_var = float(np.asarray(time_var).reshape(-1)[0])
-        X = Y = None
-        if d.n_x > 0:
-            if virtual_var is None:
-                raise ValueError("skill has virtual_var: pass virtual_var")
-            X, _ = to_device_matrix(virtual_var, d.n_x, dev, "virtual_var", B)
-        if d.n_y > 0:
-            if input_var is None:
-                raise ValueError("skill has input_var: pass input_var")
-            Y, _ = to_device_matrix(input_var, d.n_y, dev, "input_var", B)
+        Q, X, Y, B, was_np = self._batch_inputs(robot_var, virtual_var, input_var)
+        time_var, T, stamps = self._instance_times(time_var, B)
         dQ = torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
         dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
         ns = d.n_slack
         SL = torch.empty((B, ns), dtype=torch.float64, device=dev) if ns else None
         status = torch.empty((B,), dtype=torch.int32, device=dev) if return_status else None
-        tt, ttp = _capi.tterms_arg(d.time_terms(time_var))
         if hot_set is not None and (hot_set.dtype != torch.int32 or hot_set.numel() != B or not hot_set.is_cuda):
             raise ValueError("hot_set must be an int32 device tensor with one entry per instance")
         hot_flag = 1 if (hot_set is not None and use_hot) else 0
-        T = None
-        if times is not None and np.size(tt) > 0:
-            uniq, inverse = np.unique(times, return_inverse=True)
-            terms = np.asarray([np.asarray(d.time_terms(float(tv)), dtype=float).reshape(-1) for tv in uniq])
-            T = torch.from_numpy(np.ascontiguousarray(terms[inverse])).to(dev)
         with torch.cuda.device(dev):
             if T is not None:
                 rc = self._lib.clik_qp_solve_batch_t(
                     self._handle, B, ptr(T), ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX),
                     ptr(SL), ptr(status), ptr(hot_set), hot_flag, current_stream(dev))
             else:
+                tt, ttp = _capi.tterms_arg(d.time_terms(time_var))
                 rc = self._lib.clik_qp_solve_batch_hot(
                     self._handle, B, ttp, ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX),
                     ptr(SL), ptr(status), ptr(hot_set), hot_flag, current_stream(dev))
         if T is not None and rc == _capi.CLIK_EUNSUPPORTED:
-            # (a skill on the dynamic fallback kernel: one launch per distinct time stamp)
-            for k, tv in enumerate(uniq):
-                rows = torch.from_numpy(np.nonzero(inverse == k)[0]).to(dev)
-                hs = None if hot_set is None else hot_set.index_select(0, rows)
-                res = self.solve_batch(float(tv), Q.index_select(0, rows),
-                                       virtual_var=None if X is None else X.index_select(0, rows),
-                                       input_var=None if Y is None else Y.index_select(0, rows),
-                                       return_status=return_status, hot_set=hs, use_hot=use_hot)
-                dQ.index_copy_(0, rows, res[0])
-                if dX is not None:
-                    dX.index_copy_(0, rows, res[1])
-                if SL is not None:
-                    SL.index_copy_(0, rows, res[2])
-                if status is not None:
-                    status.index_copy_(0, rows, res[3])
-                if hs is not None:
-                    hot_set.index_copy_(0, rows, hs)
+            # (a skill on the dynamic fallback kernel: one launch per distinct time stamp; each group's working sets
+            # travel through its own rows of hot_set)
+            def one_stamp(tv, Qk, Xk, Yk, hs):
+                return self.solve_batch(tv, Qk, virtual_var=Xk, input_var=Yk, return_status=return_status,
+                                        hot_set=hs, use_hot=use_hot) + (hs,)
+            self._solve_per_stamp(stamps, one_stamp, (Q, X, Y, hot_set), (dQ, dX, SL, status, hot_set))
             rc = 0
         _capi.check(self._lib, rc)
-        if was_np:
-            return (dQ.cpu().numpy(), None if dX is None else dX.cpu().numpy(),
-                    None if SL is None else SL.cpu().numpy(),
-                    None if status is None else status.cpu().numpy())
-        return dQ, dX, SL, status
+        return self._to_caller((dQ, dX, SL, status), was_np)
 
     def rollout_batch(self, time_vars, robot_var, input_var=None, dt=0.008, max_speed=0.0, virtual_var=None,
                       method="euler"):
@@ -710,41 +598,19 @@ class ReactiveQPController(BaseController):
         torch = _torch()
         d = self.descriptor
         dev = self._device
-        Q, was_np = to_device_matrix(robot_var, d.n_q, dev, "robot_var")
-        if not was_np:
-            Q = Q.clone()
-        B = Q.shape[0]
-        X = dX = None
-        if d.n_x > 0:
-            if virtual_var is None:
-                raise ValueError("skill has virtual_var: pass virtual_var")
-            X, x_np = to_device_matrix(virtual_var, d.n_x, dev, "virtual_var", B)
-            if not x_np:
-                X = X.clone()
-            dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev)
-        Y = None
-        if d.n_y > 0:
-            Y, _ = to_device_matrix(input_var, d.n_y, dev, "input_var", B)
-        if method not in ("euler", "rk4"):
-            raise ValueError("method must be 'euler' or 'rk4'")
-        times = np.asarray(time_vars, dtype=float).reshape(-1)
-        n_ticks = int(times.size)
-        if method == "rk4":
-            times = np.stack([times, times + 0.5 * dt, times + 0.5 * dt, times + dt], axis=1).reshape(-1)
-        tt = np.concatenate([d.time_terms(t) for t in times]) if d.n_tslots else np.zeros(0)
-        tt, ttp = _capi.tterms_arg(tt)
+        Q, X, Y, B, was_np = self._batch_inputs(robot_var, virtual_var, input_var, clone=True)
+        n_ticks, stages, (tt, ttp) = self._rollout_times(time_vars, dt, method)
         dQ = torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
+        dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
         SL = torch.empty((B, d.n_slack), dtype=torch.float64, device=dev) if d.n_slack else None
         status = torch.empty((B,), dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
             rc = self._lib.clik_qp_rollout_batch_m(
-                self._handle, B, n_ticks, 1 if method == "rk4" else 0, float(dt), float(max_speed), ttp,
+                self._handle, B, n_ticks, stages, float(dt), float(max_speed), ttp,
                 ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX), ptr(SL), ptr(status), current_stream(dev))
         _capi.check(self._lib, rc)
         outs = (Q, dQ, SL, status) if X is None else (Q, X, dQ, dX, SL, status)
-        if was_np:
-            return tuple(None if o is None else o.cpu().numpy() for o in outs)
-        return outs
+        return self._to_caller(outs, was_np)
 
     def bind_batch(self, robot_var, input_var=None, virtual_var=None, out=None, hot_start=False, hot_set=None):
         """Pre-bind device tensors and return ``tick(time_var=0.0)``: one kernel
@@ -757,13 +623,7 @@ class ReactiveQPController(BaseController):
         torch = _torch()
         d = self.descriptor
         dev = self._device
-        Q, _ = to_device_matrix(robot_var, d.n_q, dev, "robot_var")
-        B = Q.shape[0]
-        X = Y = None
-        if d.n_x > 0:
-            X, _ = to_device_matrix(virtual_var, d.n_x, dev, "virtual_var", B)
-        if d.n_y > 0:
-            Y, _ = to_device_matrix(input_var, d.n_y, dev, "input_var", B)
+        Q, X, Y, B, _ = self._batch_inputs(robot_var, virtual_var, input_var)
         check_out_tensor(out, (B, d.n_q), "float64", dev, "out")
         dQ = out if out is not None else torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
         dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
@@ -801,13 +661,7 @@ class ReactiveQPController(BaseController):
         torch = _torch()
         d = self.descriptor
         dev = self._device
-        Q, was_np = to_device_matrix(robot_var, d.n_q, dev, "robot_var")
-        B = Q.shape[0]
-        X = Y = None
-        if d.n_x > 0:
-            X, _ = to_device_matrix(virtual_var, d.n_x, dev, "virtual_var", B)
-        if d.n_y > 0:
-            Y, _ = to_device_matrix(input_var, d.n_y, dev, "input_var", B)
+        Q, X, Y, B, was_np = self._batch_inputs(robot_var, virtual_var, input_var)
         nv, nc = self.n_qp_vars, self.n_qp_rows
         Hd = torch.empty((B, nv), dtype=torch.float64, device=dev)
         A = torch.empty((B, nc, nv), dtype=torch.float64, device=dev)
@@ -819,9 +673,7 @@ class ReactiveQPController(BaseController):
                 self._handle, B, ttp, ptr(Q), ptr(X), ptr(Y), ptr(Hd), ptr(A),
                 ptr(lb), ptr(ub), current_stream(dev))
         _capi.check(self._lib, rc)
-        if was_np:
-            return Hd.cpu().numpy(), A.cpu().numpy(), lb.cpu().numpy(), ub.cpu().numpy()
-        return Hd, A, lb, ub
+        return self._to_caller((Hd, A, lb, ub), was_np)
 
     def solve(self, time_var, robot_var, virtual_var=None, input_var=None,
               warmstart_robot_vel_var=None, warmstart_virtual_vel_var=None,
@@ -830,36 +682,16 @@ class ReactiveQPController(BaseController):
         (reactive_qp.py:461-528): ``(robot_vel DM, virtual_vel DM | None,
         slack DM | None)``; raises RuntimeError when the QP is infeasible (the
         reference surfaces qpOASES failure as a CasADi RuntimeError)."""
-        spec = self.skill_spec
-        q = _flat(robot_var, spec.n_robot_var, "robot_var")
-        x = y = None
-        if spec.n_virtual_var > 0:
-            x = _flat(virtual_var if virtual_var is not None
-                      else np.zeros(spec.n_virtual_var), spec.n_virtual_var, "virtual_var")
-        if spec.n_input_var > 0:
-            y = _flat(input_var if input_var is not None
-                      else np.zeros(spec.n_input_var), spec.n_input_var, "input_var")
         # B = 1 through persistent pinned / device staging (one copy each way); the working set of
         # the previous call hot-starts this one, like the reference's stateful qpOASES instance
-        self._require_handle()
-        torch = _torch()
+        slot, pq, px, py = self._stage_solve(robot_var, virtual_var, input_var)
         d = self.descriptor
-        nq, nx, ny, ns = d.n_q, d.n_x, d.n_y, d.n_slack
-        slot = getattr(self, "_slot", None)
-        if slot is None:
-            slot = self._slot = SingleSlot(self._device, nq + nx + ny, nq + nx + ns, 2)
-            self._slot_calls = 0
-        slot.in_np[:nq] = q
-        if nx:
-            slot.in_np[nq:nq + nx] = x
-        if ny:
-            slot.in_np[nq + nx:nq + nx + ny] = y
-        tt, ttp = _capi.tterms_arg(d.time_terms(float(_scalar(time_var))))
+        nq, nx, ns = d.n_q, d.n_x, d.n_slack
+        tt, ttp = _capi.tterms_arg(d.time_terms(float(scalar_of(time_var))))
         with slot.guard():
             stream = slot.begin()
             rc = self._lib.clik_qp_solve_batch_hot(
-                self._handle, 1, ttp, slot.in_ptr(0), slot.in_ptr(nq) if nx else None,
-                slot.in_ptr(nq + nx) if ny else None, slot.out_ptr(0), slot.out_ptr(nq) if nx else None,
+                self._handle, 1, ttp, pq, px, py, slot.out_ptr(0), slot.out_ptr(nq) if nx else None,
                 slot.out_ptr(nq + nx) if ns else None, slot.int_ptr(0), slot.int_ptr(1),
                 1 if self._slot_calls > 0 else 0, stream)
             _capi.check(self._lib, rc)
@@ -871,7 +703,11 @@ class ReactiveQPController(BaseController):
                                % ("infeasible" if status == 2 else "hit the iteration cap"))
         out = slot.out_f.copy()
         res_robot_vel = cs.DM(out[:nq])
-        res_virtual_vel = cs.DM(out[nq:nq + nx]) if (nx and spec._has_virtual) else None
+        res_virtual_vel = cs.DM(out[nq:nq + nx]) if (nx and self.skill_spec._has_virtual) else None
         res_slack = cs.DM(out[nq + nx:nq + nx + ns]) if ns else None
         self.res = {"x": cs.DM(out[:nq + nx + ns])}
         return res_robot_vel, res_virtual_vel, res_slack
+
+    def _slot_results(self):
+        d = self.descriptor
+        return d.n_q + d.n_x + d.n_slack, 2
