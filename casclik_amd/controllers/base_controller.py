@@ -227,6 +227,45 @@ def flat_vector(v, n, what):
     return arr
 
 
+def rollout_records(n_ticks, record_every):
+    """Number of records ``R = n_ticks // record_every`` of a recording rollout (record r is taken after tick
+    ``(r + 1) * record_every``, counted from 1; ticks after the last multiple are not recorded; ``record_every >
+    n_ticks`` gives none); ``None`` when ``record_every`` is None (recording off).  ValueError unless an int >= 1."""
+    if record_every is None:
+        return None
+    if isinstance(record_every, bool) or not isinstance(record_every, (int, np.integer)) or record_every < 1:
+        raise ValueError("record_every must be an int >= 1 or None, got %r" % (record_every,))
+    return int(n_ticks) // int(record_every)
+
+
+def per_tick_input(input_var, n_ticks, n_y):
+    """Is ``input_var`` one target per tick?  True for a ``[n_ticks, B, n_y]`` array or tensor (tick i reads record
+    i); False for what a rollout took before (``[B, n_y]``, a vector, None).  ValueError for a 3-D ``input_var`` whose
+    first dimension is not ``n_ticks`` or whose last is not ``n_y``."""
+    if input_var is None or hasattr(input_var, "toarray"):
+        return False
+    shape = tuple(input_var.shape) if hasattr(input_var, "shape") else np.shape(input_var)
+    if len(shape) != 3:
+        return False
+    if shape[0] != n_ticks:
+        raise ValueError("input_var [n_ticks, B, n_y] has %d records, the rollout %d ticks" % (shape[0], n_ticks))
+    if shape[2] != n_y:
+        raise ValueError("input_var must have %d columns, got shape %s" % (n_y, shape))
+    return True
+
+
+def record_layout(fields, R, B):
+    """``{name: (shape, dtype name)}`` of the records of a rollout: ``fields`` is a list of ``(name, width, dtype
+    name)``; width 0 leaves the field out, width None makes it ``[R, B]`` (one number per instance), any other
+    ``[R, B, width]``."""
+    out = {}
+    for name, width, dtype in fields:
+        if width == 0:
+            continue
+        out[name] = ((R, B) if width is None else (R, B, int(width)), dtype)
+    return out
+
+
 class BaseController(object):
     """What a device controller is apart from its mathematics.  A controller class names the C entry points that make
     and free its handle (``_create_fn`` / ``_destroy_fn``), returns their options structure from ``_c_options()``, says
@@ -271,6 +310,8 @@ class BaseController(object):
             rc = getattr(self._lib, self._create_fn)(C.byref(cdesc), C.byref(copts), C.byref(handle))
         _capi.check(self._lib, rc)
         self._handle = handle
+        self._setup_c = (cdesc, copts)      # (the recording rollouts are instantiated later, at their first use)
+        self._rec_kernel = None
         return cdesc, copts
 
     def _want_jit(self):
@@ -380,6 +421,58 @@ class BaseController(object):
             stage_times = np.stack([times, times + 0.5 * dt, times + 0.5 * dt, times + dt], axis=1).reshape(-1)
         tt = np.concatenate([d.time_terms(t) for t in stage_times]) if d.n_tslots else np.zeros(0)
         return int(times.size), 1 if method == "rk4" else 0, _capi.tterms_arg(tt)
+
+    def _rollout_io(self, robot_var, virtual_var, input_var, n_ticks, record_every, record_out, fields):
+        """The marshalling of a rollout: ``(Q, X, Y, B, was_np, y_per_tick, rec)``.  ``Q`` / ``X`` are copies the
+        launch overwrites with the final state.  ``input_var`` may be ``[n_ticks, B, n_y]`` - one target per tick,
+        ``y_per_tick`` is then 1 and ``Y`` that whole tensor - or what it was before.  ``rec``: None without
+        ``record_every``, else the dict of ``[R, B, .]`` record tensors (``record_layout`` of ``fields``) on the device -
+        those of ``record_out`` (validated with ``check_out_tensor``; every key must be a field) and new ones for the
+        rest."""
+        torch = _torch()
+        d, dev = self.descriptor, self._device
+        R = rollout_records(n_ticks, record_every)
+        y_per_tick = 1 if d.n_y > 0 and per_tick_input(input_var, n_ticks, d.n_y) else 0
+        Y3 = None
+        if y_per_tick:
+            if isinstance(input_var, torch.Tensor):
+                Y3 = input_var.to(device=dev, dtype=torch.float64).contiguous()
+            else:
+                Y3 = torch.from_numpy(np.ascontiguousarray(np.asarray(input_var, dtype=np.float64))).to(dev)
+            input_var = Y3[0] if n_ticks > 0 else None
+        Q, X, Y, B, was_np = self._batch_inputs(robot_var, virtual_var, input_var, clone=True)
+        if Y3 is not None:
+            Y = Y3
+        rec = None
+        if R is not None:
+            rec = {}
+            given = dict(record_out or {})
+            for name, (shape, dtype) in record_layout(fields, R, B).items():
+                t = given.pop(name, None)
+                check_out_tensor(t, shape, dtype, dev, "record_out[%r]" % name)
+                rec[name] = t if t is not None else torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
+            if given:
+                raise ValueError("record_out has no field(s) %s for this skill" % ", ".join(sorted(map(repr, given))))
+        elif record_out:
+            raise ValueError("record_out needs record_every")
+        return Q, X, Y, B, was_np, y_per_tick, rec
+
+    def _rollout_result(self, outs, rec, was_np):
+        """What a rollout returns: ``outs`` in the caller's container type and - when recording - the dict of records
+        as one more, last element."""
+        res = self._to_caller(outs, was_np)
+        if rec is None:
+            return res
+        return tuple(res) + ({k: (v.cpu().numpy() if was_np else v) for k, v in rec.items()},)
+
+    def _require_rec_kernel(self, attach):
+        """The recording / per-tick-target rollouts of this controller's skill, instantiated and attached at their
+        first use (``attach()``: the controller's ``jit.attach_rec`` / ``attach_qp_rec`` call) and cached like every
+        other instantiation.  Where no kernel may be instantiated (``_want_jit``) or none can be, nothing is attached
+        and the library refuses the call: there is no chunked fallback."""
+        if self._rec_kernel is None and self._want_jit():
+            with _torch().cuda.device(self._device):
+                self._rec_kernel = attach() or False
 
     # -- resident ticks -----------------------------------------------------------------------------------------
     def _resident_setup(self, waves, ring_depth, publish_ahead, stream, time_var):

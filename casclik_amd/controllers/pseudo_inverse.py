@@ -396,30 +396,50 @@ class PseudoInverseController(BaseController):
                 "keep": (Q, Y, tt)}
 
     def rollout_batch(self, time_vars, robot_var, input_var=None, dt=0.008,
-                      max_speed=0.0, virtual_var=None, method="euler"):
+                      max_speed=0.0, virtual_var=None, method="euler", record_every=None, record_out=None):
         """``len(time_vars)`` ticks of solve -> clamp(+-max_speed) -> integrate in one launch.
         ``method="euler"``: ``q += dq*dt``, the host loop of ur5_moe2016_example2.ipynb:537-545;
         ``method="rk4"``: classical Runge-Kutta with the controller as the right-hand side
         (casclik/integration_methods.py:17-23: k1..k4 at t, t+dt/2, t+dt/2, t+dt, each clamped).
         Returns (q_final, dq_last, mode_last); for a skill with virtual variables (path following,
         cart_on_track_1D...ipynb cell 60: pass ``virtual_var``) the path parameters are integrated
-        alongside, unclamped, and the result is (q_final, x_final, dq_last, dx_last, mode_last)."""
+        alongside, unclamped, and the result is (q_final, x_final, dq_last, dx_last, mode_last).
+
+        Trajectory in: ``input_var`` may be ``[n_ticks, B, n_y]``, tick i then reads record i (``"rk4"``: all four
+        stages of the tick).  Trajectory out: ``record_every=k`` appends one last element to the result, a dict of
+        ``[n_ticks // k, B, .]`` arrays ``q``, ``dq`` (``x``, ``dx`` with virtual variables) and ``mode [R, B]``: entry
+        r is what a launch ending at tick ``(r + 1) * k`` returns.  ``record_out``: preallocated device tensors for
+        some of them.  Both need a kernel instantiated for the skill (NotImplementedError otherwise)."""
         self._require_handle()
         torch = _torch()
         d = self.descriptor
         dev = self._device
         n_ticks, stages, (tt, ttp) = self._rollout_times(time_vars, dt, method)
-        Q, X, Y, B, was_np = self._batch_inputs(robot_var, virtual_var, input_var, clone=True)
+        Q, X, Y, B, was_np, y_per_tick, rec = self._rollout_io(
+            robot_var, virtual_var, input_var, n_ticks, record_every, record_out,
+            [("q", d.n_q, "float64"), ("dq", d.n_q, "float64"), ("x", d.n_x, "float64"), ("dx", d.n_x, "float64"),
+             ("mode", None, "int32")])
         dQ = torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
         dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
         mode = torch.empty((B,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            rc = self._lib.clik_pinv_rollout_batch_m(
-                self._handle, B, n_ticks, stages, float(dt), float(max_speed), ttp,
+        args = (self._handle, B, n_ticks, stages, float(dt), float(max_speed), ttp,
                 ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX), ptr(mode), current_stream(dev))
+        if rec is None and not y_per_tick:
+            with torch.cuda.device(dev):
+                rc = self._lib.clik_pinv_rollout_batch_m(*args)
+        else:
+            from .. import jit
+            cdesc, copts = self._setup_c
+            self._require_rec_kernel(lambda: jit.attach_rec(self._lib, self._handle, cdesc, copts,
+                                                            extern=d.extern_source(), values=bool(self.value_kernel)))
+            r = rec or {}
+            with torch.cuda.device(dev):
+                rc = self._lib.clik_pinv_rollout_batch_rec(
+                    *args, y_per_tick, int(record_every or 0), ptr(r.get("q")), ptr(r.get("dq")), ptr(r.get("x")),
+                    ptr(r.get("dx")), ptr(r.get("mode")))
         _capi.check(self._lib, rc)
         outs = (Q, X, dQ, dX, mode) if d.n_x > 0 else (Q, dQ, mode)
-        return self._to_caller(outs, was_np)
+        return self._rollout_result(outs, rec, was_np)
 
     def solve(self, time_var, robot_var, virtual_var=None, input_var=None,
               warmstart_robot_vel_var=None, warmstart_virtual_vel_var=None,

@@ -585,7 +585,7 @@ class ReactiveQPController(BaseController):
         return self._to_caller((dQ, dX, SL, status), was_np)
 
     def rollout_batch(self, time_vars, robot_var, input_var=None, dt=0.008, max_speed=0.0, virtual_var=None,
-                      method="euler"):
+                      method="euler", record_every=None, record_out=None):
         """``len(time_vars)`` ticks of QP solve -> clamp(+-max_speed) -> integrate in
         one launch, the working set hot-started from tick to tick (the host loop of
         ur5_moe2016_example2.ipynb:537-545 for this controller).  ``method="euler"``: ``q += dq*dt``;
@@ -593,24 +593,44 @@ class ReactiveQPController(BaseController):
         (casclik/integration_methods.py:17-23: k1..k4 at t, t+dt/2, t+dt/2, t+dt, each clamped).  Returns
         (q_final, dq_last, slack_last | None, status [B] = worst status met); for a skill with
         virtual variables (pass ``virtual_var``; cart_on_track_1D...ipynb cell 60) they are integrated
-        alongside, unclamped: (q_final, x_final, dq_last, dx_last, slack_last | None, status)."""
+        alongside, unclamped: (q_final, x_final, dq_last, dx_last, slack_last | None, status).
+
+        Trajectory in: ``input_var`` may be ``[n_ticks, B, n_y]``, tick i then reads record i (``"rk4"``: all four
+        stages of the tick).  Trajectory out: ``record_every=k`` appends one last element to the result, a dict of
+        ``[n_ticks // k, B, .]`` arrays ``q``, ``dq`` (``x``, ``dx`` with virtual variables; ``slack`` when the skill has
+        slack) and ``status [R, B]``, the worst status up to and including that tick: entry r is what a launch ending
+        at tick ``(r + 1) * k`` returns.  ``record_out``: preallocated device tensors for some of them.  Both need a
+        kernel instantiated for the skill (NotImplementedError otherwise)."""
         self._require_handle()
         torch = _torch()
         d = self.descriptor
         dev = self._device
-        Q, X, Y, B, was_np = self._batch_inputs(robot_var, virtual_var, input_var, clone=True)
         n_ticks, stages, (tt, ttp) = self._rollout_times(time_vars, dt, method)
+        Q, X, Y, B, was_np, y_per_tick, rec = self._rollout_io(
+            robot_var, virtual_var, input_var, n_ticks, record_every, record_out,
+            [("q", d.n_q, "float64"), ("dq", d.n_q, "float64"), ("x", d.n_x, "float64"), ("dx", d.n_x, "float64"),
+             ("slack", d.n_slack, "float64"), ("status", None, "int32")])
         dQ = torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
         dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
         SL = torch.empty((B, d.n_slack), dtype=torch.float64, device=dev) if d.n_slack else None
         status = torch.empty((B,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            rc = self._lib.clik_qp_rollout_batch_m(
-                self._handle, B, n_ticks, stages, float(dt), float(max_speed), ttp,
+        args = (self._handle, B, n_ticks, stages, float(dt), float(max_speed), ttp,
                 ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX), ptr(SL), ptr(status), current_stream(dev))
+        if rec is None and not y_per_tick:
+            with torch.cuda.device(dev):
+                rc = self._lib.clik_qp_rollout_batch_m(*args)
+        else:
+            from .. import jit
+            self._require_rec_kernel(lambda: jit.attach_qp_rec(self._lib, self._handle, self._setup_c[0],
+                                                               extern=d.extern_source(), values=bool(self.value_kernel)))
+            r = rec or {}
+            with torch.cuda.device(dev):
+                rc = self._lib.clik_qp_rollout_batch_rec(
+                    *args, y_per_tick, int(record_every or 0), ptr(r.get("q")), ptr(r.get("dq")), ptr(r.get("x")),
+                    ptr(r.get("dx")), ptr(r.get("slack")), ptr(r.get("status")))
         _capi.check(self._lib, rc)
         outs = (Q, dQ, SL, status) if X is None else (Q, X, dQ, dX, SL, status)
-        return self._to_caller(outs, was_np)
+        return self._rollout_result(outs, rec, was_np)
 
     def bind_batch(self, robot_var, input_var=None, virtual_var=None, out=None, hot_start=False, hot_set=None):
         """Pre-bind device tensors and return ``tick(time_var=0.0)``: one kernel

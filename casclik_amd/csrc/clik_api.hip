@@ -92,7 +92,16 @@ struct clik_pinv {
     // ... and its resident form (clik_pinv_attach_resident_kernel)
     hipError_t (*val_resident)(const TickArgs*, long long, const double*, const double*, double*, int32_t*, void*,
                                unsigned*, int, unsigned long long, hipStream_t);
+    // the recording / per-tick-target rollouts (clik_pinv_attach_rec_kernel): image-reading and value-specialised
+    clik_jit_rollout_fn rec_rollout = nullptr;
+    clik_jit_rollout_fn val_rec_rollout = nullptr;
 };
+
+// clik_jit_qp_rollout_rec / clik_jit_qp_value_rollout_rec: the rollouts' arguments and the RollRec
+typedef hipError_t (*clik_qp_rec_fn)(const void*, const double*, int, double, double, long long, double*, const double*,
+                                     double*, double*, int32_t*, double*, double*, hipStream_t, int, const clik::RollRec*);
+typedef hipError_t (*clik_qp_value_rec_fn)(const double*, int, double, double, long long, double*, const double*, double*,
+                                           double*, int32_t*, double*, double*, hipStream_t, int, const clik::RollRec*);
 
 struct clik_qp {
     DevSkill  host;
@@ -108,6 +117,9 @@ struct clik_qp {
     clik::qp_value_fn val_solve;     // per-tick kernel with this skill's numbers and QP options compiled in
     clik::qp_value_rollout_fn val_rollout;   // ... and its on-device rollout (box family), or null
     clik::qp_value_resident_fn val_resident; // ... and its resident form (clik_qp_attach_resident_kernel), or null
+    // the recording / per-tick-target rollouts (clik_qp_attach_rec_kernel): image-reading and value-specialised (box)
+    clik_qp_rec_fn rec_rollout = nullptr;
+    clik_qp_value_rec_fn val_rec_rollout = nullptr;
     char      jit_name[64];
     // work area of the global-workspace kernels (clik_workspace.hpp): belongs to this handle, released by clik_qp_destroy
     clik::GwsOwner* gws;
@@ -1135,9 +1147,61 @@ extern "C" int clik_pinv_rollout_batch_x(const clik_pinv* hc, int64_t B, int32_t
                                      stream);
 }
 
+// what _rec adds to _m, checked: the RollRec the kernels take, or an error
+static int roll_rec_of(int64_t B, int n_y, int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
+                       double* rec_x, double* rec_dx, double* rec_slack, int32_t* rec_flag, clik::RollRec* rr)
+{
+    if (record_every < 0) return fail(CLIK_EINVAL, "record_every must be 0 (no records) or the number of ticks per record");
+    rr->y_stride = (y_per_tick != 0 && n_y > 0) ? (long long)B * n_y : 0;
+    rr->every = record_every;
+    rr->q = rec_q;
+    rr->dq = rec_dq;
+    rr->x = rec_x;
+    rr->dx = rec_dx;
+    rr->slack = rec_slack;
+    rr->flag = rec_flag;
+    return CLIK_OK;
+}
+
+static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
+                               double max_speed, const double* tterms, double* q, double* x, const double* y,
+                               double* dq, double* dx, int32_t* mode, void* stream, const clik::RollRec* rec);
+
 extern "C" int clik_pinv_rollout_batch_m(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
                                          double max_speed, const double* tterms, double* q, double* x,
                                          const double* y, double* dq, double* dx, int32_t* mode, void* stream)
+{
+    return pinv_rollout_common(h, B, n_ticks, method, dt, max_speed, tterms, q, x, y, dq, dx, mode, stream, nullptr);
+}
+
+extern "C" int clik_pinv_rollout_batch_rec(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
+                                           double max_speed, const double* tterms, double* q, double* x,
+                                           const double* y, double* dq, double* dx, int32_t* mode, void* stream,
+                                           int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
+                                           double* rec_x, double* rec_dx, int32_t* rec_mode)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    clik::RollRec rr;
+    int rc = roll_rec_of(B, h->host.d.n_y, y_per_tick, record_every, rec_q, rec_dq, rec_x, rec_dx, nullptr, rec_mode, &rr);
+    if (rc) return rc;
+    return pinv_rollout_common(h, B, n_ticks, method, dt, max_speed, tterms, q, x, y, dq, dx, mode, stream, &rr);
+}
+
+extern "C" int clik_pinv_attach_rec_kernel(clik_pinv* h, void* rollout_rec_fn, void* value_rollout_rec_fn)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    CLIK_NEEDS_DEVICE_HANDLE(h);
+    if (rollout_rec_fn && !h->jit_solve && !h->jit_rollout && !(h->kernel >= 0 && clik::pinv_kernel_is_static(h->kernel)))
+        return fail(CLIK_EUNSUPPORTED, "recording rollouts exist for skills a shape-specialised kernel serves");
+    if (rollout_rec_fn && !h->d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device: attach the kernel first");
+    h->rec_rollout = (clik_jit_rollout_fn)rollout_rec_fn;
+    h->val_rec_rollout = (clik_jit_rollout_fn)value_rollout_rec_fn;
+    return CLIK_OK;
+}
+
+static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
+                               double max_speed, const double* tterms, double* q, double* x, const double* y,
+                               double* dq, double* dx, int32_t* mode, void* stream, const clik::RollRec* rec)
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
     CLIK_NEEDS_DEVICE_HANDLE(h);
@@ -1159,12 +1223,26 @@ extern "C" int clik_pinv_rollout_batch_m(const clik_pinv* h, int64_t B, int32_t 
     if (h->kernel < 0 && !h->jit_rollout) return no_kernel_for_wide_state(S, "clik_pinv_rollout_batch");
     if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
     if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    if (rec && !h->rec_rollout)
+        return fail(CLIK_EUNSUPPORTED, "records and per-tick targets need a shape-specialised recording rollout (none "
+                                       "attached for this skill: clik_pinv_attach_rec_kernel)");
     const int stages = method == CLIK_INTEGRATE_RK4 ? 4 : 1;
     double* d_tt = nullptr;
     int rc = stage_tterms(tterms, (size_t)n_ticks * stages * 2 * (size_t)S.d.n_tslots, (hipStream_t)stream, &d_tt);
     if (rc) return rc;
-    const clik::LaunchArgs la = {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->policy, x, dx, stages, nullptr};
+    const clik::LaunchArgs la = {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->policy, x, dx, stages, nullptr,
+                                 rec};
     hipError_t e = hipErrorNotSupported;
+    if (rec) {
+        if (h->val_rec_rollout && h->val_rollout && S.d.n_x == 0 &&
+            clik::pinv_value_variant(clik::pinv_select(S.shape, h->policy, (long long)B, clik::PinvOp::rollout)))
+            e = h->val_rec_rollout(&la, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, mode, (hipStream_t)stream);
+        if (e == hipErrorNotSupported)
+            e = h->rec_rollout(&la, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, mode, (hipStream_t)stream);
+        if (d_tt) (void)hipFreeAsync(d_tt, (hipStream_t)stream);
+        if (e != hipSuccess) return hipfail(e, "pinv recording rollout launch");
+        return CLIK_OK;
+    }
     if (h->val_rollout && S.d.n_x == 0 &&
         clik::pinv_value_variant(clik::pinv_select(S.shape, h->policy, (long long)B, clik::PinvOp::rollout)))
         e = h->val_rollout(&la, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, mode, (hipStream_t)stream);
@@ -1365,9 +1443,52 @@ extern "C" int clik_qp_rollout_batch_x(const clik_qp* hc, int64_t B, int32_t n_t
                                    status, stream);
 }
 
+static int qp_rollout_common(const clik_qp* hc, int64_t B, int32_t n_ticks, int32_t method, double dt,
+                             double max_speed, const double* tterms, double* q, double* x, const double* y,
+                             double* dq, double* dx, double* slack, int32_t* status, void* stream,
+                             const clik::RollRec* rec);
+
 extern "C" int clik_qp_rollout_batch_m(const clik_qp* hc, int64_t B, int32_t n_ticks, int32_t method, double dt,
                                        double max_speed, const double* tterms, double* q, double* x, const double* y,
                                        double* dq, double* dx, double* slack, int32_t* status, void* stream)
+{
+    return qp_rollout_common(hc, B, n_ticks, method, dt, max_speed, tterms, q, x, y, dq, dx, slack, status, stream, nullptr);
+}
+
+extern "C" int clik_qp_rollout_batch_rec(const clik_qp* hc, int64_t B, int32_t n_ticks, int32_t method, double dt,
+                                         double max_speed, const double* tterms, double* q, double* x, const double* y,
+                                         double* dq, double* dx, double* slack, int32_t* status, void* stream,
+                                         int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
+                                         double* rec_x, double* rec_dx, double* rec_slack, int32_t* rec_status)
+{
+    if (!hc) return fail(CLIK_EINVAL, "null handle");
+    clik::RollRec rr;
+    int rc = roll_rec_of(B, hc->host.d.n_y, y_per_tick, record_every, rec_q, rec_dq, rec_x, rec_dx, rec_slack, rec_status,
+                         &rr);
+    if (rc) return rc;
+    return qp_rollout_common(hc, B, n_ticks, method, dt, max_speed, tterms, q, x, y, dq, dx, slack, status, stream, &rr);
+}
+
+extern "C" int clik_qp_attach_rec_kernel(clik_qp* h, void* rollout_rec_fn, void* value_rollout_rec_fn)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    CLIK_NEEDS_DEVICE_HANDLE(h);
+    if (rollout_rec_fn && !qp_static_eligible(h->host))
+        return fail(CLIK_EUNSUPPORTED, "skill is outside the shape-specialised QP family");
+    if (rollout_rec_fn) {
+        int rc = qp_upload_image(h);
+        if (rc) return rc;
+    }
+    h->rec_rollout = (clik_qp_rec_fn)rollout_rec_fn;
+    // (the value-specialised rollout exists for the box family only)
+    h->val_rec_rollout = CLIK_QP_BOX_OK(h->host.shape) ? (clik_qp_value_rec_fn)value_rollout_rec_fn : nullptr;
+    return CLIK_OK;
+}
+
+static int qp_rollout_common(const clik_qp* hc, int64_t B, int32_t n_ticks, int32_t method, double dt,
+                             double max_speed, const double* tterms, double* q, double* x, const double* y,
+                             double* dq, double* dx, double* slack, int32_t* status, void* stream,
+                             const clik::RollRec* rec)
 {
     const clik_qp* h = hc;
     if (method != CLIK_INTEGRATE_EULER && method != CLIK_INTEGRATE_RK4)
@@ -1385,9 +1506,22 @@ extern "C" int clik_qp_rollout_batch_m(const clik_qp* hc, int64_t B, int32_t n_t
         return fail(CLIK_EUNSUPPORTED, "the QP rollout needs a shape-specialised kernel (none attached for this skill)");
     if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
     if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    if (rec && !h->rec_rollout)
+        return fail(CLIK_EUNSUPPORTED, "records and per-tick targets need a shape-specialised recording rollout (none "
+                                       "attached for this skill: clik_qp_attach_rec_kernel)");
     double* d_tt = nullptr;
     int rc = stage_tterms(tterms, (size_t)n_ticks * stages * 2 * (size_t)S.d.n_tslots, (hipStream_t)stream, &d_tt);
     if (rc) return rc;
+    if (rec) {
+        hipError_t er = (k == clik::QpKernel::value && h->val_rec_rollout)
+                            ? h->val_rec_rollout(d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, slack, status, x, dx,
+                                                 (hipStream_t)stream, stages, rec)
+                            : h->rec_rollout(h->d_img, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, slack, status,
+                                             x, dx, (hipStream_t)stream, stages, rec);
+        if (d_tt) (void)hipFreeAsync(d_tt, (hipStream_t)stream);
+        if (er != hipSuccess) return hipfail(er, "qp recording rollout launch");
+        return CLIK_OK;
+    }
     hipError_t e = k == clik::QpKernel::value
                        ? h->val_rollout(d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, slack, status, x, dx,
                                         (hipStream_t)stream, stages)

@@ -278,6 +278,40 @@ struct TickArgs {
     double tv[2 * CLIK_MAX_TSLOTS];
 };
 
+// Trajectory in, trajectory out of an on-device rollout (clik_*_rollout_batch_rec, include/clik.h): the argument of the
+// recording / per-tick-target kernels (*_rec_kernel in clik_pinv_rec.hpp and clik_qp_rec.hpp, headers that only the
+// recording translation units include; the rollouts that record nothing are untouched, text and code).
+struct RollRec {
+    long long y_stride;     // doubles from tick i's input_var rows to tick i + 1's (B * n_y); 0: one [B, n_y] for the launch
+    int every;              // a record after every `every`-th tick; 0: none
+    double* q;              // [R][B][n_q] state after the recorded tick              (each pointer may be null)
+    double* dq;             // [R][B][n_q] clamped velocity applied in it (Runge-Kutta: the combined rate)
+    double* x;              // [R][B][n_x] virtual variables ...
+    double* dx;             // [R][B][n_x] ... and their rates
+    double* slack;          // [R][B][n_slack] (QP)
+    int32_t* flag;          // [R][B] pinv: the tick's mode; QP: the worst status up to and including the tick
+};
+__device__ __forceinline__ const RollRec& rec_of(const RollRec& r) { return r; }
+
+// which ticks are recorded: wave-uniform, one counter instead of a division per tick
+struct RecClock {
+    int left;
+    long long r;            // records written so far
+    __device__ __forceinline__ void start(const RollRec& a) { left = a.every; r = 0; }
+    // at the end of every tick: is this one recorded?  (the caller stores, then advances r)
+    __device__ __forceinline__ bool due(const RollRec& a)
+    {
+        if (a.every <= 0 || --left != 0) return false;
+        left = a.every;
+        return true;
+    }
+};
+// rows of the tick whose target is requested while tick `tick` runs: the next one (the last tick asks for its own again)
+__device__ __forceinline__ const double* next_rows(const double* y, const RollRec& a, const int tick, const int n_ticks)
+{
+    return y + (size_t)(tick + 1 < n_ticks ? tick + 1 : tick) * (size_t)a.y_stride;
+}
+
 __device__ __forceinline__ int tri(int i, int k) { return i * (i + 1) / 2 + k; }  // k <= i
 
 // uniform (wave-invariant) value -> SGPR

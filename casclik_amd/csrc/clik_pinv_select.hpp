@@ -138,6 +138,7 @@ struct LaunchArgs {
     double* roll_dx;
     int roll_stages;           // rollout: controller evaluations per tick (0 / 1 explicit Euler, 4 Runge-Kutta)
     const double* t_inst;      // solve: one time-slot record per instance ([B][2 * n_tslots], device) or null
+    const RollRec* roll_rec;   // recording / per-tick-target rollout (host copy, read by the launcher) or null
 };
 
 }  // namespace clik

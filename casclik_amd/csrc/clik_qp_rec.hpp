@@ -1,0 +1,439 @@
+// Rollouts that record their trajectory and read one target per tick (clik_qp_rollout_batch_rec, include/clik.h; RollRec in
+// clik_device.hpp): the loops of clik_qp_static.hpp again, as bodies with a trailing parameter pack (empty: the
+// loop as it stands there; one RollRec: records and per-tick targets), the kernels that pass them one RollRec, and their
+// launchers.  A header of its own, included by the recording translation units only (casclik_amd/jit.py): the compiler's code
+// for a kernel depends on what else its translation unit declares - with these templates declared next to them, the rollouts
+// that record nothing fused their multiply-adds in another order, and their results are pinned to the tick kernels' (the
+// smoke test: q after one tick to 1e-12).
+#pragma once
+#include "clik_qp_static.hpp"
+namespace clik {
+
+// One record of a QP rollout (RollRec): what a launch ending at this tick returns - the state, the clamped velocity and
+// the slack with the NaN of an infeasible instance, the worst status so far.  The lane stores its own rows with plain
+// stores, nothing waits for them.
+template <int NQ, int NX, int NS, int NSA>
+__device__ __forceinline__ void qp_record(const RollRec& ra, const long long row, const double (&z)[NQ + NX],
+                                          const double (&v)[NQ + NX], const double (&sl)[NSA], const int worst)
+{
+    const unsigned bad = (worst == 2) ? 0x7ff80000u : 0u;
+    if (ra.q != nullptr) {
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) ra.q[row * NQ + j] = z[j];
+    }
+    if (ra.dq != nullptr) {
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) ra.dq[row * NQ + j] = nan_or(v[j], bad);
+    }
+    if constexpr (NX > 0) {
+        if (ra.x != nullptr) {
+#pragma unroll
+            for (int j = 0; j < NX; ++j) ra.x[row * NX + j] = z[NQ + j];
+        }
+        if (ra.dx != nullptr) {
+#pragma unroll
+            for (int j = 0; j < NX; ++j) ra.dx[row * NX + j] = nan_or(v[NQ + j], bad);
+        }
+    }
+    if constexpr (NS > 0) {
+        if (ra.slack != nullptr) {
+#pragma unroll
+            for (int k = 0; k < NS; ++k) ra.slack[row * NS + k] = nan_or(sl[k], bad);
+        }
+    }
+    if (ra.flag != nullptr) ra.flag[row] = worst;
+}
+
+// ... and its on-device rollout (see qp_rollout_static_kernel): state, working set and Runge-Kutta bookkeeping in
+// registers from tick to tick, rows loaded once and stored once by the lane itself
+// REC: empty, or one RollRec (clik_device.hpp): records of the trajectory and one target row per tick.
+template <const ShapeDesc& SD, class IMGV, bool RK, class... REC>
+__device__ __forceinline__ void qp_rollout_static_box_values_body(
+    double* __restrict__ q, const double* __restrict__ y, double* __restrict__ dq, double* __restrict__ slack_out,
+    int32_t* __restrict__ status_out, const long long B, const double* __restrict__ tterms, const int n_ticks,
+    const double dt, const double max_speed, double* __restrict__ x, double* __restrict__ dx, const REC... rec)
+{
+    constexpr bool RECORD = sizeof...(REC) > 0;
+    using LY = QpLayout<SD>;
+    static_assert(LY::BOX, "box family only");
+    constexpr int N = SD.n, NX = SD.n_x, NQ = N - NX, NS = LY::NS;
+    constexpr QpImg<SD> kValues = IMGV::value;
+    constexpr int stages = RK ? 4 : 1;
+    const int lane = threadIdx.x;
+    const long long inst = (long long)blockIdx.x * WAVE + lane;
+    const bool valid = inst < B;
+    const long long row = valid ? inst : B - 1;
+    const int nts = kValues.img.n_tslots;
+    double z[N];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) z[j] = q[row * NQ + j];
+    if constexpr (NX > 0) {
+#pragma unroll
+        for (int j = 0; j < NX; ++j) z[NQ + j] = x[row * NX + j];
+    }
+    const double* ysl = SD.n_y > 0 ? y + row * SD.n_y : nullptr;
+    double v[N], sl[LY::NSA];
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = 0.0;
+#pragma unroll
+    for (int k = 0; k < LY::NSA; ++k) sl[k] = 0.0;
+    int32_t hot = 0;
+    int worst = 0;
+    // per-tick target (RollRec): the row lives in registers, and the NEXT tick's is requested at the top of a tick
+    [[maybe_unused]] RecClock clk;
+    [[maybe_unused]] double ycur[SD.n_y > 0 ? SD.n_y : 1], ynext[SD.n_y > 0 ? SD.n_y : 1];
+    if constexpr (RECORD) {
+        clk.start(rec_of(rec...));
+        if constexpr (SD.n_y > 0) {
+#pragma unroll
+            for (int k = 0; k < SD.n_y; ++k) ycur[k] = ynext[k] = ysl[k];
+            ysl = ycur;
+        }
+    }
+#pragma unroll 1
+    for (int tick = 0; tick < n_ticks; ++tick) {
+        if constexpr (RECORD && SD.n_y > 0) {
+            const RollRec& ra = rec_of(rec...);
+            if (ra.y_stride != 0) {
+                const double* yn = next_rows(y, ra, tick, n_ticks) + row * SD.n_y;
+#pragma unroll
+                for (int k = 0; k < SD.n_y; ++k) ynext[k] = yn[k];
+            }
+        }
+        double z0[N], ks[N];
+        bool okl = true;
+        if constexpr (RK) {
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                z0[j] = z[j];
+                ks[j] = 0.0;
+            }
+        }
+#pragma unroll 1
+        for (int stg = 0; stg < stages; ++stg) {
+            const TickArgs& tk = *reinterpret_cast<const TickArgs*>(tterms + ((size_t)tick * stages + stg) * 2 * nts);
+            double priv[LY::SLOTS];
+            // (one copy of the tick with a run-time `use_hot`: two copies with the flag a literal in each - as the launched and the
+            // resident kernels have - measured 85 instructions MORE per tick here, 3.78 against 3.72 us, round 6: the register
+            // allocator's doing)
+            const int st = qp_tick_static<SD, 1>(&kValues.img, &kValues.tail, tk, z, ysl, lane, valid, priv, v, sl, &hot,
+                                                 (tick | stg) > 0);
+            worst = st > worst ? st : worst;
+            okl = okl & (st != 2);              // an infeasible tick (stage) leaves the state where it was
+            if constexpr (!RK) {
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    double d = v[j];
+                    if (j < NQ && max_speed > 0.0) d = fmax(fmin(d, max_speed), -max_speed);
+                    v[j] = d;
+                    z[j] = okl ? fma(d, dt, z[j]) : z[j];
+                }
+            } else {
+                const double wgt = (stg == 0 || stg == 3) ? 1.0 : 2.0;
+                const double cnext = (stg == 2) ? dt : 0.5 * dt;
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    double d = okl ? v[j] : 0.0;
+                    if (j < NQ && max_speed > 0.0) d = fmax(fmin(d, max_speed), -max_speed);
+                    ks[j] = fma(wgt, d, ks[j]);
+                    z[j] = fma(d, cnext, z0[j]);
+                }
+            }
+        }
+        if constexpr (RK) {
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                const double d = ks[j] * (1.0 / 6.0);
+                v[j] = okl ? d : v[j];
+                z[j] = okl ? fma(d, dt, z0[j]) : z0[j];
+            }
+        }
+        if constexpr (RECORD) {
+            const RollRec& ra = rec_of(rec...);
+            if (clk.due(ra)) {
+                if (valid) qp_record<NQ, NX, NS, LY::NSA>(ra, clk.r * B + inst, z, v, sl, worst);
+                ++clk.r;
+            }
+            if constexpr (SD.n_y > 0) {
+#pragma unroll
+                for (int k = 0; k < SD.n_y; ++k) ycur[k] = ynext[k];
+            }
+        }
+    }
+    if (valid) {
+        const unsigned bad = (worst == 2) ? 0x7ff80000u : 0u;      // (nan_or: the NaN of an infeasible instance, as bits)
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            q[inst * NQ + j] = z[j];
+            dq[inst * NQ + j] = nan_or(v[j], bad);
+        }
+        if constexpr (NX > 0) {
+#pragma unroll
+            for (int j = 0; j < NX; ++j) {
+                x[inst * NX + j] = z[NQ + j];
+                dx[inst * NX + j] = nan_or(v[NQ + j], bad);
+            }
+        }
+        if constexpr (NS > 0) {
+            if (slack_out != nullptr) {
+#pragma unroll
+                for (int k = 0; k < NS; ++k) slack_out[inst * NS + k] = nan_or(sl[k], bad);
+            }
+        }
+        if (status_out != nullptr) status_out[inst] = worst;
+    }
+}
+
+// ... recording its trajectory / reading one target per tick (RollRec, clik_device.hpp)
+template <const ShapeDesc& SD, class IMGV, bool RK>
+__global__ __launch_bounds__(WAVE) void qp_rollout_static_box_values_rec_kernel(
+    double* __restrict__ q, const double* __restrict__ y, double* __restrict__ dq, double* __restrict__ slack_out,
+    int32_t* __restrict__ status_out, const long long B, const double* __restrict__ tterms, const int n_ticks,
+    const double dt, const double max_speed, double* __restrict__ x, double* __restrict__ dx, const RollRec rec)
+{
+    qp_rollout_static_box_values_body<SD, IMGV, RK, RollRec>(q, y, dq, slack_out, status_out, B, tterms, n_ticks, dt, max_speed, x, dx, rec);
+}
+
+// n_ticks of (QP tick -> clamp(+-max_speed) -> explicit Euler q += dq dt) in one launch: the host
+// loop of the notebooks (ur5_moe2016_example2.ipynb:537-545) for the QP controller.  The working
+// set stays in a register from tick to tick (hot start), the skill image and the targets in LDS.
+// q is updated in place; dq / slack receive the last tick, status the worst status met.
+// RK: classical Runge-Kutta with the controller as the right-hand side (integration_methods.py:17-23; four QP
+// solves per tick, the working set hot-started from stage to stage, tterms holds four records per tick) instead of
+// explicit Euler; a tick with an infeasible stage leaves the state where it was.
+// REC: empty, or one RollRec (clik_device.hpp): records of the trajectory and one target row per tick.
+template <const ShapeDesc& SD, bool RK, class... REC>
+__device__ __forceinline__ void qp_rollout_static_body(
+    const void* __restrict__ img_g, double* __restrict__ q, const double* __restrict__ y,
+    double* __restrict__ dq, double* __restrict__ slack_out, int32_t* __restrict__ status_out, const long long B,
+    const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed,
+    double* __restrict__ x, double* __restrict__ dx, const REC... rec)
+{
+    constexpr bool RECORD = sizeof...(REC) > 0;
+    // x / dx: virtual variables, integrated like the robot variables and never clamped (null without them)
+    extern __shared__ double lds[];
+    using LY = QpLayout<SD>;
+    constexpr int N = SD.n;
+    constexpr int NX = SD.n_x, NQ = N - NX;
+    constexpr int NS = LY::NS;
+    const int lane = threadIdx.x;
+    const long long b0 = (long long)blockIdx.x * WAVE;
+    const long long left = B - b0;
+    const int rows_valid = left < WAVE ? (int)left : WAVE;
+    const bool valid = lane < rows_valid;
+    double* slots = lds + LY::IMG_DOUBLES;
+    double* zs = slots + LY::O_Z * WAVE;
+    double* ys = slots + LY::O_Y * WAVE;
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    {
+        d2 img[LY::IMG_CHUNKS];
+        const d2* src = (const d2*)img_g;
+#pragma unroll
+        for (int k = 0; k < LY::IMG_CHUNKS; ++k) img[k] = src[k * WAVE + lane];
+        double qv[NQ], xv[NX > 0 ? NX : 1], yv[SD.n_y > 0 ? SD.n_y : 1];
+        stage_load<NQ>(q + b0 * NQ, NQ, rows_valid, lane, qv);
+        if constexpr (NX > 0) stage_load<NX>(x + b0 * NX, NX, rows_valid, lane, xv);
+        if constexpr (SD.n_y > 0) stage_load<SD.n_y>(y + b0 * SD.n_y, SD.n_y, rows_valid, lane, yv);
+        d2* dst = (d2*)lds;
+#pragma unroll
+        for (int k = 0; k < LY::IMG_CHUNKS; ++k) dst[k * WAVE + lane] = img[k];
+        rows_to_lds<NQ>(qv, zs, lane);
+        if constexpr (NX > 0) rows_to_lds<NX>(xv, zs + NQ * WAVE, lane);
+        if constexpr (SD.n_y > 0) rows_to_lds<SD.n_y>(yv, ys, lane);
+    }
+    __syncthreads();
+    const Img<SD>* __restrict__ S = (const Img<SD>*)lds;
+    const QpTail* __restrict__ T = (const QpTail*)((const char*)lds + LY::TAIL_OFF);
+    const int nts = S->n_tslots;
+    const double* ysl = ys + lane * SD.n_y;
+    double* xs = zs + NQ * WAVE;
+    double z[N];
+    state_from_lds<NQ, NX>(zs, xs, lane, z);
+    double v[N], sl[LY::NSA];
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = 0.0;
+#pragma unroll
+    for (int k = 0; k < LY::NSA; ++k) sl[k] = 0.0;
+    int32_t hot = 0;
+    int worst = 0;
+    [[maybe_unused]] RecClock clk;
+    [[maybe_unused]] double ynext[SD.n_y > 0 ? SD.n_y : 1];
+    if constexpr (RECORD) clk.start(rec_of(rec...));
+    // per-tick target: the NEXT tick's block is requested at the top of a tick (coalesced, as the first one was) and
+    // replaces this tick's in LDS at its end, where the tick's record is stored too (see pinv_rollout_static_kernel)
+    auto request_rows = [&](const int tick) __attribute__((always_inline)) {
+        if constexpr (RECORD && SD.n_y > 0) {
+            const RollRec& ra = rec_of(rec...);
+            if (ra.y_stride != 0)
+                stage_load<SD.n_y>(next_rows(y, ra, tick, n_ticks) + b0 * SD.n_y, SD.n_y, rows_valid, lane, ynext);
+        }
+    };
+    auto end_of_tick = [&]() __attribute__((always_inline)) {
+        if constexpr (RECORD) {
+            const RollRec& ra = rec_of(rec...);
+            if (clk.due(ra)) {
+                if (valid) qp_record<NQ, NX, NS, LY::NSA>(ra, clk.r * B + b0 + lane, z, v, sl, worst);
+                ++clk.r;
+            }
+            if constexpr (SD.n_y > 0) {
+                if (ra.y_stride != 0) {
+                    rows_to_lds<SD.n_y>(ynext, ys, lane);
+                    __syncthreads();
+                }
+            }
+        }
+    };
+    if constexpr (!RK) {
+#pragma unroll 1
+        for (int tick = 0; tick < n_ticks; ++tick) {
+            request_rows(tick);
+            asm volatile("" ::: "memory");      // (keeps the image reads inside the loop, see pinv_rollout_static_kernel)
+            const TickArgs& tk = *reinterpret_cast<const TickArgs*>(tterms + (size_t)tick * 2 * nts);
+            const int st = qp_tick_static<SD>(S, T, tk, z, ysl, lane, valid, slots, v, sl, &hot, tick > 0);
+            worst = st > worst ? st : worst;
+            const bool okl = st != 2;           // an infeasible tick leaves the state where it is
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                double d = v[j];
+                if (j < NQ && max_speed > 0.0) d = fmax(fmin(d, max_speed), -max_speed);
+                v[j] = d;
+                z[j] = okl ? fma(d, dt, z[j]) : z[j];
+            }
+            end_of_tick();
+        }
+    } else {
+        double* z0s = slots + LY::SLOTS * WAVE;      // [N][64] state at the start of the tick, [N][64] sum of w_i k_i
+        double* kss = z0s + N * WAVE;
+#pragma unroll 1
+        for (int tick = 0; tick < n_ticks; ++tick) {
+            request_rows(tick);
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                z0s[j * WAVE + lane] = z[j];
+                kss[j * WAVE + lane] = 0.0;
+            }
+            bool okl = true;
+#pragma unroll 1
+            for (int stg = 0; stg < 4; ++stg) {
+                asm volatile("" ::: "memory");
+                const TickArgs& tk = *reinterpret_cast<const TickArgs*>(tterms + ((size_t)tick * 4 + stg) * 2 * nts);
+                const int st = qp_tick_static<SD>(S, T, tk, z, ysl, lane, valid, slots, v, sl, &hot, (tick | stg) > 0);
+                worst = st > worst ? st : worst;
+                okl = okl & (st != 2);
+                const double wgt = (stg == 0 || stg == 3) ? 1.0 : 2.0;
+                const double cnext = (stg == 2) ? dt : 0.5 * dt;
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    double d = okl ? v[j] : 0.0;
+                    if (j < NQ && max_speed > 0.0) d = fmax(fmin(d, max_speed), -max_speed);
+                    kss[j * WAVE + lane] = fma(wgt, d, kss[j * WAVE + lane]);
+                    z[j] = fma(d, cnext, z0s[j * WAVE + lane]);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                const double d = kss[j * WAVE + lane] * (1.0 / 6.0);
+                v[j] = okl ? d : v[j];
+                z[j] = okl ? fma(d, dt, z0s[j * WAVE + lane]) : z0s[j * WAVE + lane];
+            }
+            end_of_tick();
+        }
+    }
+    const unsigned bad = (worst == 2) ? 0x7ff80000u : 0u;      // (nan_or: the NaN of an infeasible instance, as bits)
+    __syncthreads();
+    state_to_lds<NQ, NX>(z, zs, xs, lane);
+    __syncthreads();
+    rows_from_lds<NQ>(q + b0 * NQ, rows_valid, zs, lane);
+    if constexpr (NX > 0) rows_from_lds<NX>(x + b0 * NX, rows_valid, xs, lane);
+    __syncthreads();
+    {
+        double vb[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) vb[j] = nan_or(v[j], bad);
+        state_to_lds<NQ, NX>(vb, zs, xs, lane);
+    }
+    if constexpr (NS > 0) {
+        double* so = slots + LY::O_SL * WAVE;
+        if (slack_out != nullptr) {
+#pragma unroll
+            for (int k = 0; k < NS; ++k) so[lane * NS + k] = nan_or(sl[k], bad);
+        }
+    }
+    __syncthreads();
+    rows_from_lds<NQ>(dq + b0 * NQ, rows_valid, zs, lane);
+    if constexpr (NX > 0) rows_from_lds<NX>(dx + b0 * NX, rows_valid, xs, lane);
+    if constexpr (NS > 0) {
+        if (slack_out != nullptr) rows_from_lds<NS>(slack_out + b0 * NS, rows_valid, slots + LY::O_SL * WAVE, lane);
+    }
+    if (status_out != nullptr && valid) status_out[b0 + lane] = worst;
+}
+
+// ... recording its trajectory / reading one target per tick (RollRec, clik_device.hpp)
+template <const ShapeDesc& SD, bool RK>
+__global__ __launch_bounds__(WAVE) void qp_rollout_static_rec_kernel(
+    const void* __restrict__ img_g, double* __restrict__ q, const double* __restrict__ y,
+    double* __restrict__ dq, double* __restrict__ slack_out, int32_t* __restrict__ status_out, const long long B,
+    const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed,
+    double* __restrict__ x, double* __restrict__ dx, const RollRec rec)
+{
+    qp_rollout_static_body<SD, RK, RollRec>(img_g, q, y, dq, slack_out, status_out, B, tterms, n_ticks, dt, max_speed, x, dx, rec);
+}
+
+// The recording / per-tick-target instantiations of the two rollouts (clik_qp_rollout_batch_rec): in translation units
+// of their own (casclik_amd/jit.py: clik_jit_qp_rollout_rec / clik_jit_qp_value_rollout_rec)
+template <const ShapeDesc& SD>
+inline hipError_t launch_qp_rollout_static_rec(const void* d_img, const double* d_tterms, int n_ticks, double dt,
+                                               double max_speed, long long B, double* q, const double* y, double* dq,
+                                               double* slack, int32_t* status, double* x, double* dx,
+                                               hipStream_t stream, int stages, const RollRec* rec)
+{
+    if (rec == nullptr || (SD.n_x != 0 && (x == nullptr || dx == nullptr))) return hipErrorInvalidValue;
+    const RollRec rr = *rec;
+    const unsigned grid = (unsigned)((B + WAVE - 1) / WAVE);
+    if (stages == 4) {
+        constexpr size_t shmem = QpLayout<SD>::LDS_BYTES + (size_t)2 * SD.n * WAVE * sizeof(double);
+        static_assert(shmem <= kLdsBytesPerCu, "Runge-Kutta QP rollout needs more LDS than a CU has");
+        if (shmem > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void*)qp_rollout_static_rec_kernel<SD, true>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL((qp_rollout_static_rec_kernel<SD, true>), dim3(grid), dim3(WAVE), shmem, stream, d_img, q, y,
+                           dq, slack, status, B, d_tterms, n_ticks, dt, max_speed, x, dx, rr);
+        return hipGetLastError();
+    }
+    constexpr size_t shmem = QpLayout<SD>::LDS_BYTES;
+    if (shmem > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)qp_rollout_static_rec_kernel<SD, false>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((qp_rollout_static_rec_kernel<SD, false>), dim3(grid), dim3(WAVE), shmem, stream, d_img, q, y, dq,
+                       slack, status, B, d_tterms, n_ticks, dt, max_speed, x, dx, rr);
+    return hipGetLastError();
+}
+
+// hipErrorNotSupported outside the box family (the caller then uses the image-reading recording rollout)
+template <const ShapeDesc& SD, class IMGV>
+inline hipError_t launch_qp_rollout_static_values_rec(const double* d_tterms, int n_ticks, double dt, double max_speed,
+                                                      long long B, double* q, const double* y, double* dq, double* slack,
+                                                      int32_t* status, double* x, double* dx, hipStream_t stream,
+                                                      int stages, const RollRec* rec)
+{
+    if constexpr (QpLayout<SD>::BOX) {
+        if (rec == nullptr || (SD.n_x != 0 && (x == nullptr || dx == nullptr))) return hipErrorInvalidValue;
+        const RollRec rr = *rec;
+        const unsigned grid = (unsigned)((B + WAVE - 1) / WAVE);
+        if (stages == 4)
+            hipLaunchKernelGGL((qp_rollout_static_box_values_rec_kernel<SD, IMGV, true>), dim3(grid), dim3(WAVE), 0,
+                               stream, q, y, dq, slack, status, B, d_tterms, n_ticks, dt, max_speed, x, dx, rr);
+        else
+            hipLaunchKernelGGL((qp_rollout_static_box_values_rec_kernel<SD, IMGV, false>), dim3(grid), dim3(WAVE), 0,
+                               stream, q, y, dq, slack, status, B, d_tterms, n_ticks, dt, max_speed, x, dx, rr);
+        return hipGetLastError();
+    } else {
+        return hipErrorNotSupported;
+    }
+}
+
+}  // namespace clik

@@ -354,6 +354,27 @@ int clik_pinv_rollout_batch_m(const clik_pinv* h, int64_t B, int32_t n_ticks, in
                               double* q, double* x, const double* y, double* dq,
                               double* dx, int32_t* mode, void* stream);
 
+/* Trajectory in, trajectory out: clik_pinv_rollout_batch_m with a target per tick and records of the ticks in between.
+ *   y_per_tick != 0: y is [n_ticks][B][n_y] (device) and tick i reads record i - with Runge-Kutta all four stages of
+ *     tick i read record i (zero-order hold); 0: y is [B][n_y], as above.
+ *   record_every = k > 0: with R = n_ticks / k (rounded down), record r = 0 .. R-1 is taken after tick (r+1)*k, counted
+ *     from 1, and holds exactly what a launch ending at that tick returns: rec_q [R][B][n_q] the state, rec_dq [R][B][n_q]
+ *     the clamped velocity applied in that tick (Runge-Kutta: the combined rate), rec_x / rec_dx [R][B][n_x] the same for
+ *     the virtual variables, rec_mode [R][B] the tick's mode (Runge-Kutta: of its first stage).  Ticks after the last
+ *     multiple of k are not recorded; k > n_ticks records nothing.  Every rec_ pointer may be NULL (that array is not
+ *     written); record_every = 0: none is.  All device memory, written with plain stores during the launch.
+ * q / x / dq / dx / mode receive the end of the launch as before.  Needs the shape-specialised RECORDING rollout of the
+ * skill, attached with clik_pinv_attach_rec_kernel (rollout_rec_fn: the image-reading one, needs a shape-specialised
+ * kernel on the handle; value_rollout_rec_fn: the one with the skill's numbers compiled in, may be NULL; both NULL
+ * detaches); a handle without one - one served by the built-in dynamic-shape kernel - gets CLIK_EUNSUPPORTED.   */
+int clik_pinv_attach_rec_kernel(clik_pinv* h, void* rollout_rec_fn, void* value_rollout_rec_fn);
+int clik_pinv_rollout_batch_rec(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method,
+                                double dt, double max_speed, const double* tterms,
+                                double* q, double* x, const double* y, double* dq,
+                                double* dx, int32_t* mode, void* stream,
+                                int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
+                                double* rec_x, double* rec_dx, int32_t* rec_mode);
+
 /* ---- ReactiveQPController path ----------------------------------------- */
 /* replaces setup_problem_functions()+setup_solver() (reactive_qp.py:248-298) */
 int clik_qp_create(const clik_skill_desc* desc, const clik_qp_opts* opts,
@@ -437,6 +458,18 @@ int clik_qp_rollout_batch_x(const clik_qp* h, int64_t B, int32_t n_ticks,
 int clik_qp_rollout_batch_m(const clik_qp* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
                             double max_speed, const double* tterms, double* q, double* x, const double* y,
                             double* dq, double* dx, double* slack, int32_t* status, void* stream);
+/* ... with a target per tick and records (see clik_pinv_rollout_batch_rec for y_per_tick, record_every and the layout
+ * of the records).  rec_status [R][B] is the worst status up to and including the recorded tick - the running meaning
+ * of status; rec_slack [R][B][n_slack] that tick's slack; rec_dq / rec_dx / rec_slack of an instance that has met an
+ * infeasible tick are NaN, as dq / dx / slack of a launch ending there are.  Needs the recording rollout of the skill
+ * (clik_qp_attach_rec_kernel: rollout_rec_fn the image-reading one, value_rollout_rec_fn the value-specialised one of
+ * the bound-constrained family or NULL); CLIK_EUNSUPPORTED without one.                                          */
+int clik_qp_attach_rec_kernel(clik_qp* h, void* rollout_rec_fn, void* value_rollout_rec_fn);
+int clik_qp_rollout_batch_rec(const clik_qp* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
+                              double max_speed, const double* tterms, double* q, double* x, const double* y,
+                              double* dq, double* dx, double* slack, int32_t* status, void* stream,
+                              int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
+                              double* rec_x, double* rec_dx, double* rec_slack, int32_t* rec_status);
 
 /* QP data only (H diag, A, lbA, ubA as the reference's H_func/A_func/Blb/Bub,
  * reactive_qp.py:283-298) for inspection and parity tests:

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Registers / scratch / occupancy of the value-specialised kernels of a BASELINE skill, from the compiler's resource
-remarks (no GPU needed).      python tools/kernel_resources.py [stack|pose|qp] [-DFLAG ...] [--asm=listing.s] [--obj=device.o]"""
+remarks (no GPU needed).      python tools/kernel_resources.py [stack|pose|qp] [-DFLAG ...] [--asm=listing.s] [--obj=device.o]
+--rec: the recording / per-tick-target rollouts of that skill (jit._VALUE_REC_TEMPLATE / _QP_VALUE_REC_TEMPLATE) instead."""
 import os
 import subprocess
 import sys
@@ -37,7 +38,7 @@ if which == "qp":
     copts = _capi.qp_opts_to_c(qc.weight_shifter, state_w, list(qc._slack_var_weights))
     buf = C.create_string_buffer(16384)
     assert lib.clik_qp_shape_describe(C.byref(cdesc), buf, len(buf)) == 1
-    init, template = buf.value.decode(), jit._QP_VALUE_TEMPLATE
+    init, template = buf.value.decode(), jit._QP_VALUE_REC_TEMPLATE if "--rec" in sys.argv else jit._QP_VALUE_TEMPLATE
     words = jit.host_image_words(lib, "qp", cdesc, copts)
 else:
     spec = skills.stack_skill(fk) if which == "stack" else skills.pose_skill(fk)
@@ -46,7 +47,7 @@ else:
     cdesc = _capi.desc_to_c(d)
     copts = _capi.pinv_opts_to_c(cc.PseudoInverseController(skill_spec=spec, options=opts).options)
     ok, init = jit.shape_of(lib, cdesc, copts)
-    template = jit._VALUE_TEMPLATE
+    template = jit._VALUE_REC_TEMPLATE if "--rec" in sys.argv else jit._VALUE_TEMPLATE
     words = jit.host_image_words(lib, "pinv", cdesc, copts)
 # (the scheduling strategy the shipped object is compiled with, casclik_amd/jit.py::sched_strategy - unless one is given)
 sched = jit.sched_strategy(template, init)

@@ -10,6 +10,8 @@ derivative for every tick of the launch on the host (Python) and copies them ove
 host work that a loop which prepares the next launch's terms beside the running one would hide.  The DEVICE time per tick
 is the rollout kernel's duration / ticks: run this script under `rocprofv3 --kernel-trace --stats` (a 256-tick launch lasts a
 millisecond: the profiler's stretch of ~1 us does not matter) - profiles/r6_moe_rollout_kernel_stats.csv.
+The "recorded" column is the same loop with `record_every=5`: one launch per 256 ticks that also returns the curve (a
+sample every fifth tick, what tests/test_gpu_figure_pins.py gets from a launch per five ticks), host-inclusive too.
 """
 import os
 import sys
@@ -71,6 +73,23 @@ def rollout(ctrl, Q, t_start, launches=6):
     return (time.perf_counter() - t) / (launches * TPL) * 1e6, res
 
 
+def recorded(ctrl, Q, t_start, launches=6, every=5):
+    """the same launches, each also returning a record of every `every`-th tick (device tensors, left on the device)"""
+    times = t_start + cf.MOE_DT * np.arange(TPL)
+    q = torch.from_numpy(Q).cuda()
+    kw = dict(dt=cf.MOE_DT, max_speed=figure_skills.MOE_MAX_SPEED, record_every=every)
+    q = ctrl.rollout_batch(times, q, **kw)[0]       # (warm-up launch: instantiates the recording rollout)
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    curve = []
+    for k in range(launches):
+        res = ctrl.rollout_batch(times + (k + 1) * TPL * cf.MOE_DT, q, **kw)
+        q = res[0]
+        curve.append(res[-1]["q"])
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) / (launches * TPL) * 1e6, sum(c.shape[0] for c in curve)
+
+
 print("Moe-2016 skills (ur5_moe2016_example2.ipynb), %d instances around the notebook's start pose; rollouts of %d ticks per launch"
       % (B, TPL))
 for case in cf.MOE_CASES:
@@ -84,11 +103,14 @@ for case in cf.MOE_CASES:
     ctrl.setup_solver()
     Q = cf.MOE_HOME[None, :] + rng.normal(scale=0.03, size=(B, 6))
     us_roll, res = rollout(ctrl, Q, 0.0)
+    us_rec, n_rec = recorded(ctrl, Q, 0.0)
     us_tick = per_tick_launch(ctrl, torch.from_numpy(Q).cuda(), 0.0)
     extra = ""
     if kind == "pinv":
         extra = "modes at the end %s" % np.bincount(res[2].cpu().numpy().astype(int) + 1, minlength=2)[:9]
     else:
         extra = "statuses at the end %s" % np.bincount(res[-1].cpu().numpy().astype(int), minlength=3)
-    print("%-14s kernel %-26s rollout (host-inclusive) %6.2f us per tick   launch per tick %6.2f us   %s"
-          % (case, ctrl.kernel_variant(B) if hasattr(ctrl, "kernel_variant") else ctrl.kernel_name, us_roll, us_tick, extra))
+    print("%-14s kernel %-26s rollout (host-inclusive) %6.2f us per tick   recorded (every 5th tick, %d records) %6.2f us   "
+          "launch per tick %6.2f us   %s"
+          % (case, ctrl.kernel_variant(B) if hasattr(ctrl, "kernel_variant") else ctrl.kernel_name, us_roll, n_rec, us_rec,
+             us_tick, extra))
