@@ -178,6 +178,8 @@ _SYMBOLS = [
     "clik_pinv_create", "clik_pinv_create_host", "clik_pinv_destroy", "clik_pinv_n_modes", "clik_pinv_kernel_name", "clik_pinv_kernel_variant", "clik_pinv_image_words", "clik_pinv_attach_value_kernel", "clik_pinv_attach_resident_kernel", "clik_pinv_resident_waves", "clik_pinv_resident_run", "clik_pinv_resident_run_state", "clik_ticket_feed", "clik_shape_describe", "clik_pinv_attach_kernel",
     "clik_pinv_solve_batch", "clik_pinv_solve_batch_t", "clik_pinv_rollout_batch", "clik_pinv_rollout_batch_x", "clik_pinv_rollout_batch_m",
     "clik_pinv_attach_rec_kernel", "clik_pinv_rollout_batch_rec", "clik_qp_attach_rec_kernel", "clik_qp_rollout_batch_rec",
+    "clik_pinv_attach_time_kernel", "clik_pinv_time_terms", "clik_pinv_rollout_batch_dev",
+    "clik_qp_attach_time_kernel", "clik_qp_time_terms", "clik_qp_rollout_batch_dev",
     "clik_qp_create", "clik_qp_create_host", "clik_qp_destroy", "clik_qp_n_vars", "clik_qp_n_rows", "clik_qp_workspace_bytes",
     "clik_qp_kernel_name", "clik_qp_kernel_variant", "clik_qp_shape_describe", "clik_qp_attach_kernel", "clik_qp_image_words", "clik_qp_attach_value_kernel", "clik_qp_is_box_family",
     "clik_qp_attach_resident_kernel", "clik_qp_resident_waves", "clik_qp_resident_run",
@@ -333,6 +335,17 @@ def load_library(path=None):
     lib.clik_qp_rollout_batch_rec.restype = C.c_int
     lib.clik_qp_rollout_batch_rec.argtypes = lib.clik_qp_rollout_batch_m.argtypes + [C.c_int32, C.c_int32, dp, dp, dp, dp,
                                                                                      dp, ip]
+    # time slots on the device: `times` is a DEVICE pointer where the calls above take the host table `tterms`
+    for name in ("clik_pinv_attach_time_kernel", "clik_qp_attach_time_kernel"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, C.c_void_p]
+    for name in ("clik_pinv_time_terms", "clik_qp_time_terms"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, C.c_int64, dp, C.c_int32, C.c_double, dp, vp]
+    for name, rec in (("clik_pinv_rollout_batch_dev", lib.clik_pinv_rollout_batch_rec),
+                      ("clik_qp_rollout_batch_dev", lib.clik_qp_rollout_batch_rec)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [dp if k == 6 else a for k, a in enumerate(rec.argtypes)]
     lib.clik_qp_n_vars.restype = C.c_int
     lib.clik_qp_n_vars.argtypes = [vp]
     lib.clik_qp_n_rows.restype = C.c_int

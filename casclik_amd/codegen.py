@@ -17,6 +17,10 @@ scalar DAG and its symbolic derivatives (autodiff.py), with common sub-expressio
 shared.  Time-only sub-expressions stay on the host as time slots (``tv``), like in
 the row table.  The kernel templates around it are the hand-written ones; jit.py
 compiles both for the skill.
+
+The time slots themselves have device code too, on request (``emit_time_slots``; the
+controllers' option ``time_on_device``): one straight-line function that fills ``tv``
+from a time, for the kernel of clik_time.hpp.
 """
 from __future__ import annotations
 
@@ -115,6 +119,11 @@ class TaskEmitter(object):
             return self._temp(("fk_d", i, j, s), expr)
         if op == "ori_err":
             raise NotImplementedError("orientation_error inside a non-affine constraint expression")
+        return self._op(node)
+
+    def _op(self, node):
+        """an operation node (no leaf, no kinematics atom): one memoised temporary over its arguments' references"""
+        op = node.op
         args = [self.ref(a) for a in node.args]
         if op in ("sin", "cos"):
             # one evaluation serves both (a Jacobian needs the other one anyway); sincos_joint is the
@@ -224,3 +233,52 @@ class TaskEmitter(object):
                 "        %s\n"
                 "    }\n"
                 "};\n" % (ti, n, len(nodes), body))
+
+
+class _TimeEmitter(TaskEmitter):
+    """Node emission of TaskEmitter for trees over time alone: the time symbol is the one leaf beside constants."""
+
+    def __init__(self, time_family):
+        TaskEmitter.__init__(self, None)
+        self.time_family = time_family
+
+    def _ref(self, node):
+        op = node.op
+        if op == "const":
+            return _lit(node.value)
+        if op == "sym":
+            if node.family is not None and node.family is self.time_family:
+                return "t"
+            raise NotImplementedError("symbol '%s' in a time slot is not the time variable" % node.name)
+        if op in ("fk", "fk_d", "ori_err"):
+            raise NotImplementedError("no device code for operation '%s' in a time slot" % op)
+        return self._op(node)
+
+
+def emit_time_slots(low_or_desc):
+    """C++ source of ``struct TimeSlots`` for a lowered skill (its lowering._Lowerer or its SkillDescriptor): one
+    straight-line function
+
+        TimeSlots::eval(double t, double* tv)
+
+    that writes ``tv[k]``, the value of time slot k, and ``tv[n_tslots + k]``, its time derivative - the layout of
+    ``SkillDescriptor.time_terms`` and of the kernels' TickArgs - with common sub-expressions shared across slots and
+    across values and derivatives.  ``sin`` / ``cos`` go through ``sincos_joint``, which the includer supplies
+    (clik_device.hpp on the device; the text is host C++ as well once ``__device__``, ``__forceinline__`` and
+    ``sincos_joint`` are defined).  A skill without time slots gives an empty body."""
+    desc = getattr(low_or_desc, "desc", low_or_desc)
+    n = desc.n_tslots
+    em = _TimeEmitter(desc.time_family)
+    out = []
+    for k, (val, der) in enumerate(desc.tslots):
+        out.append("tv[%d] = %s;" % (k, em.ref(val)))
+        out.append("tv[%d] = %s;" % (n + k, em.ref(der)))
+    body = "\n        ".join(em.lines + out)
+    return ("struct TimeSlots {\n"
+            "    static constexpr int n_tslots = %d;\n"
+            "    __device__ __forceinline__ static void eval(double t, double* tv)\n"
+            "    {\n"
+            "        (void)t; (void)tv;\n"
+            "        %s\n"
+            "    }\n"
+            "};\n" % (n, body))

@@ -254,6 +254,19 @@ def per_tick_input(input_var, n_ticks, n_y):
     return True
 
 
+def rollout_stage_times(time_vars, dt, method):
+    """The times at which a rollout evaluates its time slots, as the host computes them: ``time_vars`` itself for
+    ``method="euler"``; for ``"rk4"`` tick-major, stage-minor ``t, t + 0.5 * dt, t + 0.5 * dt, t + dt`` - one rounded
+    add each (``0.5 * dt`` is exact), the identity the device's time kernel keeps bit for bit (clik_time.hpp).
+    ValueError for any other method."""
+    if method not in ("euler", "rk4"):
+        raise ValueError("method must be 'euler' or 'rk4'")
+    times = np.asarray(time_vars, dtype=float).reshape(-1)
+    if method == "rk4":
+        return np.stack([times, times + 0.5 * dt, times + 0.5 * dt, times + dt], axis=1).reshape(-1)
+    return times
+
+
 def record_layout(fields, R, B):
     """``{name: (shape, dtype name)}`` of the records of a rollout: ``fields`` is a list of ``(name, width, dtype
     name)``; width 0 leaves the field out, width None makes it ``[R, B]`` (one number per instance), any other
@@ -274,6 +287,8 @@ class BaseController(object):
     other helper here works from."""
     controller_type = "BaseController"
     _create_fn = _destroy_fn = None
+    _time_kind = None           # "pinv" | "qp": whose clik_*_attach_time_kernel / clik_*_time_terms the handle takes
+    _time_kernel = None         # cache tag of the attached time kernel (options["time_on_device"]), or None
 
     def __repr__(self):
         return self.controller_type + "<" + self.skill_spec.label + ">"
@@ -312,6 +327,7 @@ class BaseController(object):
         self._handle = handle
         self._setup_c = (cdesc, copts)      # (the recording rollouts are instantiated later, at their first use)
         self._rec_kernel = None
+        self._time_kernel = None
         return cdesc, copts
 
     def _want_jit(self):
@@ -343,6 +359,61 @@ class BaseController(object):
                 "kernel could be instantiated for it (jit disabled, hipcc missing, or the skill is "
                 "outside the shape-specialised family)" % ", ".join(
                     repr(d.tasks[k]["label"]) for k in sorted(d.extern_code)))
+
+    # -- time slots on the device -------------------------------------------------------------------------------
+    def _setup_time_kernel(self):
+        """``options["time_on_device"]`` (default False), read at set-up: the skill's time slots as generated device
+        code (codegen.emit_time_slots) in a kernel of their own, attached to the handle.  Rollouts and per-instance-time
+        ticks then fill their time-term tables on the device from the times (``time_terms_batch``) instead of walking
+        the slot trees on the host once per time stamp.  A skill without time slots builds nothing and behaves as
+        without the option.  NotImplementedError when the kernel cannot be had (no compiler and nothing cached,
+        ``function_opts["jit"]`` false): there is no silent return to the host path."""
+        self._time_kernel = None
+        if not self.options.get("time_on_device", False) or self.descriptor.n_tslots == 0:
+            return
+        tag = None
+        if self._want_jit():
+            from .. import jit
+            tag = self._attach_or_warn(
+                lambda: jit.attach_time(self._lib, self._handle, self.descriptor, self._time_kind),
+                "the time kernel could not be built", 400)
+        if not tag:
+            raise NotImplementedError(
+                "options['time_on_device'] is set, but no time kernel could be instantiated for the skill's %d time "
+                "slot(s) (jit disabled, or hipcc missing and nothing cached)" % self.descriptor.n_tslots)
+        self._time_kernel = tag
+
+    def _device_times(self, time_vars):
+        """times as a flat contiguous float64 tensor on the controller's device (one that already is, is used in
+        place: no host synchronisation) and whether they came as a tensor"""
+        torch = _torch()
+        if isinstance(time_vars, torch.Tensor):
+            return time_vars.to(device=self._device, dtype=torch.float64).reshape(-1).contiguous(), True
+        arr = np.ascontiguousarray(np.asarray(time_vars, dtype=np.float64).reshape(-1))
+        return torch.from_numpy(arr).to(self._device), False
+
+    def time_terms_batch(self, times, dt=0.0, method="euler"):
+        """The time terms of the skill at ``times`` (N of them), computed on the device: ``[N * stages, 2 * n_tslots]``,
+        row ``i * stages + s`` what ``descriptor.time_terms`` gives at the time of stage s of tick i - ``stages`` is 1
+        for ``method="euler"`` (the time itself) and 4 for ``"rk4"`` (t, t + dt/2, t + dt/2, t + dt).  A device tensor
+        when ``times`` is a tensor, numpy otherwise.  Needs ``options["time_on_device"]`` (NotImplementedError
+        otherwise).  A row of a non-finite time holds whatever the arithmetic gives."""
+        if method not in ("euler", "rk4"):
+            raise ValueError("method must be 'euler' or 'rk4'")
+        if not self.options.get("time_on_device", False):
+            raise NotImplementedError("time_terms_batch needs options['time_on_device'] = True at set-up")
+        self._require_handle()
+        torch = _torch()
+        dev, n_ts = self._device, self.descriptor.n_tslots
+        stages = 4 if method == "rk4" else 1
+        T, was_tensor = self._device_times(times)
+        out = torch.empty((T.numel() * stages, 2 * n_ts), dtype=torch.float64, device=dev)
+        if n_ts and T.numel():
+            with torch.cuda.device(dev):
+                rc = getattr(self._lib, "clik_%s_time_terms" % self._time_kind)(
+                    self._handle, T.numel(), ptr(T), stages, float(dt), ptr(out), current_stream(dev))
+            _capi.check(self._lib, rc)
+        return out if was_tensor else out.cpu().numpy()
 
     # -- batches in and out -------------------------------------------------------------------------------------
     def _batch_inputs(self, robot_var, virtual_var=None, input_var=None, clone=False):
@@ -380,6 +451,18 @@ class BaseController(object):
         per distinct stamp and travel as the device tensor ``T [B, 2 * n_tslots]`` of the ``*_solve_batch_t`` entry
         points; ``stamps = (uniq, inverse)`` serves ``_solve_per_stamp``.  A skill without time slots gives the same
         tick at every stamp: ``(first stamp, None, None)``, the ordinary launch."""
+        if self._time_kernel is not None and self.kernel_name not in ("dynamic", "none"):
+            # time_on_device: T from the time kernel, in the instances' order - no sorting of the stamps, no tree-walk,
+            # and a device tensor of times is read in place.  (A skill on the dynamic fallback kernel keeps the host
+            # path below: `_solve_per_stamp` groups by stamp on the host and has no per-instance-time variant.)
+            is_tensor = isinstance(time_var, _torch().Tensor)
+            n = time_var.numel() if is_tensor else np.size(time_var)
+            if is_tensor and n == 1:
+                return float(time_var.reshape(-1)[0]), None, None
+            if n > 1 and (is_tensor or np.ndim(time_var) > 0):
+                if n != B:
+                    raise ValueError("time_var has %d entries, the batch %d instances" % (n, B))
+                return 0.0, self.time_terms_batch(self._device_times(time_var)[0]), None
         if not (np.ndim(time_var) > 0 and np.size(time_var) > 1):
             return (float(np.asarray(time_var).reshape(-1)[0]) if np.ndim(time_var) > 0 else time_var), None, None
         d = self.descriptor
@@ -412,15 +495,19 @@ class BaseController(object):
         """``(n_ticks, stages, tterms)`` of a rollout: ``stages`` is 1 for ``method="rk4"`` (the right-hand side at t,
         t + dt/2, t + dt/2, t + dt of every tick), 0 for ``"euler"`` (at t); ``tterms`` the ``_capi.tterms_arg`` pair
         of the time terms of all stage times, one after the other."""
+        d = self.descriptor
+        stage_times = rollout_stage_times(time_vars, dt, method)
+        tt = np.concatenate([d.time_terms(t) for t in stage_times]) if d.n_tslots else np.zeros(0)
+        return int(np.size(time_vars)), 1 if method == "rk4" else 0, _capi.tterms_arg(tt)
+
+    def _rollout_times_dev(self, time_vars, method):
+        """``(n_ticks, stages, T)`` of a rollout with ``time_on_device``: ``T`` the tick times as a device tensor, from
+        which ``clik_*_rollout_batch_dev`` fills the time terms of all stage times itself (a tensor on the controller's
+        device is used in place); ``stages`` as ``_rollout_times``."""
         if method not in ("euler", "rk4"):
             raise ValueError("method must be 'euler' or 'rk4'")
-        d = self.descriptor
-        times = np.asarray(time_vars, dtype=float).reshape(-1)
-        stage_times = times
-        if method == "rk4":
-            stage_times = np.stack([times, times + 0.5 * dt, times + 0.5 * dt, times + dt], axis=1).reshape(-1)
-        tt = np.concatenate([d.time_terms(t) for t in stage_times]) if d.n_tslots else np.zeros(0)
-        return int(times.size), 1 if method == "rk4" else 0, _capi.tterms_arg(tt)
+        T = self._device_times(time_vars)[0]
+        return int(T.numel()), 1 if method == "rk4" else 0, T
 
     def _rollout_io(self, robot_var, virtual_var, input_var, n_ticks, record_every, record_out, fields):
         """The marshalling of a rollout: ``(Q, X, Y, B, was_np, y_per_tick, rec)``.  ``Q`` / ``X`` are copies the

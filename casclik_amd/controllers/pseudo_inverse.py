@@ -33,8 +33,11 @@ class PseudoInverseController(BaseController):
     options_info = """feedforward (bool, True), multidim_sets (bool, False),
     converge_final_set_to_max (bool, False), pinv_method ("damped"|"standard"),
     damping_factor (float, 1e-7), function_opts (dict, accepted and ignored:
-    there is no CasADi JIT on this path), device (torch device, optional)"""
+    there is no CasADi JIT on this path), device (torch device, optional), time_on_device (bool, False: evaluate the
+    skill's time slots with a generated device kernel - rollouts and per-instance-time ticks then take their times
+    from the device, see ``time_terms_batch``)"""
     _create_fn, _destroy_fn = "clik_pinv_create", "clik_pinv_destroy"
+    _time_kind = "pinv"
 
     def __init__(self, skill_spec, options=None):
         self._handle = None
@@ -214,6 +217,7 @@ class PseudoInverseController(BaseController):
                 "shape-specialised kernel could be instantiated for it (jit disabled, hipcc missing, or the "
                 "skill is outside the shape-specialised family)" % DYN_MAX_M)
         self._require_generated_code_kernel()
+        self._setup_time_kernel()
 
     def _c_options(self):
         return _capi.pinv_opts_to_c(self.options)
@@ -250,7 +254,10 @@ class PseudoInverseController(BaseController):
         in place).  ``time_var``: one time stamp for the batch, or an array with one per
         instance (robots at different phases of a trajectory): ONE launch of the per-instance-time kernel
         (clik_pinv_solve_batch_t); a skill served by the dynamic fallback kernel has no such variant, its batch is
-        grouped by distinct time stamps, one launch per group.  Returns (robot_vel [B,n_q], virtual_vel | None,
+        grouped by distinct time stamps, one launch per group.  With ``options["time_on_device"]`` the per-instance
+        time terms come from the time kernel (``time_terms_batch``) and ``time_var`` may be a device tensor, read in
+        place; a skill on the dynamic fallback kernel keeps the host evaluation, and so does one stamp for the whole
+        batch (its time terms travel by value with the launch).  Returns (robot_vel [B,n_q], virtual_vel | None,
         mode [B]) in the container type of ``robot_var``.  The launch is asynchronous on
         torch's current stream when tensors are passed."""
         self._require_handle()
@@ -272,7 +279,7 @@ class PseudoInverseController(BaseController):
                 rc = self._lib.clik_pinv_solve_batch(
                     self._handle, B, ttp, ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX),
                     ptr(mode), current_stream(dev))
-        if T is not None and rc == _capi.CLIK_EUNSUPPORTED:
+        if T is not None and stamps is not None and rc == _capi.CLIK_EUNSUPPORTED:
             self._solve_per_stamp(
                 stamps, lambda tv, Qk, Xk, Yk: self.solve_batch(tv, Qk, virtual_var=Xk, input_var=Yk,
                                                                 return_mode=return_mode),
@@ -409,12 +416,21 @@ class PseudoInverseController(BaseController):
         stages of the tick).  Trajectory out: ``record_every=k`` appends one last element to the result, a dict of
         ``[n_ticks // k, B, .]`` arrays ``q``, ``dq`` (``x``, ``dx`` with virtual variables) and ``mode [R, B]``: entry
         r is what a launch ending at tick ``(r + 1) * k`` returns.  ``record_out``: preallocated device tensors for
-        some of them.  Both need a kernel instantiated for the skill (NotImplementedError otherwise)."""
+        some of them.  Both need a kernel instantiated for the skill (NotImplementedError otherwise).
+
+        With ``options["time_on_device"]`` the launch goes through ``clik_pinv_rollout_batch_dev``: the time terms of
+        all ticks and stages are computed on the device from ``time_vars``, which may be a tensor on the controller's
+        device (used in place, no host synchronisation)."""
         self._require_handle()
         torch = _torch()
         d = self.descriptor
         dev = self._device
-        n_ticks, stages, (tt, ttp) = self._rollout_times(time_vars, dt, method)
+        dev_times = self._time_kernel is not None
+        if dev_times:
+            n_ticks, stages, tt = self._rollout_times_dev(time_vars, method)
+            ttp = ptr(tt)
+        else:
+            n_ticks, stages, (tt, ttp) = self._rollout_times(time_vars, dt, method)
         Q, X, Y, B, was_np, y_per_tick, rec = self._rollout_io(
             robot_var, virtual_var, input_var, n_ticks, record_every, record_out,
             [("q", d.n_q, "float64"), ("dq", d.n_q, "float64"), ("x", d.n_x, "float64"), ("dx", d.n_x, "float64"),
@@ -426,7 +442,8 @@ class PseudoInverseController(BaseController):
                 ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX), ptr(mode), current_stream(dev))
         if rec is None and not y_per_tick:
             with torch.cuda.device(dev):
-                rc = self._lib.clik_pinv_rollout_batch_m(*args)
+                rc = self._lib.clik_pinv_rollout_batch_dev(*args, 0, 0, None, None, None, None, None) if dev_times \
+                    else self._lib.clik_pinv_rollout_batch_m(*args)
         else:
             from .. import jit
             cdesc, copts = self._setup_c
@@ -434,7 +451,7 @@ class PseudoInverseController(BaseController):
                                                             extern=d.extern_source(), values=bool(self.value_kernel)))
             r = rec or {}
             with torch.cuda.device(dev):
-                rc = self._lib.clik_pinv_rollout_batch_rec(
+                rc = (self._lib.clik_pinv_rollout_batch_dev if dev_times else self._lib.clik_pinv_rollout_batch_rec)(
                     *args, y_per_tick, int(record_every or 0), ptr(r.get("q")), ptr(r.get("dq")), ptr(r.get("x")),
                     ptr(r.get("dx")), ptr(r.get("mode")))
         _capi.check(self._lib, rc)

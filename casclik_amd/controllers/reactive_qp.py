@@ -61,9 +61,12 @@ class ReactiveQPController(BaseController):
     controller_type = "ReactiveQPController"
     options_info = """solver_name / solver_opts / initial_solver_opts: accepted as the reference accepts them (the solver
     here is the device active set, clik_qp_static.hpp); function_opts: `jit` (instantiate a kernel for the skill's
-    structure, default True), `jit_values` (compile the skill's numbers in), `device`."""
+    structure, default True), `jit_values` (compile the skill's numbers in), `device`; time_on_device (bool, False):
+    evaluate the skill's time slots with a generated device kernel - rollouts and per-instance-time ticks then take
+    their times from the device, see ``time_terms_batch``."""
     weight_shifter = 0.001   # mu of the eTaSL paper (reactive_qp.py:44)
     _create_fn, _destroy_fn = "clik_qp_create", "clik_qp_destroy"
+    _time_kind = "qp"
 
     def __init__(self, skill_spec, robot_var_weights=None,
                  virtual_var_weights=None, slack_var_weights=None, options=None):
@@ -183,6 +186,7 @@ class ReactiveQPController(BaseController):
             self.value_kernel = self._attach_or_warn(
                 lambda: jit.attach_qp_values(self._lib, handle, cdesc, extern=d.extern_source()),
                 "value-specialised QP kernel could not be built, using the image-reading one", 300)
+        self._setup_time_kernel()
 
     def _c_options(self):
         d = self.descriptor
@@ -548,7 +552,10 @@ class ReactiveQPController(BaseController):
         with or without it.
 
         ``time_var`` may hold one time per instance (robots at different phases of their
-        trajectories): one launch of the per-instance-time kernel (clik_qp_solve_batch_t)."""
+        trajectories): one launch of the per-instance-time kernel (clik_qp_solve_batch_t).  With
+        ``options["time_on_device"]`` the per-instance time terms come from the time kernel (``time_terms_batch``) and
+        ``time_var`` may be a device tensor, read in place; a skill on the dynamic fallback kernel keeps the host
+        evaluation, and so does one stamp for the whole batch (its time terms travel by value with the launch)."""
         self._require_handle()
         torch = _torch()
         d = self.descriptor
@@ -573,7 +580,7 @@ class ReactiveQPController(BaseController):
                 rc = self._lib.clik_qp_solve_batch_hot(
                     self._handle, B, ttp, ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX),
                     ptr(SL), ptr(status), ptr(hot_set), hot_flag, current_stream(dev))
-        if T is not None and rc == _capi.CLIK_EUNSUPPORTED:
+        if T is not None and stamps is not None and rc == _capi.CLIK_EUNSUPPORTED:
             # (a skill on the dynamic fallback kernel: one launch per distinct time stamp; each group's working sets
             # travel through its own rows of hot_set)
             def one_stamp(tv, Qk, Xk, Yk, hs):
@@ -600,12 +607,21 @@ class ReactiveQPController(BaseController):
         ``[n_ticks // k, B, .]`` arrays ``q``, ``dq`` (``x``, ``dx`` with virtual variables; ``slack`` when the skill has
         slack) and ``status [R, B]``, the worst status up to and including that tick: entry r is what a launch ending
         at tick ``(r + 1) * k`` returns.  ``record_out``: preallocated device tensors for some of them.  Both need a
-        kernel instantiated for the skill (NotImplementedError otherwise)."""
+        kernel instantiated for the skill (NotImplementedError otherwise).
+
+        With ``options["time_on_device"]`` the launch goes through ``clik_qp_rollout_batch_dev``: the time terms of all
+        ticks and stages are computed on the device from ``time_vars``, which may be a tensor on the controller's
+        device (used in place, no host synchronisation)."""
         self._require_handle()
         torch = _torch()
         d = self.descriptor
         dev = self._device
-        n_ticks, stages, (tt, ttp) = self._rollout_times(time_vars, dt, method)
+        dev_times = self._time_kernel is not None
+        if dev_times:
+            n_ticks, stages, tt = self._rollout_times_dev(time_vars, method)
+            ttp = ptr(tt)
+        else:
+            n_ticks, stages, (tt, ttp) = self._rollout_times(time_vars, dt, method)
         Q, X, Y, B, was_np, y_per_tick, rec = self._rollout_io(
             robot_var, virtual_var, input_var, n_ticks, record_every, record_out,
             [("q", d.n_q, "float64"), ("dq", d.n_q, "float64"), ("x", d.n_x, "float64"), ("dx", d.n_x, "float64"),
@@ -618,14 +634,15 @@ class ReactiveQPController(BaseController):
                 ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX), ptr(SL), ptr(status), current_stream(dev))
         if rec is None and not y_per_tick:
             with torch.cuda.device(dev):
-                rc = self._lib.clik_qp_rollout_batch_m(*args)
+                rc = self._lib.clik_qp_rollout_batch_dev(*args, 0, 0, None, None, None, None, None, None) if dev_times \
+                    else self._lib.clik_qp_rollout_batch_m(*args)
         else:
             from .. import jit
             self._require_rec_kernel(lambda: jit.attach_qp_rec(self._lib, self._handle, self._setup_c[0],
                                                                extern=d.extern_source(), values=bool(self.value_kernel)))
             r = rec or {}
             with torch.cuda.device(dev):
-                rc = self._lib.clik_qp_rollout_batch_rec(
+                rc = (self._lib.clik_qp_rollout_batch_dev if dev_times else self._lib.clik_qp_rollout_batch_rec)(
                     *args, y_per_tick, int(record_every or 0), ptr(r.get("q")), ptr(r.get("dq")), ptr(r.get("x")),
                     ptr(r.get("dx")), ptr(r.get("slack")), ptr(r.get("status")))
         _capi.check(self._lib, rc)

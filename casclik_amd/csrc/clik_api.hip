@@ -71,6 +71,9 @@ typedef hipError_t (*clik_jit_solve_fn)(const clik::LaunchArgs*, const TickArgs*
 typedef hipError_t (*clik_jit_rollout_fn)(const clik::LaunchArgs*, const double*, int, double, double, long long,
                                           double*, const double*, double*, int32_t*, hipStream_t);
 
+// clik_jit_time_terms (casclik_amd/jit.py, clik_time.hpp): times [n] (device) -> time-slot records [n * stages][2 * n_tslots]
+typedef hipError_t (*clik_time_fn)(const double*, long long, int, double, double*, hipStream_t);
+
 typedef hipError_t (*clik_jit_value_fn)(const clik::LaunchArgs*, const TickArgs*, long long, const double*,
                                         const double*, double*, int32_t*, hipStream_t);
 
@@ -95,6 +98,8 @@ struct clik_pinv {
     // the recording / per-tick-target rollouts (clik_pinv_attach_rec_kernel): image-reading and value-specialised
     clik_jit_rollout_fn rec_rollout = nullptr;
     clik_jit_rollout_fn val_rec_rollout = nullptr;
+    // the skill's time slots as device code (clik_pinv_attach_time_kernel)
+    clik_time_fn time_fn = nullptr;
 };
 
 // clik_jit_qp_rollout_rec / clik_jit_qp_value_rollout_rec: the rollouts' arguments and the RollRec
@@ -120,6 +125,7 @@ struct clik_qp {
     // the recording / per-tick-target rollouts (clik_qp_attach_rec_kernel): image-reading and value-specialised (box)
     clik_qp_rec_fn rec_rollout = nullptr;
     clik_qp_value_rec_fn val_rec_rollout = nullptr;
+    clik_time_fn time_fn = nullptr;          // the skill's time slots as device code (clik_qp_attach_time_kernel)
     char      jit_name[64];
     // work area of the global-workspace kernels (clik_workspace.hpp): belongs to this handle, released by clik_qp_destroy
     clik::GwsOwner* gws;
@@ -1079,7 +1085,9 @@ extern "C" int clik_pinv_solve_batch_t(const clik_pinv* h, int64_t B, const doub
 // that slot, so nothing depends on how the runtime treats a pageable source and the call never waits for the
 // stream.  A slot is reused once the event recorded behind its copy has completed.  (A rollout with time slots is
 // therefore not graph-capturable - its records are consumed at call time; a skill without time slots stages
-// nothing and captures like a tick.)
+// nothing and captures like a tick.  The clik_*_rollout_batch_dev calls consume nothing on the host at call time and use
+// no pinned slot: their tick times are a device array and the time kernel fills the records on the stream, see
+// rollout_tterms.)
 namespace {
 struct StageSlot { void* host = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool busy = false; int dev = -1; };
 std::mutex g_stage_mu;
@@ -1132,6 +1140,68 @@ static int stage_tterms(const double* tterms, size_t count, hipStream_t stream, 
     return CLIK_OK;
 }
 
+// Where the time-slot records of a rollout come from: a host table (`host`, staged as above) or - `on_device` - the tick
+// times as a device array, from which the handle's time kernel fills the records in stream order.
+struct TtSource {
+    const double* host;
+    const double* times;
+    clik_time_fn time_fn;
+    bool on_device;
+};
+static TtSource tt_host(const double* tterms) { return TtSource{tterms, nullptr, nullptr, false}; }
+static TtSource tt_device(const double* times, clik_time_fn fn) { return TtSource{nullptr, times, fn, true}; }
+
+// the stream-ordered record buffer of one rollout call (*out; null when the skill has no time slots), filled from `src`
+static int rollout_tterms(const TtSource& src, int n_tslots, int n_ticks, int stages, double dt, hipStream_t stream,
+                          double** out)
+{
+    const size_t count = (size_t)n_ticks * stages * 2 * (size_t)n_tslots;
+    if (!src.on_device) return stage_tterms(src.host, count, stream, out);
+    *out = nullptr;
+    if (count == 0) return CLIK_OK;
+    if (!src.times) return fail(CLIK_EINVAL, "times (device, [n_ticks]) required: the skill has time slots");
+    if (!src.time_fn)
+        return fail(CLIK_EUNSUPPORTED, "no time kernel attached for this skill (clik_*_attach_time_kernel)");
+    hipError_t e = hipMallocAsync((void**)out, count * sizeof(double), stream);
+    if (e != hipSuccess) { *out = nullptr; return hipfail(e, "hipMallocAsync(tterms)"); }
+    e = src.time_fn(src.times, (long long)n_ticks, stages, dt, *out, stream);
+    if (e != hipSuccess) {
+        (void)hipFreeAsync(*out, stream);
+        *out = nullptr;
+        return hipfail(e, "time kernel launch");
+    }
+    return CLIK_OK;
+}
+
+// what clik_*_time_terms check before they launch
+static int time_terms_common(clik_time_fn fn, int n_tslots, int64_t n_times, const double* times, int32_t stages, double dt,
+                             double* out, void* stream)
+{
+    if (n_times < 0) return fail(CLIK_EINVAL, "negative size");
+    if (stages != 1 && stages != 4) return fail(CLIK_EINVAL, "stages must be 1 or 4, got %d", stages);
+    if (n_tslots == 0 || n_times == 0) return CLIK_OK;
+    if (!fn) return fail(CLIK_EUNSUPPORTED, "no time kernel attached for this skill (clik_*_attach_time_kernel)");
+    if (!times || !out) return fail(CLIK_EINVAL, "times and out must be device pointers");
+    const hipError_t e = fn(times, (long long)n_times, stages, dt, out, (hipStream_t)stream);
+    if (e != hipSuccess) return hipfail(e, "time kernel launch");
+    return CLIK_OK;
+}
+
+extern "C" int clik_pinv_attach_time_kernel(clik_pinv* h, void* time_terms_fn)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    h->time_fn = (clik_time_fn)time_terms_fn;
+    return CLIK_OK;
+}
+
+extern "C" int clik_pinv_time_terms(const clik_pinv* h, int64_t n_times, const double* times, int32_t stages, double dt,
+                                    double* out, void* stream)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    CLIK_NEEDS_DEVICE_HANDLE(h);
+    return time_terms_common(h->time_fn, h->host.d.n_tslots, n_times, times, stages, dt, out, stream);
+}
+
 extern "C" int clik_pinv_rollout_batch(const clik_pinv* hc, int64_t B, int32_t n_ticks, double dt,
                                        double max_speed, const double* tterms, double* q, const double* y,
                                        double* dq, int32_t* mode, void* stream)
@@ -1164,14 +1234,14 @@ static int roll_rec_of(int64_t B, int n_y, int32_t y_per_tick, int32_t record_ev
 }
 
 static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
-                               double max_speed, const double* tterms, double* q, double* x, const double* y,
+                               double max_speed, const TtSource& tts, double* q, double* x, const double* y,
                                double* dq, double* dx, int32_t* mode, void* stream, const clik::RollRec* rec);
 
 extern "C" int clik_pinv_rollout_batch_m(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
                                          double max_speed, const double* tterms, double* q, double* x,
                                          const double* y, double* dq, double* dx, int32_t* mode, void* stream)
 {
-    return pinv_rollout_common(h, B, n_ticks, method, dt, max_speed, tterms, q, x, y, dq, dx, mode, stream, nullptr);
+    return pinv_rollout_common(h, B, n_ticks, method, dt, max_speed, tt_host(tterms), q, x, y, dq, dx, mode, stream, nullptr);
 }
 
 extern "C" int clik_pinv_rollout_batch_rec(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
@@ -1184,7 +1254,24 @@ extern "C" int clik_pinv_rollout_batch_rec(const clik_pinv* h, int64_t B, int32_
     clik::RollRec rr;
     int rc = roll_rec_of(B, h->host.d.n_y, y_per_tick, record_every, rec_q, rec_dq, rec_x, rec_dx, nullptr, rec_mode, &rr);
     if (rc) return rc;
-    return pinv_rollout_common(h, B, n_ticks, method, dt, max_speed, tterms, q, x, y, dq, dx, mode, stream, &rr);
+    return pinv_rollout_common(h, B, n_ticks, method, dt, max_speed, tt_host(tterms), q, x, y, dq, dx, mode, stream, &rr);
+}
+
+extern "C" int clik_pinv_rollout_batch_dev(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
+                                           double max_speed, const double* times, double* q, double* x,
+                                           const double* y, double* dq, double* dx, int32_t* mode, void* stream,
+                                           int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
+                                           double* rec_x, double* rec_dx, int32_t* rec_mode)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    const TtSource tts = tt_device(times, h->time_fn);
+    // (no records and no per-tick targets: the plain rollout kernels, as clik_pinv_rollout_batch_m)
+    if (record_every == 0 && y_per_tick == 0)
+        return pinv_rollout_common(h, B, n_ticks, method, dt, max_speed, tts, q, x, y, dq, dx, mode, stream, nullptr);
+    clik::RollRec rr;
+    int rc = roll_rec_of(B, h->host.d.n_y, y_per_tick, record_every, rec_q, rec_dq, rec_x, rec_dx, nullptr, rec_mode, &rr);
+    if (rc) return rc;
+    return pinv_rollout_common(h, B, n_ticks, method, dt, max_speed, tts, q, x, y, dq, dx, mode, stream, &rr);
 }
 
 extern "C" int clik_pinv_attach_rec_kernel(clik_pinv* h, void* rollout_rec_fn, void* value_rollout_rec_fn)
@@ -1200,7 +1287,7 @@ extern "C" int clik_pinv_attach_rec_kernel(clik_pinv* h, void* rollout_rec_fn, v
 }
 
 static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
-                               double max_speed, const double* tterms, double* q, double* x, const double* y,
+                               double max_speed, const TtSource& tts, double* q, double* x, const double* y,
                                double* dq, double* dx, int32_t* mode, void* stream, const clik::RollRec* rec)
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
@@ -1228,7 +1315,7 @@ static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, i
                                        "attached for this skill: clik_pinv_attach_rec_kernel)");
     const int stages = method == CLIK_INTEGRATE_RK4 ? 4 : 1;
     double* d_tt = nullptr;
-    int rc = stage_tterms(tterms, (size_t)n_ticks * stages * 2 * (size_t)S.d.n_tslots, (hipStream_t)stream, &d_tt);
+    int rc = rollout_tterms(tts, S.d.n_tslots, n_ticks, stages, dt, (hipStream_t)stream, &d_tt);
     if (rc) return rc;
     const clik::LaunchArgs la = {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->policy, x, dx, stages, nullptr,
                                  rec};
@@ -1444,7 +1531,7 @@ extern "C" int clik_qp_rollout_batch_x(const clik_qp* hc, int64_t B, int32_t n_t
 }
 
 static int qp_rollout_common(const clik_qp* hc, int64_t B, int32_t n_ticks, int32_t method, double dt,
-                             double max_speed, const double* tterms, double* q, double* x, const double* y,
+                             double max_speed, const TtSource& tts, double* q, double* x, const double* y,
                              double* dq, double* dx, double* slack, int32_t* status, void* stream,
                              const clik::RollRec* rec);
 
@@ -1452,7 +1539,8 @@ extern "C" int clik_qp_rollout_batch_m(const clik_qp* hc, int64_t B, int32_t n_t
                                        double max_speed, const double* tterms, double* q, double* x, const double* y,
                                        double* dq, double* dx, double* slack, int32_t* status, void* stream)
 {
-    return qp_rollout_common(hc, B, n_ticks, method, dt, max_speed, tterms, q, x, y, dq, dx, slack, status, stream, nullptr);
+    return qp_rollout_common(hc, B, n_ticks, method, dt, max_speed, tt_host(tterms), q, x, y, dq, dx, slack, status, stream,
+                             nullptr);
 }
 
 extern "C" int clik_qp_rollout_batch_rec(const clik_qp* hc, int64_t B, int32_t n_ticks, int32_t method, double dt,
@@ -1466,7 +1554,40 @@ extern "C" int clik_qp_rollout_batch_rec(const clik_qp* hc, int64_t B, int32_t n
     int rc = roll_rec_of(B, hc->host.d.n_y, y_per_tick, record_every, rec_q, rec_dq, rec_x, rec_dx, rec_slack, rec_status,
                          &rr);
     if (rc) return rc;
-    return qp_rollout_common(hc, B, n_ticks, method, dt, max_speed, tterms, q, x, y, dq, dx, slack, status, stream, &rr);
+    return qp_rollout_common(hc, B, n_ticks, method, dt, max_speed, tt_host(tterms), q, x, y, dq, dx, slack, status, stream,
+                             &rr);
+}
+
+extern "C" int clik_qp_attach_time_kernel(clik_qp* h, void* time_terms_fn)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    h->time_fn = (clik_time_fn)time_terms_fn;
+    return CLIK_OK;
+}
+
+extern "C" int clik_qp_time_terms(const clik_qp* h, int64_t n_times, const double* times, int32_t stages, double dt,
+                                  double* out, void* stream)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    CLIK_NEEDS_DEVICE_HANDLE(h);
+    return time_terms_common(h->time_fn, h->host.d.n_tslots, n_times, times, stages, dt, out, stream);
+}
+
+extern "C" int clik_qp_rollout_batch_dev(const clik_qp* hc, int64_t B, int32_t n_ticks, int32_t method, double dt,
+                                         double max_speed, const double* times, double* q, double* x, const double* y,
+                                         double* dq, double* dx, double* slack, int32_t* status, void* stream,
+                                         int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
+                                         double* rec_x, double* rec_dx, double* rec_slack, int32_t* rec_status)
+{
+    if (!hc) return fail(CLIK_EINVAL, "null handle");
+    const TtSource tts = tt_device(times, hc->time_fn);
+    if (record_every == 0 && y_per_tick == 0)
+        return qp_rollout_common(hc, B, n_ticks, method, dt, max_speed, tts, q, x, y, dq, dx, slack, status, stream, nullptr);
+    clik::RollRec rr;
+    int rc = roll_rec_of(B, hc->host.d.n_y, y_per_tick, record_every, rec_q, rec_dq, rec_x, rec_dx, rec_slack, rec_status,
+                         &rr);
+    if (rc) return rc;
+    return qp_rollout_common(hc, B, n_ticks, method, dt, max_speed, tts, q, x, y, dq, dx, slack, status, stream, &rr);
 }
 
 extern "C" int clik_qp_attach_rec_kernel(clik_qp* h, void* rollout_rec_fn, void* value_rollout_rec_fn)
@@ -1486,7 +1607,7 @@ extern "C" int clik_qp_attach_rec_kernel(clik_qp* h, void* rollout_rec_fn, void*
 }
 
 static int qp_rollout_common(const clik_qp* hc, int64_t B, int32_t n_ticks, int32_t method, double dt,
-                             double max_speed, const double* tterms, double* q, double* x, const double* y,
+                             double max_speed, const TtSource& tts, double* q, double* x, const double* y,
                              double* dq, double* dx, double* slack, int32_t* status, void* stream,
                              const clik::RollRec* rec)
 {
@@ -1510,7 +1631,7 @@ static int qp_rollout_common(const clik_qp* hc, int64_t B, int32_t n_ticks, int3
         return fail(CLIK_EUNSUPPORTED, "records and per-tick targets need a shape-specialised recording rollout (none "
                                        "attached for this skill: clik_qp_attach_rec_kernel)");
     double* d_tt = nullptr;
-    int rc = stage_tterms(tterms, (size_t)n_ticks * stages * 2 * (size_t)S.d.n_tslots, (hipStream_t)stream, &d_tt);
+    int rc = rollout_tterms(tts, S.d.n_tslots, n_ticks, stages, dt, (hipStream_t)stream, &d_tt);
     if (rc) return rc;
     if (rec) {
         hipError_t er = (k == clik::QpKernel::value && h->val_rec_rollout)

@@ -32,6 +32,10 @@
  *     Consequence: a tick is graph-capturable; a rollout is graph-capturable only
  *     for a skill without time slots (n_tslots == 0: nothing is staged) - the
  *     time-slot records of a rollout are consumed at call time, not at replay.
+ *     The clik_*_rollout_batch_dev calls are the exception: they take the tick
+ *     times as a DEVICE array and fill the time-slot records with the skill's
+ *     time kernel (clik_*_attach_time_kernel) on the caller's stream, so they
+ *     consume nothing on the host at call time and use no pinned slot.
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream) so this
  *     header needs no HIP include.
  */
@@ -375,6 +379,31 @@ int clik_pinv_rollout_batch_rec(const clik_pinv* h, int64_t B, int32_t n_ticks, 
                                 int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
                                 double* rec_x, double* rec_dx, int32_t* rec_mode);
 
+/* Time slots on the device.  The skill's time-only sub-expressions as generated device code (casclik_amd/codegen.py,
+ * emit_time_slots), instantiated in a translation unit of its own (casclik_amd/jit.py, clik_jit_time_terms) and attached
+ * here: time_terms_fn is `hipError_t (*)(const double* times, long long n_times, int stages, double dt, double* out,
+ * hipStream_t)`; NULL detaches.
+ * clik_pinv_time_terms fills out [n_times * stages][2 * n_tslots] (device) from times [n_times] (device): row
+ * i * stages + s holds what `tterms` holds at the time of stage s of tick i - stages = 1: times[i]; stages = 4 (Runge-
+ * Kutta): times[i], times[i] + dt/2, times[i] + dt/2, times[i] + dt.  With stages = 1 and n_times = B it is the t_inst
+ * of clik_pinv_solve_batch_t.  One launch on `stream`, nothing read on the host.  CLIK_EUNSUPPORTED without an attached
+ * kernel; a skill without time slots: CLIK_OK, nothing is launched or written.  A row of a non-finite time holds
+ * whatever the arithmetic gives (device code is built without NaN semantics).                                     */
+int clik_pinv_attach_time_kernel(clik_pinv* h, void* time_terms_fn);
+int clik_pinv_time_terms(const clik_pinv* h, int64_t n_times, const double* times, int32_t stages, double dt,
+                         double* out, void* stream);
+/* clik_pinv_rollout_batch_rec with the tick times on the device: times [n_ticks] (device) in place of the host table
+ * tterms.  The time-slot records live in a stream-ordered allocation as before and are filled by the attached time
+ * kernel on `stream` ahead of the rollout: no host array, no pinned slot, nothing consumed at call time.  With
+ * y_per_tick = 0 and record_every = 0 this is clik_pinv_rollout_batch_m (the recording rollout is not needed).  times
+ * may be NULL for a skill without time slots; with time slots it needs the time kernel (CLIK_EUNSUPPORTED).        */
+int clik_pinv_rollout_batch_dev(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method,
+                                double dt, double max_speed, const double* times,
+                                double* q, double* x, const double* y, double* dq,
+                                double* dx, int32_t* mode, void* stream,
+                                int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
+                                double* rec_x, double* rec_dx, int32_t* rec_mode);
+
 /* ---- ReactiveQPController path ----------------------------------------- */
 /* replaces setup_problem_functions()+setup_solver() (reactive_qp.py:248-298) */
 int clik_qp_create(const clik_skill_desc* desc, const clik_qp_opts* opts,
@@ -467,6 +496,16 @@ int clik_qp_rollout_batch_m(const clik_qp* h, int64_t B, int32_t n_ticks, int32_
 int clik_qp_attach_rec_kernel(clik_qp* h, void* rollout_rec_fn, void* value_rollout_rec_fn);
 int clik_qp_rollout_batch_rec(const clik_qp* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
                               double max_speed, const double* tterms, double* q, double* x, const double* y,
+                              double* dq, double* dx, double* slack, int32_t* status, void* stream,
+                              int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
+                              double* rec_x, double* rec_dx, double* rec_slack, int32_t* rec_status);
+
+/* Time slots on the device, as clik_pinv_attach_time_kernel / clik_pinv_time_terms / clik_pinv_rollout_batch_dev.   */
+int clik_qp_attach_time_kernel(clik_qp* h, void* time_terms_fn);
+int clik_qp_time_terms(const clik_qp* h, int64_t n_times, const double* times, int32_t stages, double dt,
+                       double* out, void* stream);
+int clik_qp_rollout_batch_dev(const clik_qp* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
+                              double max_speed, const double* times, double* q, double* x, const double* y,
                               double* dq, double* dx, double* slack, int32_t* status, void* stream,
                               int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
                               double* rec_x, double* rec_dx, double* rec_slack, int32_t* rec_status);
