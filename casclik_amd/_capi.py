@@ -180,6 +180,8 @@ _SYMBOLS = [
     "clik_pinv_attach_rec_kernel", "clik_pinv_rollout_batch_rec", "clik_qp_attach_rec_kernel", "clik_qp_rollout_batch_rec",
     "clik_pinv_attach_time_kernel", "clik_pinv_time_terms", "clik_pinv_rollout_batch_dev",
     "clik_qp_attach_time_kernel", "clik_qp_time_terms", "clik_qp_rollout_batch_dev",
+    "clik_pinv_attach_monitor_kernel", "clik_pinv_constraint_values", "clik_pinv_n_constraint_rows",
+    "clik_qp_attach_monitor_kernel", "clik_qp_constraint_values", "clik_qp_n_constraint_rows",
     "clik_qp_create", "clik_qp_create_host", "clik_qp_destroy", "clik_qp_n_vars", "clik_qp_n_rows", "clik_qp_workspace_bytes",
     "clik_qp_kernel_name", "clik_qp_kernel_variant", "clik_qp_shape_describe", "clik_qp_attach_kernel", "clik_qp_image_words", "clik_qp_attach_value_kernel", "clik_qp_is_box_family",
     "clik_qp_attach_resident_kernel", "clik_qp_resident_waves", "clik_qp_resident_run",
@@ -346,6 +348,15 @@ def load_library(path=None):
                       ("clik_qp_rollout_batch_dev", lib.clik_qp_rollout_batch_rec)):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [dp if k == 6 else a for k, a in enumerate(rec.argtypes)]
+    # constraint values over a trajectory: `tterms` is a DEVICE table here, read through its two strides
+    for kind in ("pinv", "qp"):
+        fn = getattr(lib, "clik_%s_attach_monitor_kernel" % kind)
+        fn.restype, fn.argtypes = C.c_int, [vp, C.c_void_p]
+        fn = getattr(lib, "clik_%s_constraint_values" % kind)
+        fn.restype = C.c_int
+        fn.argtypes = [vp, C.c_int64, C.c_int64, dp, C.c_int64, C.c_int64, dp, dp, dp, C.c_int64, dp, dp, dp, vp]
+        fn = getattr(lib, "clik_%s_n_constraint_rows" % kind)
+        fn.restype, fn.argtypes = C.c_int, [vp]
     lib.clik_qp_n_vars.restype = C.c_int
     lib.clik_qp_n_vars.argtypes = [vp]
     lib.clik_qp_n_rows.restype = C.c_int

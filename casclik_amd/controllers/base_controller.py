@@ -279,6 +279,34 @@ def record_layout(fields, R, B):
     return out
 
 
+def constraint_row_slices(descriptor):
+    """``label -> slice`` into the ``M_tot`` rows of ``constraint_values_batch``, in skill order: the rows of a
+    lowered skill's constraints one after the other (the Velocity*Constraints included)."""
+    from collections import OrderedDict
+    out, r = OrderedDict(), 0
+    for task in descriptor.tasks:
+        out[task["label"]] = slice(r, r + int(task["m"]))
+        r += int(task["m"])
+    return out
+
+
+def trajectory_rows(val, width, what, lead=None):
+    """``val`` as ``(tensor-or-array [R, B, width], ndim)``: a ``[B, width]`` matrix (or what ``to_device_matrix`` takes
+    for one) is one record, ``ndim`` 2; a ``[R, B, width]`` array or tensor stays as it is, ``ndim`` 3.  ``lead``: the
+    ``(R, B)`` it must have.  ValueError otherwise."""
+    shape = tuple(val.shape) if hasattr(val, "shape") and not hasattr(val, "toarray") else None
+    if shape is not None and len(shape) == 3:
+        if shape[2] != width:
+            raise ValueError("%s must have %d columns, got shape %s" % (what, width, shape))
+        if lead is not None and shape[:2] != tuple(lead):
+            raise ValueError("%s [R, B, %d] has shape %s, robot_var %d record(s) of %d instance(s)"
+                             % (what, width, shape, lead[0], lead[1]))
+        return val, 3
+    if shape is not None and len(shape) > 3:
+        raise ValueError("%s must be [B, %d] or [R, B, %d], got shape %s" % (what, width, width, shape))
+    return val, 2
+
+
 class BaseController(object):
     """What a device controller is apart from its mathematics.  A controller class names the C entry points that make
     and free its handle (``_create_fn`` / ``_destroy_fn``), returns their options structure from ``_c_options()``, says
@@ -328,6 +356,7 @@ class BaseController(object):
         self._setup_c = (cdesc, copts)      # (the recording rollouts are instantiated later, at their first use)
         self._rec_kernel = None
         self._time_kernel = None
+        self._monitor_kernel = None
         return cdesc, copts
 
     def _want_jit(self):
@@ -560,6 +589,141 @@ class BaseController(object):
         if self._rec_kernel is None and self._want_jit():
             with _torch().cuda.device(self._device):
                 self._rec_kernel = attach() or False
+
+    # -- constraint values over a trajectory --------------------------------------------------------------------
+    def constraint_rows(self):
+        """Ordered dict ``label -> slice`` into the ``M_tot`` rows ``constraint_values_batch`` returns: the rows of
+        the skill's constraints in skill order.  Known after set-up (RuntimeError before), without a GPU call."""
+        if getattr(self, "descriptor", None) is None or getattr(self, "_handle", None) is None:
+            raise RuntimeError("call setup_problem_functions() / setup_solver() first")
+        return constraint_row_slices(self.descriptor)
+
+    def _require_monitor_kernel(self):
+        """The constraint-value kernel of this controller's skill (clik_monitor.hpp), instantiated and attached at the
+        first ``constraint_values_batch`` and cached like every other instantiation.  Where no kernel may be
+        instantiated (``_want_jit``) or none can be - a skill outside the shape-specialised family - nothing is
+        attached and the library refuses the call (NotImplementedError): there is no host fallback."""
+        if self._monitor_kernel is None and self._want_jit():
+            from .. import jit
+            d = self.descriptor
+            cdesc, copts = self._setup_c
+            with _torch().cuda.device(self._device):
+                if self._time_kind == "pinv":
+                    tag = jit.attach_monitor(self._lib, self._handle, cdesc, copts, extern=d.extern_source())
+                else:
+                    tag = jit.attach_qp_monitor(self._lib, self._handle, cdesc, extern=d.extern_source())
+            self._monitor_kernel = tag or False
+
+    def _trajectory_tensor(self, val, width, what, lead=None, shared=False):
+        """``(T [R, B, width], ndim, was_np)`` of one argument of ``constraint_values_batch``: contiguous float64 on the
+        controller's device; a tensor that already is that is used in place (the records of a rollout go in as they
+        are).  A ``[B, width]`` matrix is one record (``T [1, B, width]``, ``ndim`` 2); with ``lead = (R, B)`` of
+        ``robot_var`` and R > 1 it is accepted only where one block may serve all records (``shared``)."""
+        torch = _torch()
+        val, ndim = trajectory_rows(val, width, what, lead)
+        if ndim == 2:
+            t, was_np = to_device_matrix(val, width, self._device, what, None if lead is None else lead[1])
+            if lead is not None and lead[0] != 1 and not shared:
+                raise ValueError("%s must be [R, B, %d] like robot_var (%d records), got shape %s"
+                                 % (what, width, lead[0], tuple(t.shape)))
+            return t.unsqueeze(0), 2, was_np
+        if isinstance(val, torch.Tensor):
+            return val.to(device=self._device, dtype=torch.float64).contiguous(), 3, False
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(val, dtype=np.float64))).to(self._device), 3, True
+
+    def _monitor_time_table(self, time_var, R, B, ndim):
+        """``(T | None, tt_rec_stride, tt_inst_stride)`` of a ``constraint_values_batch`` call: the device table of
+        time terms and how row (r, b) finds its record in it.  One stamp: strides 0 / 0; ``[R]`` stamps with a 3-D
+        ``robot_var``: one record each; ``[B]`` stamps with a 2-D ``robot_var``: one per instance.  The table comes from
+        ``descriptor.time_terms`` per distinct stamp, uploaded once - or, with ``options["time_on_device"]``, from
+        ``time_terms_batch`` (a device tensor of times is then read in place, nothing on the host)."""
+        torch = _torch()
+        d = self.descriptor
+        is_tensor = isinstance(time_var, torch.Tensor)
+        n = int(time_var.numel()) if is_tensor else int(np.size(time_var))
+        if n == 0:
+            raise ValueError("time_var is empty")
+        many = n > 1
+        if many:
+            want = R if ndim == 3 else B
+            if n != want:
+                raise ValueError("time_var has %d entries, the trajectory %d %s" % (
+                    n, want, "record(s) (robot_var [R, B, n_q])" if ndim == 3 else "instance(s) (robot_var [B, n_q])"))
+        if d.n_tslots == 0:
+            return None, 0, 0
+        w = 2 * d.n_tslots
+        if self._time_kernel is not None:
+            T = self.time_terms_batch(self._device_times(time_var)[0])
+        else:
+            times = (time_var.detach().cpu().numpy() if is_tensor else np.asarray(time_var, dtype=float)).reshape(-1)
+            uniq, inverse = np.unique(times.astype(float), return_inverse=True)
+            terms = np.stack([d.time_terms(float(tv)) for tv in uniq])
+            T = torch.from_numpy(np.ascontiguousarray(terms[inverse.reshape(-1)])).to(self._device)
+        if not many:
+            return T, 0, 0
+        return (T, w, 0) if ndim == 3 else (T, 0, w)
+
+    def constraint_values_batch(self, time_var, robot_var, virtual_var=None, input_var=None, jacobian=False, out=None):
+        """The values of the skill's constraint expressions over a batch or a whole trajectory of states, in ONE launch
+        of a kernel of its own: what the notebooks of the reference get from ``cnstr.eval(t, q)`` once per tick.
+
+        ``robot_var``: ``[B, n_q]`` or ``[R, B, n_q]`` (numpy or device tensor; a contiguous float64 tensor on the
+        controller's device is read in place, so ``rec["q"]`` of a recording rollout goes in directly);
+        ``virtual_var``: the same leading shape; ``input_var``: ``[B, n_y]`` (shared by all records) or
+        ``[R, B, n_y]``.  ``time_var``: one stamp, ``[R]`` stamps with a 3-D ``robot_var`` (one per record) or ``[B]``
+        with a 2-D one (one per instance, as ``solve_batch``).  With ``options["time_on_device"]`` the time terms come
+        from the time kernel and ``time_var`` may be a device tensor (no host synchronisation).
+
+        Returns ``e [..., M_tot]``, or with ``jacobian=True`` ``(e, J [..., M_tot, n_q + n_x], e_t [..., M_tot])``:
+        the rows of all constraints in skill order (``constraint_rows()``), the Velocity*Constraints included, ``J``
+        the derivative with respect to (robot_var, virtual_var), ``e_t`` the partial derivative in time.  Numpy when
+        ``robot_var`` is numpy, device tensors otherwise.  ``out``: a preallocated device tensor for ``e``, filled in place
+        and returned - with a numpy ``robot_var`` it is still filled, and a numpy copy of it is returned.  The launch
+        goes on torch's current stream.  NotImplementedError when no kernel could be instantiated for the skill."""
+        self._require_handle()
+        torch = _torch()
+        d, dev = self.descriptor, self._device
+        Q, ndim, was_np = self._trajectory_tensor(robot_var, d.n_q, "robot_var")
+        R, B = int(Q.shape[0]), int(Q.shape[1])
+        X = Y = None
+        y_stride = 0
+        if d.n_x > 0:
+            if virtual_var is None:
+                raise ValueError("skill has virtual_var: pass virtual_var")
+            X = self._trajectory_tensor(virtual_var, d.n_x, "virtual_var", (R, B))[0]
+        if d.n_y > 0:
+            if input_var is None:
+                raise ValueError("skill has input_var: pass input_var")
+            Y, y_ndim, _ = self._trajectory_tensor(input_var, d.n_y, "input_var", (R, B), shared=True)
+            y_stride = B * d.n_y if y_ndim == 3 else 0
+        T, tt_rec, tt_inst = self._monitor_time_table(time_var, R, B, ndim)
+        m_tot, n = sum(int(t["m"]) for t in d.tasks), d.n_q + d.n_x
+        lead = (R, B) if ndim == 3 else (B,)
+        check_out_tensor(out, lead + (m_tot,), "float64", dev, "out")
+        E = out if out is not None else torch.empty(lead + (m_tot,), dtype=torch.float64, device=dev)
+        J = torch.empty(lead + (m_tot, n), dtype=torch.float64, device=dev) if jacobian else None
+        Et = torch.empty(lead + (m_tot,), dtype=torch.float64, device=dev) if jacobian else None
+        self._require_monitor_kernel()
+        with torch.cuda.device(dev):
+            rc = getattr(self._lib, "clik_%s_constraint_values" % self._time_kind)(
+                self._handle, R, B, ptr(T), tt_rec, tt_inst, ptr(Q), ptr(X), ptr(Y), y_stride, ptr(E), ptr(J), ptr(Et),
+                current_stream(dev))
+        _capi.check(self._lib, rc)
+        if not jacobian:
+            return E.cpu().numpy() if was_np else E
+        return self._to_caller((E, J, Et), was_np)
+
+    def constraint_values(self, time_var, robot_var, virtual_var=None, input_var=None):
+        """One instance, the reference's argument order: dict ``label -> DM [m, 1]``, what the notebooks'
+        ``cnstr.eval(t, q)`` returns for each constraint of the skill."""
+        from .. import sym as cs
+        self._require_handle()
+        d = self.descriptor
+        q = flat_vector(robot_var, d.n_q, "robot_var").reshape(1, -1)
+        x = flat_vector(virtual_var, d.n_x, "virtual_var").reshape(1, -1) if d.n_x > 0 and virtual_var is not None else None
+        y = flat_vector(input_var, d.n_y, "input_var").reshape(1, -1) if d.n_y > 0 and input_var is not None else None
+        e = self.constraint_values_batch(float(scalar_of(time_var)), q, virtual_var=x, input_var=y)[0]
+        return {label: cs.DM(e[sl].reshape(-1, 1)) for label, sl in self.constraint_rows().items()}
 
     # -- resident ticks -----------------------------------------------------------------------------------------
     def _resident_setup(self, waves, ring_depth, publish_ahead, stream, time_var):

@@ -74,6 +74,12 @@ typedef hipError_t (*clik_jit_rollout_fn)(const clik::LaunchArgs*, const double*
 // clik_jit_time_terms (casclik_amd/jit.py, clik_time.hpp): times [n] (device) -> time-slot records [n * stages][2 * n_tslots]
 typedef hipError_t (*clik_time_fn)(const double*, long long, int, double, double*, hipStream_t);
 
+// clik_jit_constraint_values (casclik_amd/jit.py, clik_monitor.hpp): skill image, n_rec, B, time-term table and its two
+// strides, q, x, y and its record stride, e, J, et (all device)
+typedef hipError_t (*clik_monitor_fn)(const void*, long long, long long, const double*, long long, long long,
+                                      const double*, const double*, const double*, long long, double*, double*, double*,
+                                      hipStream_t);
+
 typedef hipError_t (*clik_jit_value_fn)(const clik::LaunchArgs*, const TickArgs*, long long, const double*,
                                         const double*, double*, int32_t*, hipStream_t);
 
@@ -100,6 +106,8 @@ struct clik_pinv {
     clik_jit_rollout_fn val_rec_rollout = nullptr;
     // the skill's time slots as device code (clik_pinv_attach_time_kernel)
     clik_time_fn time_fn = nullptr;
+    // e, J, d e / d t of the skill's constraints over a trajectory (clik_pinv_attach_monitor_kernel)
+    clik_monitor_fn monitor_fn = nullptr;
 };
 
 // clik_jit_qp_rollout_rec / clik_jit_qp_value_rollout_rec: the rollouts' arguments and the RollRec
@@ -126,6 +134,7 @@ struct clik_qp {
     clik_qp_rec_fn rec_rollout = nullptr;
     clik_qp_value_rec_fn val_rec_rollout = nullptr;
     clik_time_fn time_fn = nullptr;          // the skill's time slots as device code (clik_qp_attach_time_kernel)
+    clik_monitor_fn monitor_fn = nullptr;    // constraint values over a trajectory (clik_qp_attach_monitor_kernel)
     char      jit_name[64];
     // work area of the global-workspace kernels (clik_workspace.hpp): belongs to this handle, released by clik_qp_destroy
     clik::GwsOwner* gws;
@@ -1286,6 +1295,65 @@ extern "C" int clik_pinv_attach_rec_kernel(clik_pinv* h, void* rollout_rec_fn, v
     return CLIK_OK;
 }
 
+// ---- constraint values over a trajectory (clik_*_constraint_values; the kernel: clik_monitor.hpp) ---------------------
+static int n_constraint_rows(const DevSkill& S)
+{
+    int m = 0;
+    for (int ti = 0; ti < S.d.n_tasks; ++ti) m += S.d.tasks[ti].m;
+    return m;
+}
+
+// what clik_*_constraint_values check before they launch (`host_only`: the handle has nothing on the device)
+static int constraint_values_common(clik_monitor_fn fn, const DevSkill& S, const void* d_img, bool host_only, int64_t n_rec,
+                                    int64_t B, const double* tterms, int64_t tt_rec_stride, int64_t tt_inst_stride,
+                                    const double* q, const double* x, const double* y, int64_t y_stride, double* e,
+                                    double* J, double* et, void* stream)
+{
+    if (n_rec < 0 || B < 0) return fail(CLIK_EINVAL, "negative size");
+    if (n_rec == 0 || B == 0) return CLIK_OK;
+    if (!q) return fail(CLIK_EINVAL, "q must be a device pointer");
+    if (!e && !J && !et) return fail(CLIK_EINVAL, "nothing to compute: e, J and et are all null");
+    if (!fn)
+        return fail(CLIK_EUNSUPPORTED, "no constraint-value kernel instantiated for this skill (clik_*_attach_monitor_kernel: "
+                                       "skills of the shape-specialised family have one)");
+    if (host_only)
+        return fail(CLIK_EINVAL, "this handle was created host-only (clik_*_create_host / CLIK_HOST_ONLY=1): host-side queries only");
+    if (!d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device");
+    if (S.d.n_x > 0 && !x) return fail(CLIK_EINVAL, "skill has virtual_var: x required");
+    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    if (y_stride < 0 || tt_rec_stride < 0 || tt_inst_stride < 0) return fail(CLIK_EINVAL, "negative stride");
+    if (S.d.n_tslots > 0 && !tterms) return fail(CLIK_EINVAL, "tterms (device) required: the skill has time slots");
+    const hipError_t er = fn(d_img, (long long)n_rec, (long long)B, S.d.n_tslots > 0 ? tterms : nullptr,
+                             (long long)tt_rec_stride, (long long)tt_inst_stride, q, x, y, (long long)y_stride, e, J, et,
+                             (hipStream_t)stream);
+    if (er != hipSuccess) return hipfail(er, "constraint-value kernel launch");
+    return CLIK_OK;
+}
+
+extern "C" int clik_pinv_attach_monitor_kernel(clik_pinv* h, void* constraint_values_fn)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    if (constraint_values_fn) {
+        CLIK_NEEDS_DEVICE_HANDLE(h);
+        if (!h->jit_solve && !h->jit_rollout && !(h->kernel >= 0 && clik::pinv_kernel_is_static(h->kernel)))
+            return fail(CLIK_EUNSUPPORTED, "constraint values exist for skills a shape-specialised kernel serves");
+        if (!h->d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device: attach the kernel first");
+    }
+    h->monitor_fn = (clik_monitor_fn)constraint_values_fn;
+    return CLIK_OK;
+}
+
+extern "C" int clik_pinv_n_constraint_rows(const clik_pinv* h) { return h ? n_constraint_rows(h->host) : 0; }
+
+extern "C" int clik_pinv_constraint_values(const clik_pinv* h, int64_t n_rec, int64_t B, const double* tterms,
+                                           int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
+                                           const double* y, int64_t y_stride, double* e, double* J, double* et, void* stream)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    return constraint_values_common(h->monitor_fn, h->host, h->d_img, h->dev == nullptr, n_rec, B, tterms, tt_rec_stride,
+                                    tt_inst_stride, q, x, y, y_stride, e, J, et, stream);
+}
+
 static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
                                double max_speed, const TtSource& tts, double* q, double* x, const double* y,
                                double* dq, double* dx, int32_t* mode, void* stream, const clik::RollRec* rec)
@@ -1604,6 +1672,30 @@ extern "C" int clik_qp_attach_rec_kernel(clik_qp* h, void* rollout_rec_fn, void*
     // (the value-specialised rollout exists for the box family only)
     h->val_rec_rollout = CLIK_QP_BOX_OK(h->host.shape) ? (clik_qp_value_rec_fn)value_rollout_rec_fn : nullptr;
     return CLIK_OK;
+}
+
+extern "C" int clik_qp_attach_monitor_kernel(clik_qp* h, void* constraint_values_fn)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    if (constraint_values_fn) {
+        CLIK_NEEDS_DEVICE_HANDLE(h);
+        if (!qp_static_eligible(h->host)) return fail(CLIK_EUNSUPPORTED, "skill is outside the shape-specialised QP family");
+        int rc = qp_upload_image(h);
+        if (rc) return rc;
+    }
+    h->monitor_fn = (clik_monitor_fn)constraint_values_fn;
+    return CLIK_OK;
+}
+
+extern "C" int clik_qp_n_constraint_rows(const clik_qp* h) { return h ? n_constraint_rows(h->host) : 0; }
+
+extern "C" int clik_qp_constraint_values(const clik_qp* h, int64_t n_rec, int64_t B, const double* tterms,
+                                         int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
+                                         const double* y, int64_t y_stride, double* e, double* J, double* et, void* stream)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    return constraint_values_common(h->monitor_fn, h->host, h->d_img, h->dev == nullptr, n_rec, B, tterms, tt_rec_stride,
+                                    tt_inst_stride, q, x, y, y_stride, e, J, et, stream);
 }
 
 static int qp_rollout_common(const clik_qp* hc, int64_t B, int32_t n_ticks, int32_t method, double dt,

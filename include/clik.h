@@ -404,6 +404,26 @@ int clik_pinv_rollout_batch_dev(const clik_pinv* h, int64_t B, int32_t n_ticks, 
                                 int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
                                 double* rec_x, double* rec_dx, int32_t* rec_mode);
 
+/* Constraint values over a trajectory of states: e, J = d e / d (q, x) and d e / d t of every constraint of the skill
+ * (the Velocity*Constraints included: their expression is evaluated like any other) at n_rec records of B instances, as
+ * one launch of a kernel of its own (casclik_amd/csrc/clik_monitor.hpp, instantiated by casclik_amd/jit.py as
+ * clik_jit_constraint_values and attached here; NULL detaches).  All pointers are device memory:
+ *   q [n_rec][B][n_q], x [n_rec][B][n_x] (NULL without virtual variables) - the records of a recording rollout go in as
+ *     they are;
+ *   y: the input_var rows of record r are [B][n_y] at y + r * y_stride doubles; y_stride = 0: one block for all records;
+ *   tterms: a DEVICE table of time terms (2 * n_tslots doubles a row, as the host table of the ticks); row (r, b) reads
+ *     at tterms + r * tt_rec_stride + b * tt_inst_stride doubles - 0 / 0: one stamp, 2 n_tslots / 0: one per record,
+ *     0 / 2 n_tslots: one per instance (as t_inst of clik_pinv_solve_batch_t); NULL for a skill without time slots;
+ *   e [n_rec * B][M_tot], J [n_rec * B][M_tot][n_q + n_x] row-major, et [n_rec * B][M_tot]; each may be NULL (not
+ *     written), not all three.  M_tot = clik_pinv_n_constraint_rows: the sum of the constraints' rows, in skill order.
+ * CLIK_EUNSUPPORTED for a handle without an attached kernel (none was instantiated for the skill: only skills of the
+ * shape-specialised family have one); n_rec * B == 0: CLIK_OK, nothing is launched.                                 */
+int clik_pinv_attach_monitor_kernel(clik_pinv* h, void* constraint_values_fn);
+int clik_pinv_constraint_values(const clik_pinv* h, int64_t n_rec, int64_t B, const double* tterms,
+                                int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
+                                const double* y, int64_t y_stride, double* e, double* J, double* et, void* stream);
+int clik_pinv_n_constraint_rows(const clik_pinv* h);
+
 /* ---- ReactiveQPController path ----------------------------------------- */
 /* replaces setup_problem_functions()+setup_solver() (reactive_qp.py:248-298) */
 int clik_qp_create(const clik_skill_desc* desc, const clik_qp_opts* opts,
@@ -509,6 +529,14 @@ int clik_qp_rollout_batch_dev(const clik_qp* h, int64_t B, int32_t n_ticks, int3
                               double* dq, double* dx, double* slack, int32_t* status, void* stream,
                               int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
                               double* rec_x, double* rec_dx, double* rec_slack, int32_t* rec_status);
+
+/* Constraint values over a trajectory of states, as clik_pinv_attach_monitor_kernel / clik_pinv_constraint_values /
+ * clik_pinv_n_constraint_rows (plain e, J, d e / d t: no gains, no slack columns - clik_qp_data_batch has those).    */
+int clik_qp_attach_monitor_kernel(clik_qp* h, void* constraint_values_fn);
+int clik_qp_constraint_values(const clik_qp* h, int64_t n_rec, int64_t B, const double* tterms,
+                              int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
+                              const double* y, int64_t y_stride, double* e, double* J, double* et, void* stream);
+int clik_qp_n_constraint_rows(const clik_qp* h);
 
 /* QP data only (H diag, A, lbA, ubA as the reference's H_func/A_func/Blb/Bub,
  * reactive_qp.py:283-298) for inspection and parity tests:
