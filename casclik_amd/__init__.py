@@ -22,6 +22,7 @@ from casclik_amd.geom import casadi_geom, numpy_geom
 from casclik_amd.controllers import base_controller, pseudo_inverse, reactive_qp
 from casclik_amd.controllers.base_controller import ResidentWatchdog
 from casclik_amd import sym as cs
+from casclik_amd.function_batch import DeviceFunction
 
 
 class _OutOfScopeController(object):

@@ -282,3 +282,103 @@ def emit_time_slots(low_or_desc):
             "        %s\n"
             "    }\n"
             "};\n" % (n, body))
+
+
+class _FunctionEmitter(TaskEmitter):
+    """Node emission of TaskEmitter for the outputs of a ``sym.Function``: a symbol of input k is a read of the lane's
+    row of that input, ``x[...]``; there is no skill, so no time slot and no kernel-side kinematics."""
+
+    def __init__(self, leaves, name):
+        TaskEmitter.__init__(self, None)
+        self.leaves = leaves        # (id(family), index) -> "x[...]"
+        self.fn_name = name
+
+    def _ref(self, node):
+        op = node.op
+        if op == "const":
+            return _lit(node.value)
+        if op == "sym":
+            ref = self.leaves.get((id(node.family), node.index))
+            if ref is None:
+                raise NotImplementedError("symbol '%s' is not an input of the function '%s'" % (node.name, self.fn_name))
+            return ref
+        if op in ("fk", "fk_d", "ori_err"):        # (written out before emission, see emit_function)
+            raise NotImplementedError("no device code for operation '%s' in a function" % op)
+        return self._op(node)
+
+
+def _expand_all(node):
+    """keep_fk / keep_ori of expand.rewrite: no atom is kept"""
+    return False
+
+
+def function_layout(fn):
+    """(inputs, outputs) of a ``sym.Function`` as lists of (size1, size2, offset): where each input's row begins in the
+    lane's flat input array ``x`` and each output's row in ``y``.  Rows are row-major (entry (i, j) of an
+    ``size1 x size2`` matrix at ``offset + i * size2 + j``, numpy order)."""
+    ins, outs, off = [], [], 0
+    for mx in fn._inputs:
+        ins.append((mx.size1(), mx.size2(), off))
+        off += mx.numel()
+    off = 0
+    for mx in fn._outputs:
+        outs.append((mx.size1(), mx.size2(), off))
+        off += mx.numel()
+    return ins, outs
+
+
+def emit_function(fn):
+    """C++ source of ``struct BatchFn`` for a ``sym.Function``: compile-time input / output counts, widths and offsets
+    and one straight-line function
+
+        BatchFn::eval(const double (&x)[n_x], double (&y)[n_y])
+
+    that reads the lane's input rows from ``x`` (input k at ``in_off[k]``, ``in_w[k]`` doubles) and writes every entry
+    of every output into ``y`` (output k at ``out_off[k]``) exactly once, reading none of them back.  Rows are row-major
+    (``function_layout``): the symbols of a matrix input are numbered down the columns (``MX.sym``), its memory runs
+    along the rows, and the emitter maps the one to the other.  Common sub-expressions are shared across all outputs;
+    ``sin`` / ``cos`` go through ``sincos_joint``, one pair per argument, which the includer supplies (as for
+    ``emit_time_slots``).  The kinematics atoms are written out first - there is no kernel-side forward kinematics or
+    skill image here - 'fk' and 'ori_err' as for any expression outside the row table, 'fk_d' (what ``cs.jacobian`` of
+    a tool position leaves in an output) by ``expand.fk_d_entry``.  NotImplementedError for a symbol that is not one
+    of the function's inputs and for an operation without device code."""
+    from . import expand
+    from . import sym as cs
+    ins, outs = function_layout(fn)
+    if not ins or not outs or any(a * b == 0 for a, b, _ in ins + outs):
+        raise NotImplementedError("function '%s': no device code for a function without inputs or outputs, or with "
+                                  "an empty one" % fn.name)
+    leaves = {}
+    for mx, (s1, s2, off) in zip(fn._inputs, ins):
+        arr = cs._as_array(mx)
+        for i in range(s1):
+            for j in range(s2):
+                leaves[(id(arr[i, j].family), arr[i, j].index)] = "x[%d]" % (off + i * s2 + j)
+    em = _FunctionEmitter(leaves, fn.name)
+    memo, stores = {}, []
+    for mx, (s1, s2, off) in zip(fn._outputs, outs):
+        arr = cs._as_array(mx)
+        for i in range(s1):
+            for j in range(s2):
+                node = expand.rewrite(arr[i, j], _expand_all, _expand_all, memo, expand_fk_d=True)
+                em._keep.append(node)
+                stores.append("y[%d] = %s;" % (off + i * s2 + j, em.ref(node)))
+    body = "\n        ".join(em.lines + stores)
+
+    def arr_of(vals):
+        return "{%s}" % ", ".join(str(v) for v in vals)
+    return ("struct BatchFn {\n"
+            "    static constexpr int n_in = %d, n_out = %d, n_x = %d, n_y = %d;\n"
+            "    static constexpr int in_w[%d] = %s;\n"
+            "    static constexpr int in_off[%d] = %s;\n"
+            "    static constexpr int out_w[%d] = %s;\n"
+            "    static constexpr int out_off[%d] = %s;\n"
+            "    __device__ __forceinline__ static void eval(const double (&x)[%d], double (&y)[%d])\n"
+            "    {\n"
+            "        (void)x;\n"
+            "        %s\n"
+            "    }\n"
+            "};\n" % (len(ins), len(outs), sum(a * b for a, b, _ in ins), sum(a * b for a, b, _ in outs),
+                      len(ins), arr_of(a * b for a, b, _ in ins), len(ins), arr_of(o for _, _, o in ins),
+                      len(outs), arr_of(a * b for a, b, _ in outs), len(outs), arr_of(o for _, _, o in outs),
+                      sum(a * b for a, b, _ in ins), sum(a * b for a, b, _ in outs), body))

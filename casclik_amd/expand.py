@@ -99,31 +99,79 @@ def ori_err_entries(rn, qn):
     return [m(half, acc[k]) for k in range(3)]
 
 
-def rewrite(node, keep_fk, keep_ori, memo):
+_FK_D_CACHE = {}
+
+
+def _substituted(node, table, memo):
+    """``node`` with the symbols in ``table`` ((id(family), index) -> Scalar) replaced; shared sub-trees stay shared"""
+    k = id(node)
+    if k in memo:
+        return memo[k]
+    if node.op == "const":
+        out = node
+    elif node.op == "sym":
+        out = table.get((id(node.family), node.index), node)
+    else:
+        args = tuple(_substituted(a, table, memo) for a in node.args)
+        out = node if all(x is y for x, y in zip(args, node.args)) else cs.Scalar(
+            node.op, args, value=node.value, name=node.name, index=node.index, family=node.family, aux=node.aux)
+    memo[k] = out
+    return out
+
+
+def fk_d_entry(chain, qargs, i, j, k, memo):
+    """The Scalar an 'fk_d' atom stands for - d T[i][j] / d (joint argument k) of ``chain`` - written out: the chain's
+    transform in sin / cos of placeholder symbols (``fk_entries``), differentiated with respect to placeholder k
+    (autodiff.diff_scalar), the atom's arguments ``qargs`` put back.  Placeholders, transform and derivative trees are
+    kept per chain; the substitution is memoised in the caller's ``memo`` (that of ``rewrite``), so the entries of one
+    Jacobian share their sub-trees."""
+    from . import autodiff
+    hit = _FK_D_CACHE.get(id(chain))
+    if hit is None or hit[0] is not chain:          # (the entry keeps its chain alive: an id cannot be reused under it)
+        pl = tuple(cs._as_array(cs.MX.sym("fk_placeholder", chain.n_actuated)).reshape(-1))
+        if len(_FK_D_CACHE) > 16:                   # (a few chains per process: bounded, oldest entries go)
+            _FK_D_CACHE.pop(next(iter(_FK_D_CACHE)))
+        hit = _FK_D_CACHE[id(chain)] = (chain, pl, fk_entries(chain, pl), [dict() for _ in pl])
+    _, pl, T, dmemo = hit
+    d = autodiff.diff_scalar(T[i][j], (id(pl[k].family), pl[k].index), dmemo[k])
+    skey = ("fk_d", id(chain)) + tuple(id(a) for a in qargs)
+    if skey not in memo:                            # (the entry keeps the arguments alive, as above)
+        memo[skey] = (tuple(qargs), {(id(p.family), p.index): a for p, a in zip(pl, qargs)}, {})
+    _, table, smemo = memo[skey]
+    return _substituted(d, table, smemo)
+
+
+def rewrite(node, keep_fk, keep_ori, memo, expand_fk_d=False):
     """``node`` with every 'fk' atom for which ``keep_fk(node)`` is false and every 'ori_err' atom for which
     ``keep_ori(node)`` is false replaced by its explicit expression (recursively: the R entries of an expanded
-    orientation error are rewritten too).  Shared sub-trees stay shared (memo by node identity)."""
+    orientation error are rewritten too).  Shared sub-trees stay shared (memo by node identity).  With
+    ``expand_fk_d`` the 'fk_d' atoms that differentiation leaves behind (autodiff: d fk / d argument) are written out as
+    well (``fk_d_entry``) - for code that has no kernel-side kinematics to read them from (codegen.emit_function)."""
     k = id(node)
     if k in memo:
         return memo[k]
     op = node.op
     if op in ("const", "sym"):
         out = node
+    elif op == "fk_d" and expand_fk_d:
+        chain, i, j, kk = node.aux
+        args = tuple(rewrite(a, keep_fk, keep_ori, memo, expand_fk_d) for a in node.args)
+        out = fk_d_entry(chain, args, i, j, kk, memo)
     elif op == "fk":
         if keep_fk(node):
             out = node
         else:
             chain, i, j = node.aux
-            args = tuple(rewrite(a, keep_fk, keep_ori, memo) for a in node.args)
+            args = tuple(rewrite(a, keep_fk, keep_ori, memo, expand_fk_d) for a in node.args)
             out = fk_entries(chain, args)[i][j]
     elif op == "ori_err":
         if keep_ori(node):
             out = node
         else:
-            args = [rewrite(a, keep_fk, keep_ori, memo) for a in node.args]
+            args = [rewrite(a, keep_fk, keep_ori, memo, expand_fk_d) for a in node.args]
             out = ori_err_entries(args[:9], args[9:13])[node.aux]
     else:
-        args = tuple(rewrite(a, keep_fk, keep_ori, memo) for a in node.args)
+        args = tuple(rewrite(a, keep_fk, keep_ori, memo, expand_fk_d) for a in node.args)
         if all(x is y for x, y in zip(args, node.args)):
             out = node
         else:

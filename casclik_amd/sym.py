@@ -1110,6 +1110,12 @@ class Function(object):
             outs = [DM(evaluate(o, env)) for o in self._outputs]
         return outs[0] if len(outs) == 1 else tuple(outs)
 
+    def on_device(self, device=None):
+        """The compiled, batched form of this function on the GPU (``casclik_amd.DeviceFunction``): its outputs at
+        every row of a batch or of a recorded trajectory in one launch, device tensors in and out."""
+        from .function_batch import DeviceFunction
+        return DeviceFunction(self, device)
+
     def __repr__(self):
         return "Function(%s)" % self.name
 
