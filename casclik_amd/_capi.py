@@ -182,6 +182,9 @@ _SYMBOLS = [
     "clik_qp_attach_time_kernel", "clik_qp_time_terms", "clik_qp_rollout_batch_dev",
     "clik_pinv_attach_monitor_kernel", "clik_pinv_constraint_values", "clik_pinv_n_constraint_rows",
     "clik_qp_attach_monitor_kernel", "clik_qp_constraint_values", "clik_qp_n_constraint_rows",
+    "clik_summary_chunk_length",
+    "clik_pinv_attach_summary_kernel", "clik_pinv_summary_work_bytes", "clik_pinv_constraint_summary",
+    "clik_qp_attach_summary_kernel", "clik_qp_summary_work_bytes", "clik_qp_constraint_summary",
     "clik_qp_create", "clik_qp_create_host", "clik_qp_destroy", "clik_qp_n_vars", "clik_qp_n_rows", "clik_qp_workspace_bytes",
     "clik_qp_kernel_name", "clik_qp_kernel_variant", "clik_qp_shape_describe", "clik_qp_attach_kernel", "clik_qp_image_words", "clik_qp_attach_value_kernel", "clik_qp_is_box_family",
     "clik_qp_attach_resident_kernel", "clik_qp_resident_waves", "clik_qp_resident_run",
@@ -357,6 +360,17 @@ def load_library(path=None):
         fn.argtypes = [vp, C.c_int64, C.c_int64, dp, C.c_int64, C.c_int64, dp, dp, dp, C.c_int64, dp, dp, dp, vp]
         fn = getattr(lib, "clik_%s_n_constraint_rows" % kind)
         fn.restype, fn.argtypes = C.c_int, [vp]
+        # ... and their summaries: the same inputs, then tol, the work area and its size, the seven outputs
+        fn = getattr(lib, "clik_%s_attach_summary_kernel" % kind)
+        fn.restype, fn.argtypes = C.c_int, [vp, C.c_void_p, C.c_void_p]
+        fn = getattr(lib, "clik_%s_summary_work_bytes" % kind)
+        fn.restype, fn.argtypes = C.c_int64, [vp, C.c_int64, C.c_int64]
+        fn = getattr(lib, "clik_%s_constraint_summary" % kind)
+        fn.restype = C.c_int
+        fn.argtypes = [vp, C.c_int64, C.c_int64, dp, C.c_int64, C.c_int64, dp, dp, dp, C.c_int64, dp, vp, C.c_int64,
+                       dp, ip, dp, dp, dp, ip, ip, vp]
+    lib.clik_summary_chunk_length.restype = C.c_int64
+    lib.clik_summary_chunk_length.argtypes = [C.c_int64, C.c_int64]
     lib.clik_qp_n_vars.restype = C.c_int
     lib.clik_qp_n_vars.argtypes = [vp]
     lib.clik_qp_n_rows.restype = C.c_int

@@ -290,6 +290,22 @@ def constraint_row_slices(descriptor):
     return out
 
 
+def summary_tolerances(tol, m_tot):
+    """``tol`` of ``constraint_summary_batch`` as ``[m_tot]`` float64 (None stays None): a scalar for all rows or one
+    value per row, finite and >= 0.  ValueError otherwise."""
+    if tol is None:
+        return None
+    arr = np.asarray(tol.detach().cpu().numpy() if hasattr(tol, "detach") else tol, dtype=np.float64)
+    if arr.ndim == 0:
+        arr = np.full(m_tot, float(arr))
+    arr = arr.reshape(-1)
+    if arr.size != m_tot:
+        raise ValueError("tol has %d entries, the skill %d constraint rows" % (arr.size, m_tot))
+    if not (np.isfinite(arr).all() and (arr >= 0.0).all()):
+        raise ValueError("tol must be finite and >= 0")
+    return np.ascontiguousarray(arr)
+
+
 def trajectory_rows(val, width, what, lead=None):
     """``val`` as ``(tensor-or-array [R, B, width], ndim)``: a ``[B, width]`` matrix (or what ``to_device_matrix`` takes
     for one) is one record, ``ndim`` 2; a ``[R, B, width]`` array or tensor stays as it is, ``ndim`` 3.  ``lead``: the
@@ -357,6 +373,7 @@ class BaseController(object):
         self._rec_kernel = None
         self._time_kernel = None
         self._monitor_kernel = None
+        self._summary_kernel = None
         return cdesc, copts
 
     def _want_jit(self):
@@ -724,6 +741,90 @@ class BaseController(object):
         y = flat_vector(input_var, d.n_y, "input_var").reshape(1, -1) if d.n_y > 0 and input_var is not None else None
         e = self.constraint_values_batch(float(scalar_of(time_var)), q, virtual_var=x, input_var=y)[0]
         return {label: cs.DM(e[sl].reshape(-1, 1)) for label, sl in self.constraint_rows().items()}
+
+    # -- constraint summaries over a trajectory -----------------------------------------------------------------
+    def _require_summary_kernel(self):
+        """The constraint-summary kernels of this controller's skill (clik_summary.hpp), instantiated and attached at
+        the first ``constraint_summary_batch`` and cached like every other instantiation; as
+        ``_require_monitor_kernel``: where none may or can be instantiated, nothing is attached and the library refuses
+        the call (NotImplementedError)."""
+        if self._summary_kernel is None and self._want_jit():
+            from .. import jit
+            d = self.descriptor
+            cdesc, copts = self._setup_c
+            with _torch().cuda.device(self._device):
+                if self._time_kind == "pinv":
+                    tag = jit.attach_summary(self._lib, self._handle, cdesc, copts, extern=d.extern_source())
+                else:
+                    tag = jit.attach_qp_summary(self._lib, self._handle, cdesc, extern=d.extern_source())
+            self._summary_kernel = tag or False
+
+    def constraint_summary_batch(self, time_var, robot_var, virtual_var=None, input_var=None, tol=None):
+        """What the skill's constraint expressions did over a whole trajectory of states, per instance and per
+        constraint row: the reduction over the record axis of what ``constraint_values_batch`` returns, done inside the
+        kernel that evaluates the constraints - ``e [R, B, M_tot]`` is never stored.
+
+        The arguments are those of ``constraint_values_batch``: ``robot_var`` ``[R, B, n_q]`` (or ``[B, n_q]``: one
+        record), ``virtual_var`` the same leading shape, ``input_var`` ``[B, n_y]`` (shared by all records) or
+        ``[R, B, n_y]``, ``time_var`` one stamp or ``[R]`` stamps (a device tensor with ``options["time_on_device"]``).
+        Device tensors are read in place - ``rec["q"]`` of a recording rollout goes in directly - and the launch goes on
+        torch's current stream.
+
+        Returns a dict of ``[B, M_tot]`` arrays, rows as ``constraint_rows()``; numpy when ``robot_var`` is numpy,
+        device tensors otherwise.  Over the records r = 0 .. R - 1:
+
+        * ``abs_max`` (float64) max |e[r]|, ``abs_max_at`` (int32) the first r that attains it;
+        * ``last`` e[R - 1]; ``rms`` sqrt(mean e[r]^2);
+        * ``viol_max`` on the rows of a ``SetConstraint`` max over r of max(set_min - e, e - set_max, 0) and
+          ``viol_count`` (int32) the number of records with a violation > 0 - with the bounds the ticks use, expressions
+          evaluated at the record's own (t, q, x, y); an infinite bound is "no bound".  0 on the rows of every other
+          class (the bounds of a ``VelocitySetConstraint`` apply to a velocity, not to e);
+        * ``settled_at`` (int32), only with ``tol`` - a scalar or ``[M_tot]`` values, finite and >= 0 (ValueError
+          otherwise): the smallest r such that d[r'] <= tol[row] for all r' >= r, R when the last record is outside; d
+          is the violation on ``SetConstraint`` rows and |e| on the others.
+
+        The record axis is reduced in chunks of ``summary_chunk_length(R, B)`` records, combined in order: the result
+        is the same bits on every call and for an instance whatever batch it is part of.  A row whose e is non-finite
+        at any record reports NaN in ``abs_max``, ``last``, ``rms`` and ``viol_max``; its three integer outputs are
+        unspecified; no other instance changes.  NotImplementedError when no kernel could be instantiated for the
+        skill: there is no host fallback."""
+        self._require_handle()
+        torch = _torch()
+        d, dev = self.descriptor, self._device
+        Q, ndim, was_np = self._trajectory_tensor(robot_var, d.n_q, "robot_var")
+        R, B = int(Q.shape[0]), int(Q.shape[1])
+        X = Y = None
+        y_stride = 0
+        if d.n_x > 0:
+            if virtual_var is None:
+                raise ValueError("skill has virtual_var: pass virtual_var")
+            X = self._trajectory_tensor(virtual_var, d.n_x, "virtual_var", (R, B))[0]
+        if d.n_y > 0:
+            if input_var is None:
+                raise ValueError("skill has input_var: pass input_var")
+            Y, y_ndim, _ = self._trajectory_tensor(input_var, d.n_y, "input_var", (R, B), shared=True)
+            y_stride = B * d.n_y if y_ndim == 3 else 0
+        # (one stamp, or one per record: a [B, n_q] robot_var is one record, not B stamps as in constraint_values_batch)
+        T, tt_rec, tt_inst = self._monitor_time_table(time_var, R, B, 3)
+        m_tot = sum(int(t["m"]) for t in d.tasks)
+        tol_dev = summary_tolerances(tol, m_tot)
+        if tol_dev is not None:
+            tol_dev = torch.from_numpy(tol_dev).to(dev)
+        f64 = lambda: torch.empty((B, m_tot), dtype=torch.float64, device=dev)      # noqa: E731
+        i32 = lambda: torch.empty((B, m_tot), dtype=torch.int32, device=dev)        # noqa: E731
+        out = {"abs_max": f64(), "abs_max_at": i32(), "last": f64(), "rms": f64(), "viol_max": f64(), "viol_count": i32()}
+        if tol_dev is not None:
+            out["settled_at"] = i32()
+        self._require_summary_kernel()
+        with torch.cuda.device(dev):
+            n_work = int(getattr(self._lib, "clik_%s_summary_work_bytes" % self._time_kind)(self._handle, R, B))
+            work = torch.empty(max(n_work, 8) // 8 + 1, dtype=torch.float64, device=dev)
+            rc = getattr(self._lib, "clik_%s_constraint_summary" % self._time_kind)(
+                self._handle, R, B, ptr(T), tt_rec, tt_inst, ptr(Q), ptr(X), ptr(Y), y_stride, ptr(tol_dev), ptr(work),
+                work.numel() * 8, ptr(out["abs_max"]), ptr(out["abs_max_at"]), ptr(out["last"]), ptr(out["rms"]),
+                ptr(out["viol_max"]), ptr(out["viol_count"]), ptr(out.get("settled_at")), current_stream(dev))
+        _capi.check(self._lib, rc)
+        return {k: v.cpu().numpy() for k, v in out.items()} if was_np else out
 
     # -- resident ticks -----------------------------------------------------------------------------------------
     def _resident_setup(self, waves, ring_depth, publish_ahead, stream, time_var):

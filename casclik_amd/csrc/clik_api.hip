@@ -80,6 +80,14 @@ typedef hipError_t (*clik_monitor_fn)(const void*, long long, long long, const d
                                       const double*, const double*, const double*, long long, double*, double*, double*,
                                       hipStream_t);
 
+// clik_jit_constraint_summary / clik_jit_summary_work_bytes (casclik_amd/jit.py, clik_summary.hpp): as clik_monitor_fn up
+// to y_stride, then tol, the work area and its size, the seven outputs (all device)
+typedef hipError_t (*clik_summary_fn)(const void*, long long, long long, const double*, long long, long long,
+                                      const double*, const double*, const double*, long long, const double*, void*,
+                                      unsigned long long, double*, int32_t*, double*, double*, double*, int32_t*, int32_t*,
+                                      hipStream_t);
+typedef unsigned long long (*clik_summary_work_fn)(long long, long long);
+
 typedef hipError_t (*clik_jit_value_fn)(const clik::LaunchArgs*, const TickArgs*, long long, const double*,
                                         const double*, double*, int32_t*, hipStream_t);
 
@@ -108,6 +116,9 @@ struct clik_pinv {
     clik_time_fn time_fn = nullptr;
     // e, J, d e / d t of the skill's constraints over a trajectory (clik_pinv_attach_monitor_kernel)
     clik_monitor_fn monitor_fn = nullptr;
+    // per-instance summaries of them over a trajectory (clik_pinv_attach_summary_kernel)
+    clik_summary_fn summary_fn = nullptr;
+    clik_summary_work_fn summary_work_fn = nullptr;
 };
 
 // clik_jit_qp_rollout_rec / clik_jit_qp_value_rollout_rec: the rollouts' arguments and the RollRec
@@ -135,6 +146,8 @@ struct clik_qp {
     clik_qp_value_rec_fn val_rec_rollout = nullptr;
     clik_time_fn time_fn = nullptr;          // the skill's time slots as device code (clik_qp_attach_time_kernel)
     clik_monitor_fn monitor_fn = nullptr;    // constraint values over a trajectory (clik_qp_attach_monitor_kernel)
+    clik_summary_fn summary_fn = nullptr;    // their per-instance summaries (clik_qp_attach_summary_kernel)
+    clik_summary_work_fn summary_work_fn = nullptr;
     char      jit_name[64];
     // work area of the global-workspace kernels (clik_workspace.hpp): belongs to this handle, released by clik_qp_destroy
     clik::GwsOwner* gws;
@@ -1354,6 +1367,92 @@ extern "C" int clik_pinv_constraint_values(const clik_pinv* h, int64_t n_rec, in
                                     tt_inst_stride, q, x, y, y_stride, e, J, et, stream);
 }
 
+// ---- constraint summaries over a trajectory (clik_*_constraint_summary; the kernels: clik_summary.hpp) -----------------
+// what clik_*_constraint_summary check before they launch
+static int constraint_summary_common(clik_summary_fn fn, clik_summary_work_fn work_fn, const DevSkill& S, const void* d_img,
+                                     bool host_only, int64_t n_rec, int64_t B, const double* tterms, int64_t tt_rec_stride,
+                                     int64_t tt_inst_stride, const double* q, const double* x, const double* y,
+                                     int64_t y_stride, const double* tol, void* work, int64_t work_bytes, double* abs_max,
+                                     int32_t* abs_max_at, double* last, double* rms, double* viol_max, int32_t* viol_count,
+                                     int32_t* settled_at, void* stream)
+{
+    if (n_rec < 0 || B < 0) return fail(CLIK_EINVAL, "negative size");
+    if (n_rec == 0 || B == 0) return CLIK_OK;
+    if (!q) return fail(CLIK_EINVAL, "q must be a device pointer");
+    if (!abs_max || !abs_max_at || !last || !rms || !viol_max || !viol_count)
+        return fail(CLIK_EINVAL, "abs_max, abs_max_at, last, rms, viol_max and viol_count must be device pointers");
+    if ((tol == nullptr) != (settled_at == nullptr)) return fail(CLIK_EINVAL, "tol and settled_at go together");
+    if (!fn || !work_fn)
+        return fail(CLIK_EUNSUPPORTED, "no constraint-summary kernel instantiated for this skill (clik_*_attach_summary_kernel: "
+                                       "skills of the shape-specialised family have one)");
+    if (host_only)
+        return fail(CLIK_EINVAL, "this handle was created host-only (clik_*_create_host / CLIK_HOST_ONLY=1): host-side queries only");
+    if (!d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device");
+    if (n_rec > 0x7fffffffLL) return fail(CLIK_EINVAL, "more than 2^31 - 1 records");
+    if (S.d.n_x > 0 && !x) return fail(CLIK_EINVAL, "skill has virtual_var: x required");
+    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    if (y_stride < 0 || tt_rec_stride < 0 || tt_inst_stride < 0) return fail(CLIK_EINVAL, "negative stride");
+    if (S.d.n_tslots > 0 && !tterms) return fail(CLIK_EINVAL, "tterms (device) required: the skill has time slots");
+    const unsigned long long need = work_fn((long long)n_rec, (long long)B);
+    if (!work || work_bytes < 0 || (unsigned long long)work_bytes < need)
+        return fail(CLIK_EINVAL, "work must hold %llu bytes (clik_*_summary_work_bytes), got %lld", need, (long long)work_bytes);
+    const hipError_t er = fn(d_img, (long long)n_rec, (long long)B, S.d.n_tslots > 0 ? tterms : nullptr,
+                             (long long)tt_rec_stride, (long long)tt_inst_stride, q, x, y, (long long)y_stride, tol, work,
+                             (unsigned long long)work_bytes, abs_max, abs_max_at, last, rms, viol_max, viol_count, settled_at,
+                             (hipStream_t)stream);
+    if (er != hipSuccess) return hipfail(er, "constraint-summary kernel launch");
+    return CLIK_OK;
+}
+
+static int64_t summary_work_bytes_common(clik_summary_work_fn work_fn, int64_t n_rec, int64_t B)
+{
+    if (!work_fn || n_rec <= 0 || B <= 0) return 0;
+    return (int64_t)work_fn((long long)n_rec, (long long)B);
+}
+
+extern "C" int64_t clik_summary_chunk_length(int64_t n_rec, int64_t B)
+{
+    // (clik_summary.hpp: summary_chunk_length - restated, because this unit holds entry points and no kernel header;
+    // tests/test_summary_codegen.py holds this, the header's and jit.summary_chunk_length together)
+    const int64_t groups = B > 0 ? (B + 255) / 256 : 1;
+    const int64_t want = groups < 1024 ? 1024 / groups : 1;
+    const int64_t c = (n_rec + want - 1) / want;
+    return c > 8 ? c : 8;
+}
+
+extern "C" int clik_pinv_attach_summary_kernel(clik_pinv* h, void* constraint_summary_fn, void* work_bytes_fn)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    if (constraint_summary_fn) {
+        CLIK_NEEDS_DEVICE_HANDLE(h);
+        if (!work_bytes_fn) return fail(CLIK_EINVAL, "the summary kernel comes with its work-size function");
+        if (!h->jit_solve && !h->jit_rollout && !(h->kernel >= 0 && clik::pinv_kernel_is_static(h->kernel)))
+            return fail(CLIK_EUNSUPPORTED, "constraint summaries exist for skills a shape-specialised kernel serves");
+        if (!h->d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device: attach the kernel first");
+    }
+    h->summary_fn = (clik_summary_fn)constraint_summary_fn;
+    h->summary_work_fn = constraint_summary_fn ? (clik_summary_work_fn)work_bytes_fn : nullptr;
+    return CLIK_OK;
+}
+
+extern "C" int64_t clik_pinv_summary_work_bytes(const clik_pinv* h, int64_t n_rec, int64_t B)
+{
+    return h ? summary_work_bytes_common(h->summary_work_fn, n_rec, B) : 0;
+}
+
+extern "C" int clik_pinv_constraint_summary(const clik_pinv* h, int64_t n_rec, int64_t B, const double* tterms,
+                                            int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
+                                            const double* y, int64_t y_stride, const double* tol, void* work,
+                                            int64_t work_bytes, double* abs_max, int32_t* abs_max_at, double* last,
+                                            double* rms, double* viol_max, int32_t* viol_count, int32_t* settled_at,
+                                            void* stream)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    return constraint_summary_common(h->summary_fn, h->summary_work_fn, h->host, h->d_img, h->dev == nullptr, n_rec, B,
+                                     tterms, tt_rec_stride, tt_inst_stride, q, x, y, y_stride, tol, work, work_bytes, abs_max,
+                                     abs_max_at, last, rms, viol_max, viol_count, settled_at, stream);
+}
+
 static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
                                double max_speed, const TtSource& tts, double* q, double* x, const double* y,
                                double* dq, double* dx, int32_t* mode, void* stream, const clik::RollRec* rec)
@@ -1696,6 +1795,38 @@ extern "C" int clik_qp_constraint_values(const clik_qp* h, int64_t n_rec, int64_
     if (!h) return fail(CLIK_EINVAL, "null handle");
     return constraint_values_common(h->monitor_fn, h->host, h->d_img, h->dev == nullptr, n_rec, B, tterms, tt_rec_stride,
                                     tt_inst_stride, q, x, y, y_stride, e, J, et, stream);
+}
+
+extern "C" int clik_qp_attach_summary_kernel(clik_qp* h, void* constraint_summary_fn, void* work_bytes_fn)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    if (constraint_summary_fn) {
+        CLIK_NEEDS_DEVICE_HANDLE(h);
+        if (!work_bytes_fn) return fail(CLIK_EINVAL, "the summary kernel comes with its work-size function");
+        if (!qp_static_eligible(h->host)) return fail(CLIK_EUNSUPPORTED, "skill is outside the shape-specialised QP family");
+        int rc = qp_upload_image(h);
+        if (rc) return rc;
+    }
+    h->summary_fn = (clik_summary_fn)constraint_summary_fn;
+    h->summary_work_fn = constraint_summary_fn ? (clik_summary_work_fn)work_bytes_fn : nullptr;
+    return CLIK_OK;
+}
+
+extern "C" int64_t clik_qp_summary_work_bytes(const clik_qp* h, int64_t n_rec, int64_t B)
+{
+    return h ? summary_work_bytes_common(h->summary_work_fn, n_rec, B) : 0;
+}
+
+extern "C" int clik_qp_constraint_summary(const clik_qp* h, int64_t n_rec, int64_t B, const double* tterms,
+                                          int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
+                                          const double* y, int64_t y_stride, const double* tol, void* work,
+                                          int64_t work_bytes, double* abs_max, int32_t* abs_max_at, double* last, double* rms,
+                                          double* viol_max, int32_t* viol_count, int32_t* settled_at, void* stream)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    return constraint_summary_common(h->summary_fn, h->summary_work_fn, h->host, h->d_img, h->dev == nullptr, n_rec, B,
+                                     tterms, tt_rec_stride, tt_inst_stride, q, x, y, y_stride, tol, work, work_bytes, abs_max,
+                                     abs_max_at, last, rms, viol_max, viol_count, settled_at, stream);
 }
 
 static int qp_rollout_common(const clik_qp* hc, int64_t B, int32_t n_ticks, int32_t method, double dt,

@@ -424,6 +424,30 @@ int clik_pinv_constraint_values(const clik_pinv* h, int64_t n_rec, int64_t B, co
                                 const double* y, int64_t y_stride, double* e, double* J, double* et, void* stream);
 int clik_pinv_n_constraint_rows(const clik_pinv* h);
 
+/* Constraint summaries over a trajectory of states: per instance and constraint row what e did over the n_rec records,
+ * reduced inside the kernels that evaluate the constraints (casclik_amd/csrc/clik_summary.hpp, instantiated by
+ * casclik_amd/jit.py as clik_jit_constraint_summary / clik_jit_summary_work_bytes and attached here; NULL detaches) - e
+ * itself is never stored.  Inputs as clik_pinv_constraint_values.  Outputs, [B][M_tot] each, device memory:
+ *   abs_max = max_r |e[r]|, abs_max_at (int32) the first r that attains it, last = e[n_rec - 1], rms = sqrt(mean_r e[r]^2);
+ *   viol_max = max_r max(set_min - e, e - set_max, 0) and viol_count (int32) = records with a violation > 0 on the rows
+ *     of a SetConstraint, with the bounds the ticks use (image values or the expressions of attr_ext, evaluated at the
+ *     record's own t, q, x, y); 0 on the rows of every other class (a VelocitySetConstraint bounds a velocity);
+ *   settled_at (int32; NULL together with tol): the smallest r with d[r'] <= tol[row] for all r' >= r, n_rec when the
+ *     last record is outside; d = the violation on SetConstraint rows, |e| on the others; tol: [M_tot] doubles (device).
+ * The record axis is cut into chunks of clik_summary_chunk_length(n_rec, B) records - a function of the two sizes alone,
+ * so the result does not depend on the device - whose partials go through `work`, device memory of at least
+ * clik_pinv_summary_work_bytes(h, n_rec, B) bytes (0 without an attached kernel).  A row whose e is non-finite at any
+ * record reports NaN in its four floating-point outputs (its integer outputs are unspecified); no other row changes.
+ * CLIK_EUNSUPPORTED for a handle without an attached kernel; n_rec * B == 0: CLIK_OK, nothing is launched.            */
+int64_t clik_summary_chunk_length(int64_t n_rec, int64_t B);
+int clik_pinv_attach_summary_kernel(clik_pinv* h, void* constraint_summary_fn, void* work_bytes_fn);
+int64_t clik_pinv_summary_work_bytes(const clik_pinv* h, int64_t n_rec, int64_t B);
+int clik_pinv_constraint_summary(const clik_pinv* h, int64_t n_rec, int64_t B, const double* tterms,
+                                 int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
+                                 const double* y, int64_t y_stride, const double* tol, void* work, int64_t work_bytes,
+                                 double* abs_max, int32_t* abs_max_at, double* last, double* rms, double* viol_max,
+                                 int32_t* viol_count, int32_t* settled_at, void* stream);
+
 /* ---- ReactiveQPController path ----------------------------------------- */
 /* replaces setup_problem_functions()+setup_solver() (reactive_qp.py:248-298) */
 int clik_qp_create(const clik_skill_desc* desc, const clik_qp_opts* opts,
@@ -537,6 +561,16 @@ int clik_qp_constraint_values(const clik_qp* h, int64_t n_rec, int64_t B, const 
                               int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
                               const double* y, int64_t y_stride, double* e, double* J, double* et, void* stream);
 int clik_qp_n_constraint_rows(const clik_qp* h);
+
+/* Constraint summaries over a trajectory, as clik_pinv_attach_summary_kernel / clik_pinv_summary_work_bytes /
+ * clik_pinv_constraint_summary.                                                                                      */
+int clik_qp_attach_summary_kernel(clik_qp* h, void* constraint_summary_fn, void* work_bytes_fn);
+int64_t clik_qp_summary_work_bytes(const clik_qp* h, int64_t n_rec, int64_t B);
+int clik_qp_constraint_summary(const clik_qp* h, int64_t n_rec, int64_t B, const double* tterms,
+                               int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
+                               const double* y, int64_t y_stride, const double* tol, void* work, int64_t work_bytes,
+                               double* abs_max, int32_t* abs_max_at, double* last, double* rms, double* viol_max,
+                               int32_t* viol_count, int32_t* settled_at, void* stream);
 
 /* QP data only (H diag, A, lbA, ubA as the reference's H_func/A_func/Blb/Bub,
  * reactive_qp.py:283-298) for inspection and parity tests:

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Registers / scratch / occupancy of the value-specialised kernels of a BASELINE skill, from the compiler's resource
 remarks (no GPU needed).      python tools/kernel_resources.py [stack|pose|qp] [-DFLAG ...] [--asm=listing.s] [--obj=device.o]
---rec: the recording / per-tick-target rollouts of that skill (jit._VALUE_REC_TEMPLATE / _QP_VALUE_REC_TEMPLATE) instead."""
+--rec: the recording / per-tick-target rollouts of that skill (jit._VALUE_REC_TEMPLATE / _QP_VALUE_REC_TEMPLATE) instead.
+--summary: the two constraint-summary kernels of that skill (jit._SUMMARY_TEMPLATE: image-reading, no numbers compiled in)."""
 import os
 import subprocess
 import sys
@@ -49,6 +50,9 @@ else:
     ok, init = jit.shape_of(lib, cdesc, copts)
     template = jit._VALUE_REC_TEMPLATE if "--rec" in sys.argv else jit._VALUE_TEMPLATE
     words = jit.host_image_words(lib, "pinv", cdesc, copts)
+value_flag = ["-DCLIK_VALUE_KERNEL"]
+if "--summary" in sys.argv:
+    template, words, value_flag = jit._SUMMARY_TEMPLATE, [], []
 # (the scheduling strategy the shipped object is compiled with, casclik_amd/jit.py::sched_strategy - unless one is given)
 sched = jit.sched_strategy(template, init)
 if sched and not any("sched-strategy" in f for f in flags):
@@ -58,17 +62,17 @@ text = template.replace("%(nwords)d", str(len(words))).replace("%(words)s", ", "
 with tempfile.TemporaryDirectory() as tmp:
     src = os.path.join(tmp, "k.hip")
     open(src, "w").write(text)
-    out = subprocess.run([jit._hipcc()] + FLAGS + ["-DCLIK_VALUE_KERNEL"] + flags + ["-c", src, "-o", os.path.join(tmp, "k.o")],
+    out = subprocess.run([jit._hipcc()] + FLAGS + value_flag + flags + ["-c", src, "-o", os.path.join(tmp, "k.o")],
                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     if out.returncode != 0:
         print(out.stdout.decode()[-3000:])
         sys.exit(1)
     if asm_out:
         # (the listing tools/isa_count.py reads)
-        subprocess.run([jit._hipcc()] + [f for f in FLAGS if not f.startswith("-Rpass")] + ["-DCLIK_VALUE_KERNEL"] + flags +
+        subprocess.run([jit._hipcc()] + [f for f in FLAGS if not f.startswith("-Rpass")] + value_flag + flags +
                        ["-S", "--cuda-device-only", src, "-o", asm_out[0]], check=True)
     if obj_out:
-        subprocess.run([jit._hipcc()] + [f for f in FLAGS if not f.startswith("-Rpass")] + ["-DCLIK_VALUE_KERNEL"] + flags +
+        subprocess.run([jit._hipcc()] + [f for f in FLAGS if not f.startswith("-Rpass")] + value_flag + flags +
                        ["-c", "--cuda-device-only", "--no-gpu-bundle-output", src, "-o", obj_out[0]], check=True)
     for name, r in sorted(parse_resource_remarks(out.stdout.decode()).items()):
         short = name.split("(")[0][-70:]
