@@ -306,6 +306,20 @@ def summary_tolerances(tol, m_tot):
     return np.ascontiguousarray(arr)
 
 
+def rollout_summary_request(summary, summary_tol, n_ticks, m_tot):
+    """What ``rollout_batch(..., summary=, summary_tol=)`` asks for, checked on the host: ``(False, None)`` without
+    ``summary``, else ``(True, tol)`` with ``tol`` as ``summary_tolerances`` returns it (``[m_tot]`` float64 or None).
+    ValueError for a ``summary_tol`` without ``summary=True``, for a summary of no tick at all, and for what
+    ``summary_tolerances`` refuses (wrong length, negative, non-finite)."""
+    if not summary:
+        if summary_tol is not None:
+            raise ValueError("summary_tol needs summary=True")
+        return False, None
+    if int(n_ticks) < 1:
+        raise ValueError("summary=True needs at least one tick: a summary of no record does not exist")
+    return True, summary_tolerances(summary_tol, m_tot)
+
+
 def trajectory_rows(val, width, what, lead=None):
     """``val`` as ``(tensor-or-array [R, B, width], ndim)``: a ``[B, width]`` matrix (or what ``to_device_matrix`` takes
     for one) is one record, ``ndim`` 2; a ``[R, B, width]`` array or tensor stays as it is, ``ndim`` 3.  ``lead``: the
@@ -374,6 +388,7 @@ class BaseController(object):
         self._time_kernel = None
         self._monitor_kernel = None
         self._summary_kernel = None
+        self._rollsum_kernel = None
         return cdesc, copts
 
     def _want_jit(self):
@@ -590,13 +605,51 @@ class BaseController(object):
             raise ValueError("record_out needs record_every")
         return Q, X, Y, B, was_np, y_per_tick, rec
 
-    def _rollout_result(self, outs, rec, was_np):
-        """What a rollout returns: ``outs`` in the caller's container type and - when recording - the dict of records
-        as one more, last element."""
-        res = self._to_caller(outs, was_np)
-        if rec is None:
-            return res
-        return tuple(res) + ({k: (v.cpu().numpy() if was_np else v) for k, v in rec.items()},)
+    def _rollout_result(self, outs, rec, was_np, summ=None):
+        """What a rollout returns: ``outs`` in the caller's container type, then - when recording - the dict of records
+        and - with ``summary=True`` - the dict of summaries, each as one more, last element."""
+        res = tuple(self._to_caller(outs, was_np))
+        for extra in (rec, summ):
+            if extra is not None:
+                res += ({k: (v.cpu().numpy() if was_np else v) for k, v in extra.items()},)
+        return res
+
+    def _require_rollsum_kernel(self):
+        """The summarising rollout of this controller's skill (clik_rollout_summary.hpp), instantiated and attached at
+        the first ``rollout_batch(..., summary=True)`` and cached like every other instantiation.  Where no kernel may
+        be instantiated (``_want_jit``) or none can be, nothing is attached and the library refuses the call
+        (NotImplementedError); a skill whose block does not fit the LDS of a compute unit, or whose kernel would spill,
+        is refused here with the figure.  There is no chunked or host fallback."""
+        if self._rollsum_kernel is None and self._want_jit():
+            from .. import jit
+            d = self.descriptor
+            cdesc, copts = self._setup_c
+            with _torch().cuda.device(self._device):
+                if self._time_kind == "pinv":
+                    tag = jit.attach_rollsum(self._lib, self._handle, cdesc, copts, extern=d.extern_source())
+                else:
+                    tag = jit.attach_qp_rollsum(self._lib, self._handle, cdesc, extern=d.extern_source())
+            self._rollsum_kernel = tag or False
+
+    def _rollout_summary_out(self, tol, B):
+        """``(tol on the device | None, dict of the [B, M_tot] output tensors)`` of a summarising rollout: the keys,
+        dtypes and shapes of ``constraint_summary_batch`` (``settled_at`` only with a tolerance)."""
+        torch = _torch()
+        dev = self._device
+        m_tot = sum(int(t["m"]) for t in self.descriptor.tasks)
+        tol_dev = None if tol is None else torch.from_numpy(tol).to(dev)
+        f64 = lambda: torch.empty((B, m_tot), dtype=torch.float64, device=dev)      # noqa: E731
+        i32 = lambda: torch.empty((B, m_tot), dtype=torch.int32, device=dev)        # noqa: E731
+        out = {"abs_max": f64(), "abs_max_at": i32(), "last": f64(), "rms": f64(), "viol_max": f64(), "viol_count": i32()}
+        if tol_dev is not None:
+            out["settled_at"] = i32()
+        return tol_dev, out
+
+    @staticmethod
+    def _summary_ptrs(tol_dev, out):
+        """the trailing arguments of ``clik_*_rollout_batch_sum`` behind ``times``: tol and the seven outputs"""
+        return (ptr(tol_dev), ptr(out["abs_max"]), ptr(out["abs_max_at"]), ptr(out["last"]), ptr(out["rms"]),
+                ptr(out["viol_max"]), ptr(out["viol_count"]), ptr(out.get("settled_at")))
 
     def _require_rec_kernel(self, attach):
         """The recording / per-tick-target rollouts of this controller's skill, instantiated and attached at their

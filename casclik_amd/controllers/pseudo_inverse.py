@@ -19,7 +19,7 @@ from .. import _capi
 from .. import sym as cs
 from ..lowering import DYN_MAX_M
 from .base_controller import (BaseController, current_stream, ptr, to_device_matrix, check_out_tensor, scalar_of,
-                              _torch)
+                              _torch, rollout_summary_request)
 
 
 class PseudoInverseController(BaseController):
@@ -403,7 +403,8 @@ class PseudoInverseController(BaseController):
                 "keep": (Q, Y, tt)}
 
     def rollout_batch(self, time_vars, robot_var, input_var=None, dt=0.008,
-                      max_speed=0.0, virtual_var=None, method="euler", record_every=None, record_out=None):
+                      max_speed=0.0, virtual_var=None, method="euler", record_every=None, record_out=None,
+                      summary=False, summary_tol=None):
         """``len(time_vars)`` ticks of solve -> clamp(+-max_speed) -> integrate in one launch.
         ``method="euler"``: ``q += dq*dt``, the host loop of ur5_moe2016_example2.ipynb:537-545;
         ``method="rk4"``: classical Runge-Kutta with the controller as the right-hand side
@@ -418,6 +419,19 @@ class PseudoInverseController(BaseController):
         r is what a launch ending at tick ``(r + 1) * k`` returns.  ``record_out``: preallocated device tensors for
         some of them.  Both need a kernel instantiated for the skill (NotImplementedError otherwise).
 
+        Summary: ``summary=True`` appends one more, last element (behind the records when ``record_every`` is given as
+        well): the dict ``constraint_summary_batch`` returns - ``abs_max``, ``abs_max_at``, ``last``, ``rms``,
+        ``viol_max``, ``viol_count`` and, with ``summary_tol`` (a scalar or ``[M_tot]`` values, finite and >= 0),
+        ``settled_at``; ``[B, M_tot]`` each, rows as ``constraint_rows()`` - computed inside the rollout, with no record
+        of the trajectory.  Record r = 0 .. n_ticks - 1 is what tick r acts on: ``time_vars[r]``, the state the tick
+        starts from (record 0: ``robot_var``) and the target it reads; with ``"rk4"`` the tick's first stage.  The state
+        after the last tick is not a record (``constraint_values_batch`` on ``q_final`` gives its e).  It is what
+        ``constraint_summary_batch(time_vars, concat(q_0, rec["q"][:-1]), ...)`` gives on the records of the same launch
+        with ``record_every=1``, the same bits on every call and in every batch.  Such a launch uses the
+        lane-per-instance kernel at every batch size.  ValueError for ``summary_tol`` without ``summary``, a bad
+        ``summary_tol`` and an empty ``time_vars``; NotImplementedError when no kernel could be instantiated for the
+        skill, when its block does not fit the LDS of a compute unit or when its kernel would spill.
+
         With ``options["time_on_device"]`` the launch goes through ``clik_pinv_rollout_batch_dev``: the time terms of
         all ticks and stages are computed on the device from ``time_vars``, which may be a tensor on the controller's
         device (used in place, no host synchronisation)."""
@@ -431,6 +445,7 @@ class PseudoInverseController(BaseController):
             ttp = ptr(tt)
         else:
             n_ticks, stages, (tt, ttp) = self._rollout_times(time_vars, dt, method)
+        want_sum, tol = rollout_summary_request(summary, summary_tol, n_ticks, sum(int(t["m"]) for t in d.tasks))
         Q, X, Y, B, was_np, y_per_tick, rec = self._rollout_io(
             robot_var, virtual_var, input_var, n_ticks, record_every, record_out,
             [("q", d.n_q, "float64"), ("dq", d.n_q, "float64"), ("x", d.n_x, "float64"), ("dx", d.n_x, "float64"),
@@ -440,7 +455,18 @@ class PseudoInverseController(BaseController):
         mode = torch.empty((B,), dtype=torch.int32, device=dev)
         args = (self._handle, B, n_ticks, stages, float(dt), float(max_speed), ttp,
                 ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX), ptr(mode), current_stream(dev))
-        if rec is None and not y_per_tick:
+        summ = None
+        if want_sum:
+            # (records, per-tick targets and the summary in ONE launch of the summarising lane kernel)
+            tol_dev, summ = self._rollout_summary_out(tol, B)
+            self._require_rollsum_kernel()
+            r = rec or {}
+            with torch.cuda.device(dev):
+                rc = self._lib.clik_pinv_rollout_batch_sum(
+                    *(args[:6] + (None if dev_times else ttp,) + args[7:]), y_per_tick, int(record_every or 0),
+                    ptr(r.get("q")), ptr(r.get("dq")), ptr(r.get("x")), ptr(r.get("dx")), ptr(r.get("mode")),
+                    ttp if dev_times else None, *self._summary_ptrs(tol_dev, summ))
+        elif rec is None and not y_per_tick:
             with torch.cuda.device(dev):
                 rc = self._lib.clik_pinv_rollout_batch_dev(*args, 0, 0, None, None, None, None, None) if dev_times \
                     else self._lib.clik_pinv_rollout_batch_m(*args)
@@ -456,7 +482,7 @@ class PseudoInverseController(BaseController):
                     ptr(r.get("dx")), ptr(r.get("mode")))
         _capi.check(self._lib, rc)
         outs = (Q, X, dQ, dX, mode) if d.n_x > 0 else (Q, dQ, mode)
-        return self._rollout_result(outs, rec, was_np)
+        return self._rollout_result(outs, rec, was_np, summ)
 
     def solve(self, time_var, robot_var, virtual_var=None, input_var=None,
               warmstart_robot_vel_var=None, warmstart_virtual_vel_var=None,

@@ -88,6 +88,12 @@ typedef hipError_t (*clik_summary_fn)(const void*, long long, long long, const d
                                       hipStream_t);
 typedef unsigned long long (*clik_summary_work_fn)(long long, long long);
 
+// clik_jit_rollout_sum (casclik_amd/jit.py, clik_rollout_summary.hpp): the arguments of clik_jit_rollout_rec, then tol and
+// the seven outputs of the summary (all device)
+typedef hipError_t (*clik_rollsum_fn)(const clik::LaunchArgs*, const double*, int, double, double, long long, double*,
+                                      const double*, double*, int32_t*, hipStream_t, const double*, double*, int32_t*,
+                                      double*, double*, double*, int32_t*, int32_t*);
+
 typedef hipError_t (*clik_jit_value_fn)(const clik::LaunchArgs*, const TickArgs*, long long, const double*,
                                         const double*, double*, int32_t*, hipStream_t);
 
@@ -119,6 +125,8 @@ struct clik_pinv {
     // per-instance summaries of them over a trajectory (clik_pinv_attach_summary_kernel)
     clik_summary_fn summary_fn = nullptr;
     clik_summary_work_fn summary_work_fn = nullptr;
+    // the rollout that summarises them while it runs (clik_pinv_attach_rollout_summary_kernel)
+    clik_rollsum_fn rollsum_fn = nullptr;
 };
 
 // clik_jit_qp_rollout_rec / clik_jit_qp_value_rollout_rec: the rollouts' arguments and the RollRec
@@ -126,6 +134,10 @@ typedef hipError_t (*clik_qp_rec_fn)(const void*, const double*, int, double, do
                                      double*, double*, int32_t*, double*, double*, hipStream_t, int, const clik::RollRec*);
 typedef hipError_t (*clik_qp_value_rec_fn)(const double*, int, double, double, long long, double*, const double*, double*,
                                            double*, int32_t*, double*, double*, hipStream_t, int, const clik::RollRec*);
+// clik_jit_qp_rollout_sum: the arguments of clik_jit_qp_rollout_rec, then tol and the seven outputs of the summary
+typedef hipError_t (*clik_qp_rollsum_fn)(const void*, const double*, int, double, double, long long, double*, const double*,
+                                         double*, double*, int32_t*, double*, double*, hipStream_t, int, const clik::RollRec*,
+                                         const double*, double*, int32_t*, double*, double*, double*, int32_t*, int32_t*);
 
 struct clik_qp {
     DevSkill  host;
@@ -148,6 +160,7 @@ struct clik_qp {
     clik_monitor_fn monitor_fn = nullptr;    // constraint values over a trajectory (clik_qp_attach_monitor_kernel)
     clik_summary_fn summary_fn = nullptr;    // their per-instance summaries (clik_qp_attach_summary_kernel)
     clik_summary_work_fn summary_work_fn = nullptr;
+    clik_qp_rollsum_fn rollsum_fn = nullptr; // the rollout that summarises them (clik_qp_attach_rollout_summary_kernel)
     char      jit_name[64];
     // work area of the global-workspace kernels (clik_workspace.hpp): belongs to this handle, released by clik_qp_destroy
     clik::GwsOwner* gws;
@@ -1511,6 +1524,81 @@ static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, i
     return CLIK_OK;
 }
 
+// ---- rollouts that summarise their constraint values while they run (clik_*_rollout_batch_sum; the kernels:
+// clik_rollout_summary.hpp) --------------------------------------------------------------------------------------------
+// what both controllers check before anything else: sizes, the outputs, and where the tick times come from
+static int rollout_sum_checks(int64_t B, int32_t n_ticks, int32_t method, int n_tslots, const double* tterms,
+                              const double* times, const double* tol, const double* abs_max, const int32_t* abs_max_at,
+                              const double* last, const double* rms, const double* viol_max, const int32_t* viol_count,
+                              const int32_t* settled_at)
+{
+    if (B < 0) return fail(CLIK_EINVAL, "negative size");
+    if (n_ticks < 1) return fail(CLIK_EINVAL, "a summarising rollout needs at least one tick, got %d", n_ticks);
+    if (method != CLIK_INTEGRATE_EULER && method != CLIK_INTEGRATE_RK4) return fail(CLIK_EINVAL, "unknown integration method %d", method);
+    if (!abs_max || !abs_max_at || !last || !rms || !viol_max || !viol_count)
+        return fail(CLIK_EINVAL, "abs_max, abs_max_at, last, rms, viol_max and viol_count must be device pointers");
+    if ((tol == nullptr) != (settled_at == nullptr)) return fail(CLIK_EINVAL, "tol and settled_at go together");
+    if (tterms && times) return fail(CLIK_EINVAL, "tterms (host) and times (device) are alternatives: pass one");
+    if (n_tslots > 0 && !tterms && !times)
+        return fail(CLIK_EINVAL, "the skill has time slots: tterms (host) or times (device) required");
+    return CLIK_OK;
+}
+
+extern "C" int clik_pinv_attach_rollout_summary_kernel(clik_pinv* h, void* rollout_sum_fn)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    if (rollout_sum_fn) {
+        CLIK_NEEDS_DEVICE_HANDLE(h);
+        if (!h->jit_solve && !h->jit_rollout && !(h->kernel >= 0 && clik::pinv_kernel_is_static(h->kernel)))
+            return fail(CLIK_EUNSUPPORTED, "summarising rollouts exist for skills a shape-specialised kernel serves");
+        if (!h->d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device: attach the kernel first");
+    }
+    h->rollsum_fn = (clik_rollsum_fn)rollout_sum_fn;
+    return CLIK_OK;
+}
+
+extern "C" int clik_pinv_rollout_batch_sum(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
+                                           double max_speed, const double* tterms, double* q, double* x,
+                                           const double* y, double* dq, double* dx, int32_t* mode, void* stream,
+                                           int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
+                                           double* rec_x, double* rec_dx, int32_t* rec_mode, const double* times,
+                                           const double* tol, double* abs_max, int32_t* abs_max_at, double* last,
+                                           double* rms, double* viol_max, int32_t* viol_count, int32_t* settled_at)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    CLIK_NEEDS_DEVICE_HANDLE(h);
+    const DevSkill& S = h->host;
+    int rc = rollout_sum_checks(B, n_ticks, method, S.d.n_tslots, tterms, times, tol, abs_max, abs_max_at, last, rms,
+                                viol_max, viol_count, settled_at);
+    if (rc) return rc;
+    clik::RollRec rr;
+    rc = roll_rec_of(B, S.d.n_y, y_per_tick, record_every, rec_q, rec_dq, rec_x, rec_dx, nullptr, rec_mode, &rr);
+    if (rc) return rc;
+    if (B == 0) return CLIK_OK;
+    if (!h->rollsum_fn)
+        return fail(CLIK_EUNSUPPORTED, "no summarising rollout instantiated for this skill "
+                                       "(clik_pinv_attach_rollout_summary_kernel: skills of the shape-specialised family have one)");
+    if (S.d.n_x > 0 && (!x || !dx)) return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required");
+    // (as clik_pinv_rollout_batch_m: a skill whose rollouts are the built-in kernel's has no Runge-Kutta rollout, with or
+    // without a summary)
+    if (method == CLIK_INTEGRATE_RK4 && !h->jit_rollout && !(h->kernel >= 0 && clik::pinv_kernel_is_static(h->kernel)))
+        return fail(CLIK_EUNSUPPORTED, "the Runge-Kutta rollout needs a shape-specialised kernel (none attached for this skill)");
+    if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
+    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    const int stages = method == CLIK_INTEGRATE_RK4 ? 4 : 1;
+    double* d_tt = nullptr;
+    rc = rollout_tterms(times ? tt_device(times, h->time_fn) : tt_host(tterms), S.d.n_tslots, n_ticks, stages, dt,
+                        (hipStream_t)stream, &d_tt);
+    if (rc) return rc;
+    const clik::LaunchArgs la = {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->policy, x, dx, stages, nullptr,
+                                 &rr};
+    const hipError_t e = h->rollsum_fn(&la, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, mode, (hipStream_t)stream,
+                                       tol, abs_max, abs_max_at, last, rms, viol_max, viol_count, settled_at);
+    if (d_tt) (void)hipFreeAsync(d_tt, (hipStream_t)stream);
+    if (e != hipSuccess) return hipfail(e, "pinv summarising rollout launch");
+    return CLIK_OK;
+}
+
 // ---------------------------------------------------------------------------- QP
 static int qp_upload_image(clik_qp* h)
 {
@@ -1877,6 +1965,57 @@ static int qp_rollout_common(const clik_qp* hc, int64_t B, int32_t n_ticks, int3
                                                         (hipStream_t)stream, stages);
     if (d_tt) (void)hipFreeAsync(d_tt, (hipStream_t)stream);
     if (e != hipSuccess) return hipfail(e, "qp_rollout_kernel launch");
+    return CLIK_OK;
+}
+
+extern "C" int clik_qp_attach_rollout_summary_kernel(clik_qp* h, void* rollout_sum_fn)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    if (rollout_sum_fn) {
+        CLIK_NEEDS_DEVICE_HANDLE(h);
+        if (!qp_static_eligible(h->host)) return fail(CLIK_EUNSUPPORTED, "skill is outside the shape-specialised QP family");
+        int rc = qp_upload_image(h);
+        if (rc) return rc;
+    }
+    h->rollsum_fn = (clik_qp_rollsum_fn)rollout_sum_fn;
+    return CLIK_OK;
+}
+
+extern "C" int clik_qp_rollout_batch_sum(const clik_qp* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
+                                         double max_speed, const double* tterms, double* q, double* x, const double* y,
+                                         double* dq, double* dx, double* slack, int32_t* status, void* stream,
+                                         int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
+                                         double* rec_x, double* rec_dx, double* rec_slack, int32_t* rec_status,
+                                         const double* times, const double* tol, double* abs_max, int32_t* abs_max_at,
+                                         double* last, double* rms, double* viol_max, int32_t* viol_count,
+                                         int32_t* settled_at)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    CLIK_NEEDS_DEVICE_HANDLE(h);
+    const DevSkill& S = h->host;
+    int rc = rollout_sum_checks(B, n_ticks, method, S.d.n_tslots, tterms, times, tol, abs_max, abs_max_at, last, rms,
+                                viol_max, viol_count, settled_at);
+    if (rc) return rc;
+    clik::RollRec rr;
+    rc = roll_rec_of(B, S.d.n_y, y_per_tick, record_every, rec_q, rec_dq, rec_x, rec_dx, rec_slack, rec_status, &rr);
+    if (rc) return rc;
+    if (B == 0) return CLIK_OK;
+    if (!h->rollsum_fn || !h->d_img)
+        return fail(CLIK_EUNSUPPORTED, "no summarising rollout instantiated for this skill "
+                                       "(clik_qp_attach_rollout_summary_kernel: skills of the shape-specialised family have one)");
+    if (S.d.n_x > 0 && (!x || !dx)) return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required");
+    if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
+    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    const int stages = method == CLIK_INTEGRATE_RK4 ? 4 : 1;
+    double* d_tt = nullptr;
+    rc = rollout_tterms(times ? tt_device(times, h->time_fn) : tt_host(tterms), S.d.n_tslots, n_ticks, stages, dt,
+                        (hipStream_t)stream, &d_tt);
+    if (rc) return rc;
+    const hipError_t e = h->rollsum_fn(h->d_img, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, slack, status, x, dx,
+                                       (hipStream_t)stream, stages, &rr, tol, abs_max, abs_max_at, last, rms, viol_max,
+                                       viol_count, settled_at);
+    if (d_tt) (void)hipFreeAsync(d_tt, (hipStream_t)stream);
+    if (e != hipSuccess) return hipfail(e, "qp summarising rollout launch");
     return CLIK_OK;
 }
 

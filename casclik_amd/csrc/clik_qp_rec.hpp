@@ -5,6 +5,8 @@
 // for a kernel depends on what else its translation unit declares - with these templates declared next to them, the rollouts
 // that record nothing fused their multiply-adds in another order, and their results are pinned to the tick kernels' (the
 // smoke test: q after one tick to 1e-12).
+// (qp_rollout_static_body is written out once more, with a summary of every tick's state, in clik_rollout_summary.hpp: a change of
+// the loop here belongs there too.)
 #pragma once
 #include "clik_qp_static.hpp"
 namespace clik {

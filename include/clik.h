@@ -32,7 +32,8 @@
  *     Consequence: a tick is graph-capturable; a rollout is graph-capturable only
  *     for a skill without time slots (n_tslots == 0: nothing is staged) - the
  *     time-slot records of a rollout are consumed at call time, not at replay.
- *     The clik_*_rollout_batch_dev calls are the exception: they take the tick
+ *     The clik_*_rollout_batch_dev calls (and clik_*_rollout_batch_sum given
+ *     `times`) are the exception: they take the tick
  *     times as a DEVICE array and fill the time-slot records with the skill's
  *     time kernel (clik_*_attach_time_kernel) on the caller's stream, so they
  *     consume nothing on the host at call time and use no pinned slot.
@@ -448,6 +449,32 @@ int clik_pinv_constraint_summary(const clik_pinv* h, int64_t n_rec, int64_t B, c
                                  double* abs_max, int32_t* abs_max_at, double* last, double* rms, double* viol_max,
                                  int32_t* viol_count, int32_t* settled_at, void* stream);
 
+/* A rollout that summarises its own constraint values while it runs: clik_pinv_rollout_batch_rec / _dev and
+ * clik_pinv_constraint_summary in ONE launch, with no record of the trajectory in between (the kernels:
+ * casclik_amd/csrc/clik_rollout_summary.hpp, instantiated by casclik_amd/jit.py as clik_jit_rollout_sum and attached here;
+ * NULL detaches).  Record r = 0 .. n_ticks - 1 of the summary is what tick r acts on: the tick's time, the state it starts
+ * from (record 0: the caller's q / x) and the target it reads (y_per_tick included); with Runge-Kutta the tick's first
+ * stage.  The state after the last tick is not a record.  The arguments of clik_pinv_rollout_batch_rec come first and mean
+ * what they mean there (records and per-tick targets combine with the summary in the same launch); then
+ *   times: the tick times [n_ticks] on the device in place of the host table tterms, as clik_pinv_rollout_batch_dev -
+ *     exactly one of tterms and times for a skill with time slots (CLIK_EINVAL otherwise), both may be NULL without;
+ *   tol [M_tot] (device; NULL together with settled_at) and the seven outputs of clik_pinv_constraint_summary, [B][M_tot]
+ *     each, with n_rec = n_ticks: same meaning, same bounds rule, same rule for non-finite values.
+ * One lane owns one instance and folds tick after tick in order: no chunks, no work area, the same bits on every call and
+ * in every batch.  The lane-per-instance kernel serves every batch size.  n_ticks < 1: CLIK_EINVAL; B == 0: CLIK_OK,
+ * nothing is launched; CLIK_EUNSUPPORTED for a handle without an attached kernel (one served by the built-in dynamic-shape
+ * kernel has none), and for CLIK_INTEGRATE_RK4 on a handle whose plain rollouts have no Runge-Kutta form
+ * (clik_pinv_rollout_batch_m refuses it the same way).                                                                */
+int clik_pinv_attach_rollout_summary_kernel(clik_pinv* h, void* rollout_sum_fn);
+int clik_pinv_rollout_batch_sum(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method,
+                                double dt, double max_speed, const double* tterms,
+                                double* q, double* x, const double* y, double* dq,
+                                double* dx, int32_t* mode, void* stream,
+                                int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
+                                double* rec_x, double* rec_dx, int32_t* rec_mode,
+                                const double* times, const double* tol, double* abs_max, int32_t* abs_max_at,
+                                double* last, double* rms, double* viol_max, int32_t* viol_count, int32_t* settled_at);
+
 /* ---- ReactiveQPController path ----------------------------------------- */
 /* replaces setup_problem_functions()+setup_solver() (reactive_qp.py:248-298) */
 int clik_qp_create(const clik_skill_desc* desc, const clik_qp_opts* opts,
@@ -571,6 +598,18 @@ int clik_qp_constraint_summary(const clik_qp* h, int64_t n_rec, int64_t B, const
                                const double* y, int64_t y_stride, const double* tol, void* work, int64_t work_bytes,
                                double* abs_max, int32_t* abs_max_at, double* last, double* rms, double* viol_max,
                                int32_t* viol_count, int32_t* settled_at, void* stream);
+
+/* The summarising rollout, as clik_pinv_attach_rollout_summary_kernel / clik_pinv_rollout_batch_sum: the arguments of
+ * clik_qp_rollout_batch_rec, then times, tol and the seven outputs.  A tick that is infeasible leaves the state where it
+ * was, and the next record is that same state.                                                                        */
+int clik_qp_attach_rollout_summary_kernel(clik_qp* h, void* rollout_sum_fn);
+int clik_qp_rollout_batch_sum(const clik_qp* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
+                              double max_speed, const double* tterms, double* q, double* x, const double* y,
+                              double* dq, double* dx, double* slack, int32_t* status, void* stream,
+                              int32_t y_per_tick, int32_t record_every, double* rec_q, double* rec_dq,
+                              double* rec_x, double* rec_dx, double* rec_slack, int32_t* rec_status,
+                              const double* times, const double* tol, double* abs_max, int32_t* abs_max_at,
+                              double* last, double* rms, double* viol_max, int32_t* viol_count, int32_t* settled_at);
 
 /* QP data only (H diag, A, lbA, ubA as the reference's H_func/A_func/Blb/Bub,
  * reactive_qp.py:283-298) for inspection and parity tests:
