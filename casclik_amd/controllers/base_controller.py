@@ -345,8 +345,8 @@ class BaseController(object):
     other helper here works from."""
     controller_type = "BaseController"
     _create_fn = _destroy_fn = None
-    _time_kind = None           # "pinv" | "qp": whose clik_*_attach_time_kernel / clik_*_time_terms the handle takes
-    _time_kernel = None         # cache tag of the attached time kernel (options["time_on_device"]), or None
+    _kind = None                # "pinv" | "qp": whose clik_<kind>_* entry points and jit.UNITS entries the handle takes
+    _kernels = {}               # on-demand kernels asked for so far, what -> cache tag | False (``_create_handle`` resets it)
 
     def __repr__(self):
         return self.controller_type + "<" + self.skill_spec.label + ">"
@@ -383,12 +383,8 @@ class BaseController(object):
             rc = getattr(self._lib, self._create_fn)(C.byref(cdesc), C.byref(copts), C.byref(handle))
         _capi.check(self._lib, rc)
         self._handle = handle
-        self._setup_c = (cdesc, copts)      # (the recording rollouts are instantiated later, at their first use)
-        self._rec_kernel = None
-        self._time_kernel = None
-        self._monitor_kernel = None
-        self._summary_kernel = None
-        self._rollsum_kernel = None
+        self._setup_c = (cdesc, copts)      # (the on-demand kernels are instantiated later, at their first use)
+        self._kernels = {}
         return cdesc, copts
 
     def _want_jit(self):
@@ -429,20 +425,42 @@ class BaseController(object):
         the slot trees on the host once per time stamp.  A skill without time slots builds nothing and behaves as
         without the option.  NotImplementedError when the kernel cannot be had (no compiler and nothing cached,
         ``function_opts["jit"]`` false): there is no silent return to the host path."""
-        self._time_kernel = None
+        self._kernels.pop("time", None)
         if not self.options.get("time_on_device", False) or self.descriptor.n_tslots == 0:
             return
         tag = None
         if self._want_jit():
-            from .. import jit
+            from .. import codegen, jit
             tag = self._attach_or_warn(
-                lambda: jit.attach_time(self._lib, self._handle, self.descriptor, self._time_kind),
+                lambda: jit.attach_unit(self._lib, self._handle, self._kind, "time", None, None,
+                                        extern=codegen.emit_time_slots(self.descriptor)),
                 "the time kernel could not be built", 400)
         if not tag:
             raise NotImplementedError(
                 "options['time_on_device'] is set, but no time kernel could be instantiated for the skill's %d time "
                 "slot(s) (jit disabled, or hipcc missing and nothing cached)" % self.descriptor.n_tslots)
-        self._time_kernel = tag
+        self._kernels["time"] = tag
+
+    @property
+    def _time_kernel(self):
+        """cache tag of the attached time kernel (``options["time_on_device"]``), or None"""
+        return self._kernels.get("time")
+
+    def _require_kernel(self, what):
+        """An on-demand kernel of this controller's skill (``jit.UNITS``: "rec" the recording / per-tick-target rollouts,
+        "monitor" the constraint values, "summary" the constraint summaries, "rollsum" the summarising rollout),
+        instantiated and attached at its first use and cached like every other instantiation.  Where no kernel may be
+        instantiated (``_want_jit``) or none can be - a skill outside the shape-specialised family - nothing is attached
+        and the library refuses the call (NotImplementedError): there is no chunked or host fallback.  A skill whose
+        summary or summarising rollout does not fit the LDS of a compute unit, or would spill, is refused here with the
+        figure."""
+        if self._kernels.get(what) is None and self._want_jit():
+            from .. import jit
+            cdesc, copts = self._setup_c
+            with _torch().cuda.device(self._device):
+                tag = jit.attach_unit(self._lib, self._handle, self._kind, what, cdesc, copts,
+                                      extern=self.descriptor.extern_source(), values=bool(self.value_kernel))
+            self._kernels[what] = tag or False
 
     def _device_times(self, time_vars):
         """times as a flat contiguous float64 tensor on the controller's device (one that already is, is used in
@@ -471,7 +489,7 @@ class BaseController(object):
         out = torch.empty((T.numel() * stages, 2 * n_ts), dtype=torch.float64, device=dev)
         if n_ts and T.numel():
             with torch.cuda.device(dev):
-                rc = getattr(self._lib, "clik_%s_time_terms" % self._time_kind)(
+                rc = getattr(self._lib, "clik_%s_time_terms" % self._kind)(
                     self._handle, T.numel(), ptr(T), stages, float(dt), ptr(out), current_stream(dev))
             _capi.check(self._lib, rc)
         return out if was_tensor else out.cpu().numpy()
@@ -614,26 +632,9 @@ class BaseController(object):
                 res += ({k: (v.cpu().numpy() if was_np else v) for k, v in extra.items()},)
         return res
 
-    def _require_rollsum_kernel(self):
-        """The summarising rollout of this controller's skill (clik_rollout_summary.hpp), instantiated and attached at
-        the first ``rollout_batch(..., summary=True)`` and cached like every other instantiation.  Where no kernel may
-        be instantiated (``_want_jit``) or none can be, nothing is attached and the library refuses the call
-        (NotImplementedError); a skill whose block does not fit the LDS of a compute unit, or whose kernel would spill,
-        is refused here with the figure.  There is no chunked or host fallback."""
-        if self._rollsum_kernel is None and self._want_jit():
-            from .. import jit
-            d = self.descriptor
-            cdesc, copts = self._setup_c
-            with _torch().cuda.device(self._device):
-                if self._time_kind == "pinv":
-                    tag = jit.attach_rollsum(self._lib, self._handle, cdesc, copts, extern=d.extern_source())
-                else:
-                    tag = jit.attach_qp_rollsum(self._lib, self._handle, cdesc, extern=d.extern_source())
-            self._rollsum_kernel = tag or False
-
-    def _rollout_summary_out(self, tol, B):
-        """``(tol on the device | None, dict of the [B, M_tot] output tensors)`` of a summarising rollout: the keys,
-        dtypes and shapes of ``constraint_summary_batch`` (``settled_at`` only with a tolerance)."""
+    def _summary_out(self, tol, B):
+        """``(tol on the device | None, dict of the [B, M_tot] output tensors)`` of ``constraint_summary_batch`` and of a
+        summarising rollout; ``tol`` as ``summary_tolerances`` returns it (``settled_at`` only with a tolerance)."""
         torch = _torch()
         dev = self._device
         m_tot = sum(int(t["m"]) for t in self.descriptor.tasks)
@@ -647,18 +648,9 @@ class BaseController(object):
 
     @staticmethod
     def _summary_ptrs(tol_dev, out):
-        """the trailing arguments of ``clik_*_rollout_batch_sum`` behind ``times``: tol and the seven outputs"""
+        """tol and the seven outputs as ``clik_*_constraint_summary`` and ``clik_*_rollout_batch_sum`` take them"""
         return (ptr(tol_dev), ptr(out["abs_max"]), ptr(out["abs_max_at"]), ptr(out["last"]), ptr(out["rms"]),
                 ptr(out["viol_max"]), ptr(out["viol_count"]), ptr(out.get("settled_at")))
-
-    def _require_rec_kernel(self, attach):
-        """The recording / per-tick-target rollouts of this controller's skill, instantiated and attached at their
-        first use (``attach()``: the controller's ``jit.attach_rec`` / ``attach_qp_rec`` call) and cached like every
-        other instantiation.  Where no kernel may be instantiated (``_want_jit``) or none can be, nothing is attached
-        and the library refuses the call: there is no chunked fallback."""
-        if self._rec_kernel is None and self._want_jit():
-            with _torch().cuda.device(self._device):
-                self._rec_kernel = attach() or False
 
     # -- constraint values over a trajectory --------------------------------------------------------------------
     def constraint_rows(self):
@@ -667,22 +659,6 @@ class BaseController(object):
         if getattr(self, "descriptor", None) is None or getattr(self, "_handle", None) is None:
             raise RuntimeError("call setup_problem_functions() / setup_solver() first")
         return constraint_row_slices(self.descriptor)
-
-    def _require_monitor_kernel(self):
-        """The constraint-value kernel of this controller's skill (clik_monitor.hpp), instantiated and attached at the
-        first ``constraint_values_batch`` and cached like every other instantiation.  Where no kernel may be
-        instantiated (``_want_jit``) or none can be - a skill outside the shape-specialised family - nothing is
-        attached and the library refuses the call (NotImplementedError): there is no host fallback."""
-        if self._monitor_kernel is None and self._want_jit():
-            from .. import jit
-            d = self.descriptor
-            cdesc, copts = self._setup_c
-            with _torch().cuda.device(self._device):
-                if self._time_kind == "pinv":
-                    tag = jit.attach_monitor(self._lib, self._handle, cdesc, copts, extern=d.extern_source())
-                else:
-                    tag = jit.attach_qp_monitor(self._lib, self._handle, cdesc, extern=d.extern_source())
-            self._monitor_kernel = tag or False
 
     def _trajectory_tensor(self, val, width, what, lead=None, shared=False):
         """``(T [R, B, width], ndim, was_np)`` of one argument of ``constraint_values_batch``: contiguous float64 on the
@@ -700,6 +676,26 @@ class BaseController(object):
         if isinstance(val, torch.Tensor):
             return val.to(device=self._device, dtype=torch.float64).contiguous(), 3, False
         return torch.from_numpy(np.ascontiguousarray(np.asarray(val, dtype=np.float64))).to(self._device), 3, True
+
+    def _trajectory_inputs(self, robot_var, virtual_var, input_var):
+        """What ``constraint_values_batch`` and ``constraint_summary_batch`` open with: ``(Q [R, B, n_q], X | None, Y |
+        None, y_stride, R, B, ndim, was_np)`` - the states as ``_trajectory_tensor`` gives them, ``y_stride`` the record
+        stride of ``Y`` (0: one block shared by all records), ``ndim`` and ``was_np`` those of ``robot_var``."""
+        d = self.descriptor
+        Q, ndim, was_np = self._trajectory_tensor(robot_var, d.n_q, "robot_var")
+        R, B = int(Q.shape[0]), int(Q.shape[1])
+        X = Y = None
+        y_stride = 0
+        if d.n_x > 0:
+            if virtual_var is None:
+                raise ValueError("skill has virtual_var: pass virtual_var")
+            X = self._trajectory_tensor(virtual_var, d.n_x, "virtual_var", (R, B))[0]
+        if d.n_y > 0:
+            if input_var is None:
+                raise ValueError("skill has input_var: pass input_var")
+            Y, y_ndim, _ = self._trajectory_tensor(input_var, d.n_y, "input_var", (R, B), shared=True)
+            y_stride = B * d.n_y if y_ndim == 3 else 0
+        return Q, X, Y, y_stride, R, B, ndim, was_np
 
     def _monitor_time_table(self, time_var, R, B, ndim):
         """``(T | None, tt_rec_stride, tt_inst_stride)`` of a ``constraint_values_batch`` call: the device table of
@@ -753,19 +749,7 @@ class BaseController(object):
         self._require_handle()
         torch = _torch()
         d, dev = self.descriptor, self._device
-        Q, ndim, was_np = self._trajectory_tensor(robot_var, d.n_q, "robot_var")
-        R, B = int(Q.shape[0]), int(Q.shape[1])
-        X = Y = None
-        y_stride = 0
-        if d.n_x > 0:
-            if virtual_var is None:
-                raise ValueError("skill has virtual_var: pass virtual_var")
-            X = self._trajectory_tensor(virtual_var, d.n_x, "virtual_var", (R, B))[0]
-        if d.n_y > 0:
-            if input_var is None:
-                raise ValueError("skill has input_var: pass input_var")
-            Y, y_ndim, _ = self._trajectory_tensor(input_var, d.n_y, "input_var", (R, B), shared=True)
-            y_stride = B * d.n_y if y_ndim == 3 else 0
+        Q, X, Y, y_stride, R, B, ndim, was_np = self._trajectory_inputs(robot_var, virtual_var, input_var)
         T, tt_rec, tt_inst = self._monitor_time_table(time_var, R, B, ndim)
         m_tot, n = sum(int(t["m"]) for t in d.tasks), d.n_q + d.n_x
         lead = (R, B) if ndim == 3 else (B,)
@@ -773,9 +757,9 @@ class BaseController(object):
         E = out if out is not None else torch.empty(lead + (m_tot,), dtype=torch.float64, device=dev)
         J = torch.empty(lead + (m_tot, n), dtype=torch.float64, device=dev) if jacobian else None
         Et = torch.empty(lead + (m_tot,), dtype=torch.float64, device=dev) if jacobian else None
-        self._require_monitor_kernel()
+        self._require_kernel("monitor")
         with torch.cuda.device(dev):
-            rc = getattr(self._lib, "clik_%s_constraint_values" % self._time_kind)(
+            rc = getattr(self._lib, "clik_%s_constraint_values" % self._kind)(
                 self._handle, R, B, ptr(T), tt_rec, tt_inst, ptr(Q), ptr(X), ptr(Y), y_stride, ptr(E), ptr(J), ptr(Et),
                 current_stream(dev))
         _capi.check(self._lib, rc)
@@ -796,22 +780,6 @@ class BaseController(object):
         return {label: cs.DM(e[sl].reshape(-1, 1)) for label, sl in self.constraint_rows().items()}
 
     # -- constraint summaries over a trajectory -----------------------------------------------------------------
-    def _require_summary_kernel(self):
-        """The constraint-summary kernels of this controller's skill (clik_summary.hpp), instantiated and attached at
-        the first ``constraint_summary_batch`` and cached like every other instantiation; as
-        ``_require_monitor_kernel``: where none may or can be instantiated, nothing is attached and the library refuses
-        the call (NotImplementedError)."""
-        if self._summary_kernel is None and self._want_jit():
-            from .. import jit
-            d = self.descriptor
-            cdesc, copts = self._setup_c
-            with _torch().cuda.device(self._device):
-                if self._time_kind == "pinv":
-                    tag = jit.attach_summary(self._lib, self._handle, cdesc, copts, extern=d.extern_source())
-                else:
-                    tag = jit.attach_qp_summary(self._lib, self._handle, cdesc, extern=d.extern_source())
-            self._summary_kernel = tag or False
-
     def constraint_summary_batch(self, time_var, robot_var, virtual_var=None, input_var=None, tol=None):
         """What the skill's constraint expressions did over a whole trajectory of states, per instance and per
         constraint row: the reduction over the record axis of what ``constraint_values_batch`` returns, done inside the
@@ -843,39 +811,19 @@ class BaseController(object):
         skill: there is no host fallback."""
         self._require_handle()
         torch = _torch()
-        d, dev = self.descriptor, self._device
-        Q, ndim, was_np = self._trajectory_tensor(robot_var, d.n_q, "robot_var")
-        R, B = int(Q.shape[0]), int(Q.shape[1])
-        X = Y = None
-        y_stride = 0
-        if d.n_x > 0:
-            if virtual_var is None:
-                raise ValueError("skill has virtual_var: pass virtual_var")
-            X = self._trajectory_tensor(virtual_var, d.n_x, "virtual_var", (R, B))[0]
-        if d.n_y > 0:
-            if input_var is None:
-                raise ValueError("skill has input_var: pass input_var")
-            Y, y_ndim, _ = self._trajectory_tensor(input_var, d.n_y, "input_var", (R, B), shared=True)
-            y_stride = B * d.n_y if y_ndim == 3 else 0
+        dev = self._device
+        Q, X, Y, y_stride, R, B, _, was_np = self._trajectory_inputs(robot_var, virtual_var, input_var)
         # (one stamp, or one per record: a [B, n_q] robot_var is one record, not B stamps as in constraint_values_batch)
         T, tt_rec, tt_inst = self._monitor_time_table(time_var, R, B, 3)
-        m_tot = sum(int(t["m"]) for t in d.tasks)
-        tol_dev = summary_tolerances(tol, m_tot)
-        if tol_dev is not None:
-            tol_dev = torch.from_numpy(tol_dev).to(dev)
-        f64 = lambda: torch.empty((B, m_tot), dtype=torch.float64, device=dev)      # noqa: E731
-        i32 = lambda: torch.empty((B, m_tot), dtype=torch.int32, device=dev)        # noqa: E731
-        out = {"abs_max": f64(), "abs_max_at": i32(), "last": f64(), "rms": f64(), "viol_max": f64(), "viol_count": i32()}
-        if tol_dev is not None:
-            out["settled_at"] = i32()
-        self._require_summary_kernel()
+        tol_dev, out = self._summary_out(summary_tolerances(tol, sum(int(t["m"]) for t in self.descriptor.tasks)), B)
+        self._require_kernel("summary")
         with torch.cuda.device(dev):
-            n_work = int(getattr(self._lib, "clik_%s_summary_work_bytes" % self._time_kind)(self._handle, R, B))
+            n_work = int(getattr(self._lib, "clik_%s_summary_work_bytes" % self._kind)(self._handle, R, B))
             work = torch.empty(max(n_work, 8) // 8 + 1, dtype=torch.float64, device=dev)
-            rc = getattr(self._lib, "clik_%s_constraint_summary" % self._time_kind)(
-                self._handle, R, B, ptr(T), tt_rec, tt_inst, ptr(Q), ptr(X), ptr(Y), y_stride, ptr(tol_dev), ptr(work),
-                work.numel() * 8, ptr(out["abs_max"]), ptr(out["abs_max_at"]), ptr(out["last"]), ptr(out["rms"]),
-                ptr(out["viol_max"]), ptr(out["viol_count"]), ptr(out.get("settled_at")), current_stream(dev))
+            tol_ptr, *out_ptrs = self._summary_ptrs(tol_dev, out)
+            rc = getattr(self._lib, "clik_%s_constraint_summary" % self._kind)(
+                self._handle, R, B, ptr(T), tt_rec, tt_inst, ptr(Q), ptr(X), ptr(Y), y_stride, tol_ptr, ptr(work),
+                work.numel() * 8, *out_ptrs, current_stream(dev))
         _capi.check(self._lib, rc)
         return {k: v.cpu().numpy() for k, v in out.items()} if was_np else out
 

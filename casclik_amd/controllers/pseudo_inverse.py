@@ -37,7 +37,7 @@ class PseudoInverseController(BaseController):
     skill's time slots with a generated device kernel - rollouts and per-instance-time ticks then take their times
     from the device, see ``time_terms_batch``)"""
     _create_fn, _destroy_fn = "clik_pinv_create", "clik_pinv_destroy"
-    _time_kind = "pinv"
+    _kind = "pinv"
 
     def __init__(self, skill_spec, options=None):
         self._handle = None
@@ -458,8 +458,8 @@ class PseudoInverseController(BaseController):
         summ = None
         if want_sum:
             # (records, per-tick targets and the summary in ONE launch of the summarising lane kernel)
-            tol_dev, summ = self._rollout_summary_out(tol, B)
-            self._require_rollsum_kernel()
+            tol_dev, summ = self._summary_out(tol, B)
+            self._require_kernel("rollsum")
             r = rec or {}
             with torch.cuda.device(dev):
                 rc = self._lib.clik_pinv_rollout_batch_sum(
@@ -471,10 +471,7 @@ class PseudoInverseController(BaseController):
                 rc = self._lib.clik_pinv_rollout_batch_dev(*args, 0, 0, None, None, None, None, None) if dev_times \
                     else self._lib.clik_pinv_rollout_batch_m(*args)
         else:
-            from .. import jit
-            cdesc, copts = self._setup_c
-            self._require_rec_kernel(lambda: jit.attach_rec(self._lib, self._handle, cdesc, copts,
-                                                            extern=d.extern_source(), values=bool(self.value_kernel)))
+            self._require_kernel("rec")
             r = rec or {}
             with torch.cuda.device(dev):
                 rc = (self._lib.clik_pinv_rollout_batch_dev if dev_times else self._lib.clik_pinv_rollout_batch_rec)(

@@ -67,7 +67,7 @@ class ReactiveQPController(BaseController):
     their times from the device, see ``time_terms_batch``."""
     weight_shifter = 0.001   # mu of the eTaSL paper (reactive_qp.py:44)
     _create_fn, _destroy_fn = "clik_qp_create", "clik_qp_destroy"
-    _time_kind = "qp"
+    _kind = "qp"
 
     def __init__(self, skill_spec, robot_var_weights=None,
                  virtual_var_weights=None, slack_var_weights=None, options=None):
@@ -651,8 +651,8 @@ class ReactiveQPController(BaseController):
         summ = None
         if want_sum:
             # (records, per-tick targets and the summary in ONE launch of the summarising kernel)
-            tol_dev, summ = self._rollout_summary_out(tol, B)
-            self._require_rollsum_kernel()
+            tol_dev, summ = self._summary_out(tol, B)
+            self._require_kernel("rollsum")
             r = rec or {}
             with torch.cuda.device(dev):
                 rc = self._lib.clik_qp_rollout_batch_sum(
@@ -664,9 +664,7 @@ class ReactiveQPController(BaseController):
                 rc = self._lib.clik_qp_rollout_batch_dev(*args, 0, 0, None, None, None, None, None, None) if dev_times \
                     else self._lib.clik_qp_rollout_batch_m(*args)
         else:
-            from .. import jit
-            self._require_rec_kernel(lambda: jit.attach_qp_rec(self._lib, self._handle, self._setup_c[0],
-                                                               extern=d.extern_source(), values=bool(self.value_kernel)))
+            self._require_kernel("rec")
             r = rec or {}
             with torch.cuda.device(dev):
                 rc = (self._lib.clik_qp_rollout_batch_dev if dev_times else self._lib.clik_qp_rollout_batch_rec)(

@@ -1272,6 +1272,13 @@ static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, i
                                double max_speed, const TtSource& tts, double* q, double* x, const double* y,
                                double* dq, double* dx, int32_t* mode, void* stream, const clik::RollRec* rec);
 
+// do shape-specialised kernels serve the rollouts of this handle: an attached one or one of the table's?  (The ticks ask
+// for jit_solve instead, see pinv_solve_common: a skill with many SetConstraints has that and no jit_rollout.)
+static bool pinv_shape_served(const clik_pinv* h)
+{
+    return h->jit_rollout || (h->kernel >= 0 && clik::pinv_kernel_is_static(h->kernel));
+}
+
 extern "C" int clik_pinv_rollout_batch_m(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
                                          double max_speed, const double* tterms, double* q, double* x,
                                          const double* y, double* dq, double* dx, int32_t* mode, void* stream)
@@ -1309,13 +1316,23 @@ extern "C" int clik_pinv_rollout_batch_dev(const clik_pinv* h, int64_t B, int32_
     return pinv_rollout_common(h, B, n_ticks, method, dt, max_speed, tts, q, x, y, dq, dx, mode, stream, &rr);
 }
 
+// what the four clik_pinv_attach_*_kernel of the on-demand kernels check before they store a pointer: a shape-specialised
+// kernel serves this handle (`refusal` says what exists only then), and its image is on the device
+static int pinv_attach_checks(const clik_pinv* h, const char* refusal)
+{
+    if (!h->jit_solve && !pinv_shape_served(h)) return fail(CLIK_EUNSUPPORTED, "%s", refusal);
+    if (!h->d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device: attach the kernel first");
+    return CLIK_OK;
+}
+
 extern "C" int clik_pinv_attach_rec_kernel(clik_pinv* h, void* rollout_rec_fn, void* value_rollout_rec_fn)
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
-    CLIK_NEEDS_DEVICE_HANDLE(h);
-    if (rollout_rec_fn && !h->jit_solve && !h->jit_rollout && !(h->kernel >= 0 && clik::pinv_kernel_is_static(h->kernel)))
-        return fail(CLIK_EUNSUPPORTED, "recording rollouts exist for skills a shape-specialised kernel serves");
-    if (rollout_rec_fn && !h->d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device: attach the kernel first");
+    CLIK_NEEDS_DEVICE_HANDLE(h);        // (also when detaching, unlike the other three)
+    if (rollout_rec_fn) {
+        int rc = pinv_attach_checks(h, "recording rollouts exist for skills a shape-specialised kernel serves");
+        if (rc) return rc;
+    }
     h->rec_rollout = (clik_jit_rollout_fn)rollout_rec_fn;
     h->val_rec_rollout = (clik_jit_rollout_fn)value_rollout_rec_fn;
     return CLIK_OK;
@@ -1327,6 +1344,18 @@ static int n_constraint_rows(const DevSkill& S)
     int m = 0;
     for (int ti = 0; ti < S.d.n_tasks; ++ti) m += S.d.tasks[ti].m;
     return m;
+}
+
+// the checks clik_*_constraint_values and clik_*_constraint_summary end with: the blocks the skill reads, the strides, the
+// time-term table
+static int trajectory_inputs_check(const DevSkill& S, const double* tterms, int64_t tt_rec_stride, int64_t tt_inst_stride,
+                                   const double* x, const double* y, int64_t y_stride)
+{
+    if (S.d.n_x > 0 && !x) return fail(CLIK_EINVAL, "skill has virtual_var: x required");
+    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    if (y_stride < 0 || tt_rec_stride < 0 || tt_inst_stride < 0) return fail(CLIK_EINVAL, "negative stride");
+    if (S.d.n_tslots > 0 && !tterms) return fail(CLIK_EINVAL, "tterms (device) required: the skill has time slots");
+    return CLIK_OK;
 }
 
 // what clik_*_constraint_values check before they launch (`host_only`: the handle has nothing on the device)
@@ -1345,10 +1374,8 @@ static int constraint_values_common(clik_monitor_fn fn, const DevSkill& S, const
     if (host_only)
         return fail(CLIK_EINVAL, "this handle was created host-only (clik_*_create_host / CLIK_HOST_ONLY=1): host-side queries only");
     if (!d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device");
-    if (S.d.n_x > 0 && !x) return fail(CLIK_EINVAL, "skill has virtual_var: x required");
-    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
-    if (y_stride < 0 || tt_rec_stride < 0 || tt_inst_stride < 0) return fail(CLIK_EINVAL, "negative stride");
-    if (S.d.n_tslots > 0 && !tterms) return fail(CLIK_EINVAL, "tterms (device) required: the skill has time slots");
+    const int rc = trajectory_inputs_check(S, tterms, tt_rec_stride, tt_inst_stride, x, y, y_stride);
+    if (rc) return rc;
     const hipError_t er = fn(d_img, (long long)n_rec, (long long)B, S.d.n_tslots > 0 ? tterms : nullptr,
                              (long long)tt_rec_stride, (long long)tt_inst_stride, q, x, y, (long long)y_stride, e, J, et,
                              (hipStream_t)stream);
@@ -1361,9 +1388,8 @@ extern "C" int clik_pinv_attach_monitor_kernel(clik_pinv* h, void* constraint_va
     if (!h) return fail(CLIK_EINVAL, "null handle");
     if (constraint_values_fn) {
         CLIK_NEEDS_DEVICE_HANDLE(h);
-        if (!h->jit_solve && !h->jit_rollout && !(h->kernel >= 0 && clik::pinv_kernel_is_static(h->kernel)))
-            return fail(CLIK_EUNSUPPORTED, "constraint values exist for skills a shape-specialised kernel serves");
-        if (!h->d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device: attach the kernel first");
+        int rc = pinv_attach_checks(h, "constraint values exist for skills a shape-specialised kernel serves");
+        if (rc) return rc;
     }
     h->monitor_fn = (clik_monitor_fn)constraint_values_fn;
     return CLIK_OK;
@@ -1381,20 +1407,33 @@ extern "C" int clik_pinv_constraint_values(const clik_pinv* h, int64_t n_rec, in
 }
 
 // ---- constraint summaries over a trajectory (clik_*_constraint_summary; the kernels: clik_summary.hpp) -----------------
+// tol and the seven outputs of a summary (all device), as the entry points of the summaries and of the summarising rollouts
+// take them one by one: filled once there, in the order the attached functions take them
+struct SummaryIo {
+    const double* tol;
+    double* abs_max; int32_t* abs_max_at; double* last; double* rms; double* viol_max; int32_t* viol_count;
+    int32_t* settled_at;
+};
+
+static int summary_io_check(const SummaryIo& o)
+{
+    if (!o.abs_max || !o.abs_max_at || !o.last || !o.rms || !o.viol_max || !o.viol_count)
+        return fail(CLIK_EINVAL, "abs_max, abs_max_at, last, rms, viol_max and viol_count must be device pointers");
+    if ((o.tol == nullptr) != (o.settled_at == nullptr)) return fail(CLIK_EINVAL, "tol and settled_at go together");
+    return CLIK_OK;
+}
+
 // what clik_*_constraint_summary check before they launch
 static int constraint_summary_common(clik_summary_fn fn, clik_summary_work_fn work_fn, const DevSkill& S, const void* d_img,
                                      bool host_only, int64_t n_rec, int64_t B, const double* tterms, int64_t tt_rec_stride,
                                      int64_t tt_inst_stride, const double* q, const double* x, const double* y,
-                                     int64_t y_stride, const double* tol, void* work, int64_t work_bytes, double* abs_max,
-                                     int32_t* abs_max_at, double* last, double* rms, double* viol_max, int32_t* viol_count,
-                                     int32_t* settled_at, void* stream)
+                                     int64_t y_stride, void* work, int64_t work_bytes, const SummaryIo& o, void* stream)
 {
     if (n_rec < 0 || B < 0) return fail(CLIK_EINVAL, "negative size");
     if (n_rec == 0 || B == 0) return CLIK_OK;
     if (!q) return fail(CLIK_EINVAL, "q must be a device pointer");
-    if (!abs_max || !abs_max_at || !last || !rms || !viol_max || !viol_count)
-        return fail(CLIK_EINVAL, "abs_max, abs_max_at, last, rms, viol_max and viol_count must be device pointers");
-    if ((tol == nullptr) != (settled_at == nullptr)) return fail(CLIK_EINVAL, "tol and settled_at go together");
+    int rc = summary_io_check(o);
+    if (rc) return rc;
     if (!fn || !work_fn)
         return fail(CLIK_EUNSUPPORTED, "no constraint-summary kernel instantiated for this skill (clik_*_attach_summary_kernel: "
                                        "skills of the shape-specialised family have one)");
@@ -1402,17 +1441,15 @@ static int constraint_summary_common(clik_summary_fn fn, clik_summary_work_fn wo
         return fail(CLIK_EINVAL, "this handle was created host-only (clik_*_create_host / CLIK_HOST_ONLY=1): host-side queries only");
     if (!d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device");
     if (n_rec > 0x7fffffffLL) return fail(CLIK_EINVAL, "more than 2^31 - 1 records");
-    if (S.d.n_x > 0 && !x) return fail(CLIK_EINVAL, "skill has virtual_var: x required");
-    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
-    if (y_stride < 0 || tt_rec_stride < 0 || tt_inst_stride < 0) return fail(CLIK_EINVAL, "negative stride");
-    if (S.d.n_tslots > 0 && !tterms) return fail(CLIK_EINVAL, "tterms (device) required: the skill has time slots");
+    rc = trajectory_inputs_check(S, tterms, tt_rec_stride, tt_inst_stride, x, y, y_stride);
+    if (rc) return rc;
     const unsigned long long need = work_fn((long long)n_rec, (long long)B);
     if (!work || work_bytes < 0 || (unsigned long long)work_bytes < need)
         return fail(CLIK_EINVAL, "work must hold %llu bytes (clik_*_summary_work_bytes), got %lld", need, (long long)work_bytes);
     const hipError_t er = fn(d_img, (long long)n_rec, (long long)B, S.d.n_tslots > 0 ? tterms : nullptr,
-                             (long long)tt_rec_stride, (long long)tt_inst_stride, q, x, y, (long long)y_stride, tol, work,
-                             (unsigned long long)work_bytes, abs_max, abs_max_at, last, rms, viol_max, viol_count, settled_at,
-                             (hipStream_t)stream);
+                             (long long)tt_rec_stride, (long long)tt_inst_stride, q, x, y, (long long)y_stride, o.tol, work,
+                             (unsigned long long)work_bytes, o.abs_max, o.abs_max_at, o.last, o.rms, o.viol_max, o.viol_count,
+                             o.settled_at, (hipStream_t)stream);
     if (er != hipSuccess) return hipfail(er, "constraint-summary kernel launch");
     return CLIK_OK;
 }
@@ -1439,9 +1476,8 @@ extern "C" int clik_pinv_attach_summary_kernel(clik_pinv* h, void* constraint_su
     if (constraint_summary_fn) {
         CLIK_NEEDS_DEVICE_HANDLE(h);
         if (!work_bytes_fn) return fail(CLIK_EINVAL, "the summary kernel comes with its work-size function");
-        if (!h->jit_solve && !h->jit_rollout && !(h->kernel >= 0 && clik::pinv_kernel_is_static(h->kernel)))
-            return fail(CLIK_EUNSUPPORTED, "constraint summaries exist for skills a shape-specialised kernel serves");
-        if (!h->d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device: attach the kernel first");
+        int rc = pinv_attach_checks(h, "constraint summaries exist for skills a shape-specialised kernel serves");
+        if (rc) return rc;
     }
     h->summary_fn = (clik_summary_fn)constraint_summary_fn;
     h->summary_work_fn = constraint_summary_fn ? (clik_summary_work_fn)work_bytes_fn : nullptr;
@@ -1461,9 +1497,9 @@ extern "C" int clik_pinv_constraint_summary(const clik_pinv* h, int64_t n_rec, i
                                             void* stream)
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
+    const SummaryIo o = {tol, abs_max, abs_max_at, last, rms, viol_max, viol_count, settled_at};
     return constraint_summary_common(h->summary_fn, h->summary_work_fn, h->host, h->d_img, h->dev == nullptr, n_rec, B,
-                                     tterms, tt_rec_stride, tt_inst_stride, q, x, y, y_stride, tol, work, work_bytes, abs_max,
-                                     abs_max_at, last, rms, viol_max, viol_count, settled_at, stream);
+                                     tterms, tt_rec_stride, tt_inst_stride, q, x, y, y_stride, work, work_bytes, o, stream);
 }
 
 static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
@@ -1476,7 +1512,7 @@ static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, i
     if (method != CLIK_INTEGRATE_EULER && method != CLIK_INTEGRATE_RK4) return fail(CLIK_EINVAL, "unknown integration method %d", method);
     if (B == 0 || n_ticks == 0) return CLIK_OK;
     const DevSkill& S = h->host;
-    const bool has_static = h->jit_rollout || (h->kernel >= 0 && clik::pinv_kernel_is_static(h->kernel));
+    const bool has_static = pinv_shape_served(h);
     if (S.d.n_x > 0) {
         if (!x || !dx) return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required (clik_pinv_rollout_batch_x)");
         if (!has_static)
@@ -1485,7 +1521,7 @@ static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, i
     }
     if (method == CLIK_INTEGRATE_RK4 && !has_static)
         return fail(CLIK_EUNSUPPORTED, "the Runge-Kutta rollout needs a shape-specialised kernel (none attached for this skill)");
-    if (!h->jit_rollout && (h->kernel < 0 || !clik::pinv_kernel_is_static(h->kernel)) && skill_needs_static(S))
+    if (!has_static && skill_needs_static(S))
         return extern_needs_kernel("clik_pinv_rollout_batch");
     if (h->kernel < 0 && !h->jit_rollout) return no_kernel_for_wide_state(S, "clik_pinv_rollout_batch");
     if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
@@ -1528,16 +1564,13 @@ static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, i
 // clik_rollout_summary.hpp) --------------------------------------------------------------------------------------------
 // what both controllers check before anything else: sizes, the outputs, and where the tick times come from
 static int rollout_sum_checks(int64_t B, int32_t n_ticks, int32_t method, int n_tslots, const double* tterms,
-                              const double* times, const double* tol, const double* abs_max, const int32_t* abs_max_at,
-                              const double* last, const double* rms, const double* viol_max, const int32_t* viol_count,
-                              const int32_t* settled_at)
+                              const double* times, const SummaryIo& o)
 {
     if (B < 0) return fail(CLIK_EINVAL, "negative size");
     if (n_ticks < 1) return fail(CLIK_EINVAL, "a summarising rollout needs at least one tick, got %d", n_ticks);
     if (method != CLIK_INTEGRATE_EULER && method != CLIK_INTEGRATE_RK4) return fail(CLIK_EINVAL, "unknown integration method %d", method);
-    if (!abs_max || !abs_max_at || !last || !rms || !viol_max || !viol_count)
-        return fail(CLIK_EINVAL, "abs_max, abs_max_at, last, rms, viol_max and viol_count must be device pointers");
-    if ((tol == nullptr) != (settled_at == nullptr)) return fail(CLIK_EINVAL, "tol and settled_at go together");
+    const int rc = summary_io_check(o);
+    if (rc) return rc;
     if (tterms && times) return fail(CLIK_EINVAL, "tterms (host) and times (device) are alternatives: pass one");
     if (n_tslots > 0 && !tterms && !times)
         return fail(CLIK_EINVAL, "the skill has time slots: tterms (host) or times (device) required");
@@ -1549,9 +1582,8 @@ extern "C" int clik_pinv_attach_rollout_summary_kernel(clik_pinv* h, void* rollo
     if (!h) return fail(CLIK_EINVAL, "null handle");
     if (rollout_sum_fn) {
         CLIK_NEEDS_DEVICE_HANDLE(h);
-        if (!h->jit_solve && !h->jit_rollout && !(h->kernel >= 0 && clik::pinv_kernel_is_static(h->kernel)))
-            return fail(CLIK_EUNSUPPORTED, "summarising rollouts exist for skills a shape-specialised kernel serves");
-        if (!h->d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device: attach the kernel first");
+        int rc = pinv_attach_checks(h, "summarising rollouts exist for skills a shape-specialised kernel serves");
+        if (rc) return rc;
     }
     h->rollsum_fn = (clik_rollsum_fn)rollout_sum_fn;
     return CLIK_OK;
@@ -1568,8 +1600,8 @@ extern "C" int clik_pinv_rollout_batch_sum(const clik_pinv* h, int64_t B, int32_
     if (!h) return fail(CLIK_EINVAL, "null handle");
     CLIK_NEEDS_DEVICE_HANDLE(h);
     const DevSkill& S = h->host;
-    int rc = rollout_sum_checks(B, n_ticks, method, S.d.n_tslots, tterms, times, tol, abs_max, abs_max_at, last, rms,
-                                viol_max, viol_count, settled_at);
+    const SummaryIo o = {tol, abs_max, abs_max_at, last, rms, viol_max, viol_count, settled_at};
+    int rc = rollout_sum_checks(B, n_ticks, method, S.d.n_tslots, tterms, times, o);
     if (rc) return rc;
     clik::RollRec rr;
     rc = roll_rec_of(B, S.d.n_y, y_per_tick, record_every, rec_q, rec_dq, rec_x, rec_dx, nullptr, rec_mode, &rr);
@@ -1581,7 +1613,7 @@ extern "C" int clik_pinv_rollout_batch_sum(const clik_pinv* h, int64_t B, int32_
     if (S.d.n_x > 0 && (!x || !dx)) return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required");
     // (as clik_pinv_rollout_batch_m: a skill whose rollouts are the built-in kernel's has no Runge-Kutta rollout, with or
     // without a summary)
-    if (method == CLIK_INTEGRATE_RK4 && !h->jit_rollout && !(h->kernel >= 0 && clik::pinv_kernel_is_static(h->kernel)))
+    if (method == CLIK_INTEGRATE_RK4 && !pinv_shape_served(h))
         return fail(CLIK_EUNSUPPORTED, "the Runge-Kutta rollout needs a shape-specialised kernel (none attached for this skill)");
     if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
     if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
@@ -1593,7 +1625,7 @@ extern "C" int clik_pinv_rollout_batch_sum(const clik_pinv* h, int64_t B, int32_
     const clik::LaunchArgs la = {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->policy, x, dx, stages, nullptr,
                                  &rr};
     const hipError_t e = h->rollsum_fn(&la, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, mode, (hipStream_t)stream,
-                                       tol, abs_max, abs_max_at, last, rms, viol_max, viol_count, settled_at);
+                                       o.tol, o.abs_max, o.abs_max_at, o.last, o.rms, o.viol_max, o.viol_count, o.settled_at);
     if (d_tt) (void)hipFreeAsync(d_tt, (hipStream_t)stream);
     if (e != hipSuccess) return hipfail(e, "pinv summarising rollout launch");
     return CLIK_OK;
@@ -1845,14 +1877,20 @@ extern "C" int clik_qp_rollout_batch_dev(const clik_qp* hc, int64_t B, int32_t n
     return qp_rollout_common(hc, B, n_ticks, method, dt, max_speed, tts, q, x, y, dq, dx, slack, status, stream, &rr);
 }
 
+// what the four clik_qp_attach_*_kernel of the on-demand kernels check before they store a pointer: the skill is in the
+// shape-specialised family, and its image is on the device (uploaded here when no kernel of that family runs yet)
+static int qp_attach_checks(clik_qp* h)
+{
+    if (!qp_static_eligible(h->host)) return fail(CLIK_EUNSUPPORTED, "skill is outside the shape-specialised QP family");
+    return qp_upload_image(h);
+}
+
 extern "C" int clik_qp_attach_rec_kernel(clik_qp* h, void* rollout_rec_fn, void* value_rollout_rec_fn)
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
-    CLIK_NEEDS_DEVICE_HANDLE(h);
-    if (rollout_rec_fn && !qp_static_eligible(h->host))
-        return fail(CLIK_EUNSUPPORTED, "skill is outside the shape-specialised QP family");
+    CLIK_NEEDS_DEVICE_HANDLE(h);        // (also when detaching, unlike the other three)
     if (rollout_rec_fn) {
-        int rc = qp_upload_image(h);
+        int rc = qp_attach_checks(h);
         if (rc) return rc;
     }
     h->rec_rollout = (clik_qp_rec_fn)rollout_rec_fn;
@@ -1866,8 +1904,7 @@ extern "C" int clik_qp_attach_monitor_kernel(clik_qp* h, void* constraint_values
     if (!h) return fail(CLIK_EINVAL, "null handle");
     if (constraint_values_fn) {
         CLIK_NEEDS_DEVICE_HANDLE(h);
-        if (!qp_static_eligible(h->host)) return fail(CLIK_EUNSUPPORTED, "skill is outside the shape-specialised QP family");
-        int rc = qp_upload_image(h);
+        int rc = qp_attach_checks(h);
         if (rc) return rc;
     }
     h->monitor_fn = (clik_monitor_fn)constraint_values_fn;
@@ -1891,8 +1928,7 @@ extern "C" int clik_qp_attach_summary_kernel(clik_qp* h, void* constraint_summar
     if (constraint_summary_fn) {
         CLIK_NEEDS_DEVICE_HANDLE(h);
         if (!work_bytes_fn) return fail(CLIK_EINVAL, "the summary kernel comes with its work-size function");
-        if (!qp_static_eligible(h->host)) return fail(CLIK_EUNSUPPORTED, "skill is outside the shape-specialised QP family");
-        int rc = qp_upload_image(h);
+        int rc = qp_attach_checks(h);
         if (rc) return rc;
     }
     h->summary_fn = (clik_summary_fn)constraint_summary_fn;
@@ -1912,9 +1948,9 @@ extern "C" int clik_qp_constraint_summary(const clik_qp* h, int64_t n_rec, int64
                                           double* viol_max, int32_t* viol_count, int32_t* settled_at, void* stream)
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
+    const SummaryIo o = {tol, abs_max, abs_max_at, last, rms, viol_max, viol_count, settled_at};
     return constraint_summary_common(h->summary_fn, h->summary_work_fn, h->host, h->d_img, h->dev == nullptr, n_rec, B,
-                                     tterms, tt_rec_stride, tt_inst_stride, q, x, y, y_stride, tol, work, work_bytes, abs_max,
-                                     abs_max_at, last, rms, viol_max, viol_count, settled_at, stream);
+                                     tterms, tt_rec_stride, tt_inst_stride, q, x, y, y_stride, work, work_bytes, o, stream);
 }
 
 static int qp_rollout_common(const clik_qp* hc, int64_t B, int32_t n_ticks, int32_t method, double dt,
@@ -1973,8 +2009,7 @@ extern "C" int clik_qp_attach_rollout_summary_kernel(clik_qp* h, void* rollout_s
     if (!h) return fail(CLIK_EINVAL, "null handle");
     if (rollout_sum_fn) {
         CLIK_NEEDS_DEVICE_HANDLE(h);
-        if (!qp_static_eligible(h->host)) return fail(CLIK_EUNSUPPORTED, "skill is outside the shape-specialised QP family");
-        int rc = qp_upload_image(h);
+        int rc = qp_attach_checks(h);
         if (rc) return rc;
     }
     h->rollsum_fn = (clik_qp_rollsum_fn)rollout_sum_fn;
@@ -1993,8 +2028,8 @@ extern "C" int clik_qp_rollout_batch_sum(const clik_qp* h, int64_t B, int32_t n_
     if (!h) return fail(CLIK_EINVAL, "null handle");
     CLIK_NEEDS_DEVICE_HANDLE(h);
     const DevSkill& S = h->host;
-    int rc = rollout_sum_checks(B, n_ticks, method, S.d.n_tslots, tterms, times, tol, abs_max, abs_max_at, last, rms,
-                                viol_max, viol_count, settled_at);
+    const SummaryIo o = {tol, abs_max, abs_max_at, last, rms, viol_max, viol_count, settled_at};
+    int rc = rollout_sum_checks(B, n_ticks, method, S.d.n_tslots, tterms, times, o);
     if (rc) return rc;
     clik::RollRec rr;
     rc = roll_rec_of(B, S.d.n_y, y_per_tick, record_every, rec_q, rec_dq, rec_x, rec_dx, rec_slack, rec_status, &rr);
@@ -2012,8 +2047,8 @@ extern "C" int clik_qp_rollout_batch_sum(const clik_qp* h, int64_t B, int32_t n_
                         (hipStream_t)stream, &d_tt);
     if (rc) return rc;
     const hipError_t e = h->rollsum_fn(h->d_img, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, slack, status, x, dx,
-                                       (hipStream_t)stream, stages, &rr, tol, abs_max, abs_max_at, last, rms, viol_max,
-                                       viol_count, settled_at);
+                                       (hipStream_t)stream, stages, &rr, o.tol, o.abs_max, o.abs_max_at, o.last, o.rms,
+                                       o.viol_max, o.viol_count, o.settled_at);
     if (d_tt) (void)hipFreeAsync(d_tt, (hipStream_t)stream);
     if (e != hipSuccess) return hipfail(e, "qp summarising rollout launch");
     return CLIK_OK;

@@ -247,3 +247,63 @@ def test_scheduling_strategy_per_translation_unit(monkeypatch):
     recs = jit._records()
     assert recs and all("sched" not in json.dumps(meta.get("flags", [])) for _, meta, _ in recs)
     assert {meta["_sched"] for _, meta, _ in recs} == {None, "max-ilp", "max-memory-clause"}
+
+
+# ---- the generated translation units and the table of on-demand units ---------------------------------------------------------
+TEMPLATES = ["_TEMPLATE", "_VALUE_TEMPLATE", "_QP_TEMPLATE", "_QP_VALUE_TEMPLATE", "_REC_TEMPLATE", "_VALUE_REC_TEMPLATE",
+             "_QP_REC_TEMPLATE", "_QP_VALUE_REC_TEMPLATE", "_TIME_TEMPLATE", "_MONITOR_TEMPLATE", "_SUMMARY_TEMPLATE",
+             "_ROLLSUM_TEMPLATE", "_QP_ROLLSUM_TEMPLATE", "_FUNCTION_TEMPLATE"]
+
+
+def _words_masked(text):
+    """a recorded value unit with its image words taken out again: the template it was written from"""
+    import re
+    text = re.sub(r"RawImage<\d+>", "RawImage<%(nwords)d>", text)
+    return re.sub(r"kRaw = \{\{.*?\}\};", "kRaw = {{%(words)s}};", text, flags=re.S)
+
+
+def test_template_texts_are_those_of_the_committed_records():
+    """The text of a template is part of every request id under tests/golden/jit_records and of every cache name: each of
+    the fourteen is stored by at least one committed record exactly as the module holds it (the value templates with the
+    record's image words masked back to the placeholders; ``_TEMPLATE`` is stored as null), and no record stores a text
+    that is none of them."""
+    import json
+    from casclik_amd import jit
+    texts = {name: getattr(jit, name) for name in TEMPLATES}
+    assert len(set(texts.values())) == len(TEMPLATES)
+    counts = dict.fromkeys(TEMPLATES, 0)
+    for fn in sorted(os.listdir(jit.RECORDS)):
+        if not (fn.startswith("req_") and fn.endswith(".json")):
+            continue
+        with open(os.path.join(jit.RECORDS, fn)) as f:
+            stored = json.load(f)["template"]
+        if stored is None:
+            counts["_TEMPLATE"] += 1
+            continue
+        hits = [name for name, text in texts.items()
+                if (_words_masked(stored) if "VALUE" in name else stored) == text]
+        assert len(hits) == 1, (fn, hits)
+        counts[hits[0]] += 1
+    print(counts)
+    assert all(n >= 1 for n in counts.values()), counts
+
+
+def test_the_table_of_on_demand_units_is_complete():
+    """every entry of ``jit.UNITS`` - and the second, value-specialised object of the recording rollouts - names one of the
+    module's templates, entry symbols that template defines as ``extern "C"``, and a required symbol of the library"""
+    import re
+    from casclik_amd import jit
+    texts = [getattr(jit, name) for name in TEMPLATES]
+    assert sorted(jit.UNITS) == sorted((what, kind) for what in ("rec", "time", "monitor", "summary", "rollsum")
+                                       for kind in ("pinv", "qp"))
+    units = list(jit.UNITS.items())
+    units += [((what + " values", kind), u["values"]) for (what, kind), u in jit.UNITS.items() if u["values"]]
+    assert len(units) == 12
+    for key, unit in units:
+        assert any(unit["template"] is t for t in texts), key
+        assert unit["symbols"], key
+        for symbol in unit["symbols"]:
+            assert re.search(r'^extern "C" [\w ]+\b%s\(' % re.escape(symbol), unit["template"], re.M), (key, symbol)
+        assert unit["attach"] in _capi.exported_symbols(), key
+        assert unit["attach"].startswith("clik_%s_attach_" % key[1]), key
+        assert callable(unit["entry"]) and (unit["refuse"] is None or callable(unit["refuse"])), key

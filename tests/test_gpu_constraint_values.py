@@ -252,7 +252,7 @@ def test_tail_is_masked_and_rows_are_isolated(ctrls, iiwa_fk):
     E = torch.full((B + 1, m_tot), sentinel, dtype=torch.float64, device=dev)
     J = torch.full((B + 1, m_tot, n), sentinel, dtype=torch.float64, device=dev)
     Et = torch.full((B + 1, m_tot), sentinel, dtype=torch.float64, device=dev)
-    ctrl._require_monitor_kernel()
+    ctrl._require_kernel("monitor")
     with torch.cuda.device(dev):
         rc = ctrl._lib.clik_pinv_constraint_values(ctrl._handle, 1, B, None, 0, 0, ptr(Qd), None, ptr(Yd), 0, ptr(E), ptr(J),
                                                    ptr(Et), current_stream(dev))

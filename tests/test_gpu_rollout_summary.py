@@ -275,3 +275,53 @@ def test_a_nan_in_one_instance_marks_that_instance_and_no_other(ctrls, iiwa_fk):
         assert not bool(torch.isnan(clean[key].double()).any()), key
     limits = ctrl.constraint_rows()["joint_limits"]
     assert bool(torch.isnan(poisoned["abs_max"][bad, limits]).all()), poisoned["abs_max"][bad]
+
+
+# ---- 8: every on-demand kernel is built once -----------------------------------------------------------------------------
+def _unit_of(template):
+    """which entry of ``jit.UNITS`` a translation unit is (its second, value-specialised object counts as the entry's)"""
+    from casclik_amd import jit
+    for (what, _), unit in jit.UNITS.items():
+        for u in (unit, unit["values"]):
+            if u and any('extern "C" hipError_t %s(' % s in (template or "") for s in u["symbols"]):
+                return what
+    return None
+
+
+@pytest.mark.parametrize("name", ["stack", "qp"])
+def test_every_on_demand_kernel_is_asked_for_once(iiwa_fk, ur5_fk, monkeypatch, name):
+    """A recording rollout, a summarising one, the constraint values and their summaries, each twice on a fresh
+    controller, B = 3 (a partial wave), 2 ticks: the first round asks ``jit.build_shape_library`` for each kind of unit
+    exactly once (the recording rollouts for two objects where a value-specialised kernel serves the handle), the second
+    round for none, and returns the first round's bits."""
+    from casclik_amd import jit
+    spec, ctrl = _make(name, iiwa_fk, ur5_fk)
+    asked = []
+    build = jit.build_shape_library
+
+    def counting(init, verbose=False, template=None, defines=(), extern=""):
+        asked.append(_unit_of(template))
+        return build(init, verbose, template=template, defines=defines, extern=extern)
+    monkeypatch.setattr(jit, "build_shape_library", counting)
+    B, n = 3, 2
+    Q, _, Y = _inputs(name, B, iiwa_fk, seed=6)
+    times = DT * np.arange(n)
+
+    def one_round():
+        rec = ctrl.rollout_batch(times, Q, input_var=Y, dt=DT, record_every=1)
+        summed = ctrl.rollout_batch(times, Q, input_var=Y, dt=DT, summary=True)
+        values = ctrl.constraint_values_batch(times, rec[-1]["q"], input_var=Y)
+        summary = ctrl.constraint_summary_batch(times, rec[-1]["q"], input_var=Y)
+        flat = list(rec[:-1]) + list(summed[:-1]) + [values]
+        for d in (rec[-1], summed[-1], summary):
+            flat += [d[key] for key in sorted(d)]
+        return flat
+    first = one_round()
+    want = {"rec": 2 if ctrl.value_kernel else 1, "rollsum": 1, "monitor": 1, "summary": 1}
+    assert {what: asked.count(what) for what in set(asked)} == want, asked
+    del asked[:]
+    second = one_round()
+    assert asked == []
+    assert len(first) == len(second) and len(first) > 12
+    for a, b in zip(first, second):
+        assert _same_bits(a, b)

@@ -81,7 +81,7 @@ def lds_line(ctrl):
     """the LDS bytes of a block of the attached summarising kernels, from the loaded unit itself"""
     from casclik_amd import jit
     for so, lib in jit._loaded.items():
-        if hasattr(lib, "clik_jit_rollsum_info") and ctrl._rollsum_kernel and ctrl._rollsum_kernel in so:
+        if hasattr(lib, "clik_jit_rollsum_info") and ctrl._kernels.get("rollsum") and ctrl._kernels.get("rollsum") in so:
             info = lib.clik_jit_rollsum_info
             info.restype, info.argtypes = C.c_longlong, [C.c_int]
             return ("A block of the summarising kernels: Euler %d wave(s), %d bytes of LDS; Runge-Kutta %d wave(s), %d bytes; "
