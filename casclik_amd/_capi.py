@@ -187,6 +187,7 @@ _SYMBOLS = [
     "clik_qp_attach_summary_kernel", "clik_qp_summary_work_bytes", "clik_qp_constraint_summary",
     "clik_pinv_attach_rollout_summary_kernel", "clik_pinv_rollout_batch_sum",
     "clik_qp_attach_rollout_summary_kernel", "clik_qp_rollout_batch_sum",
+    "clik_pinv_attach_converge_kernel", "clik_pinv_converge_batch", "clik_qp_attach_converge_kernel", "clik_qp_converge_batch",
     "clik_qp_create", "clik_qp_create_host", "clik_qp_destroy", "clik_qp_n_vars", "clik_qp_n_rows", "clik_qp_workspace_bytes",
     "clik_qp_kernel_name", "clik_qp_kernel_variant", "clik_qp_shape_describe", "clik_qp_attach_kernel", "clik_qp_image_words", "clik_qp_attach_value_kernel", "clik_qp_is_box_family",
     "clik_qp_attach_resident_kernel", "clik_qp_resident_waves", "clik_qp_resident_run",
@@ -377,6 +378,15 @@ def load_library(path=None):
         fn = getattr(lib, "clik_%s_rollout_batch_sum" % kind)
         fn.restype = C.c_int
         fn.argtypes = getattr(lib, "clik_%s_rollout_batch_rec" % kind).argtypes + [dp, dp, dp, ip, dp, dp, dp, ip, ip]
+    # the converging rollout: B, max_ticks, dt, max_speed, min_step, tterms (host, one record), q, x, y, dq, dx, mode |
+    # status (QP: then slack), tol, ticks, stop_status, residual, stream
+    for kind, extra in (("pinv", []), ("qp", [dp])):
+        fn = getattr(lib, "clik_%s_attach_converge_kernel" % kind)
+        fn.restype, fn.argtypes = C.c_int, [vp, C.c_void_p]
+        fn = getattr(lib, "clik_%s_converge_batch" % kind)
+        fn.restype = C.c_int
+        fn.argtypes = [vp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double),
+                       dp, dp, dp, dp, dp, ip] + extra + [dp, ip, ip, dp, vp]
     lib.clik_summary_chunk_length.restype = C.c_int64
     lib.clik_summary_chunk_length.argtypes = [C.c_int64, C.c_int64]
     lib.clik_qp_n_vars.restype = C.c_int

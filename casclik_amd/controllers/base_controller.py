@@ -320,6 +320,62 @@ def rollout_summary_request(summary, summary_tol, n_ticks, m_tot):
     return True, summary_tolerances(summary_tol, m_tot)
 
 
+def converge_tolerances(tol, m_tot):
+    """``tol`` of ``converge_batch`` as ``[m_tot]`` float64: a scalar for all rows or one value per row, each >= 0;
+    ``+inf`` is allowed (the row cannot block).  ValueError for a wrong length, a negative entry and NaN."""
+    arr = np.asarray(tol.detach().cpu().numpy() if hasattr(tol, "detach") else tol, dtype=np.float64)
+    if arr.ndim == 0:
+        arr = np.full(m_tot, float(arr))
+    arr = arr.reshape(-1)
+    if arr.size != m_tot:
+        raise ValueError("tol has %d entries, the skill %d constraint rows" % (arr.size, m_tot))
+    if np.isnan(arr).any() or (arr < 0.0).any():
+        raise ValueError("tol must be >= 0 (+inf allowed), not NaN")
+    return np.ascontiguousarray(arr)
+
+
+def converge_request(tol, max_ticks, min_step, input_var, m_tot):
+    """What ``converge_batch`` asks for, checked on the host: ``(tol [m_tot] float64, max_ticks)``.  ValueError for a bad
+    ``tol`` (``converge_tolerances``), ``max_ticks < 0``, a negative or NaN ``min_step`` and a 3-D ``input_var``: the
+    target of a converging rollout is fixed."""
+    shape = tuple(input_var.shape) if hasattr(input_var, "shape") and not hasattr(input_var, "toarray") else ()
+    if len(shape) >= 3:
+        raise ValueError("input_var must be [B, n_y]: targets are fixed here, one per instance for the whole launch "
+                         "(rollout_batch follows a target per tick), got shape %s" % (shape,))
+    if isinstance(max_ticks, bool) or not isinstance(max_ticks, (int, np.integer)) or max_ticks < 0:
+        raise ValueError("max_ticks must be an int >= 0, got %r" % (max_ticks,))
+    if not float(min_step) >= 0.0:
+        raise ValueError("min_step must be >= 0, got %r" % (min_step,))
+    return converge_tolerances(tol, m_tot), int(max_ticks)
+
+
+def select_seeds(ticks, status, residual, tol, S):
+    """Which of its ``S`` seeds serves each target of an ``ik_batch`` launch: a pure function of torch tensors, on any
+    device.  ``ticks``, ``status`` ``[T * S]`` and ``residual`` ``[T * S, M_tot]`` are ``converge_batch``'s info of
+    instance ``t * S + s``, ``tol`` ``[M_tot]``.  Returns the seed index ``[T]`` (int64).  Among a target's seeds with
+    status 0 the fewest ticks wins, then the lowest index.  If none has status 0, the seed whose ``max_i residual_i /
+    tol_i`` over the rows with a finite, non-zero ``tol_i`` is smallest wins (then the lowest index); a seed with status 4
+    is chosen only when all of the target's seeds have it."""
+    torch = _torch()
+    S = int(S)
+    T = ticks.numel() // S
+    ticks, status = ticks.reshape(T, S), status.reshape(T, S)
+    tol = torch.as_tensor(tol, dtype=torch.float64, device=residual.device).reshape(-1)
+    rows = torch.isfinite(tol) & (tol != 0.0)
+    if bool(rows.any()):
+        score = (residual.reshape(T, S, -1)[:, :, rows] / tol[rows]).amax(dim=2)
+    else:
+        score = torch.zeros((T, S), dtype=torch.float64, device=residual.device)
+    cls = torch.where(status == 0, 0, torch.where(status == 4, 2, 1))
+    best = cls.amin(dim=1, keepdim=True)
+    key = torch.where(best == 0, ticks.to(torch.float64), torch.where(best == 1, score, torch.zeros_like(score)))
+    inf = torch.full_like(key, float("inf"))
+    key = torch.where(cls == best, key, inf)
+    hit = (cls == best) & (key == key.amin(dim=1, keepdim=True))
+    idx = torch.arange(S, device=ticks.device).expand(T, S)
+    return torch.where(hit, idx, torch.full_like(idx, S)).amin(dim=1)
+
+
 def trajectory_rows(val, width, what, lead=None):
     """``val`` as ``(tensor-or-array [R, B, width], ndim)``: a ``[B, width]`` matrix (or what ``to_device_matrix`` takes
     for one) is one record, ``ndim`` 2; a ``[R, B, width]`` array or tensor stays as it is, ``ndim`` 3.  ``lead``: the
@@ -448,7 +504,8 @@ class BaseController(object):
 
     def _require_kernel(self, what):
         """An on-demand kernel of this controller's skill (``jit.UNITS``: "rec" the recording / per-tick-target rollouts,
-        "monitor" the constraint values, "summary" the constraint summaries, "rollsum" the summarising rollout),
+        "monitor" the constraint values, "summary" the constraint summaries, "rollsum" the summarising rollout; ``jit.CONVERGE_UNITS``: "converge" the rollout
+        that runs until each instance has converged),
         instantiated and attached at its first use and cached like every other instantiation.  Where no kernel may be
         instantiated (``_want_jit``) or none can be - a skill outside the shape-specialised family - nothing is attached
         and the library refuses the call (NotImplementedError): there is no chunked or host fallback.  A skill whose
@@ -826,6 +883,99 @@ class BaseController(object):
                 work.numel() * 8, *out_ptrs, current_stream(dev))
         _capi.check(self._lib, rc)
         return {k: v.cpu().numpy() for k, v in out.items()} if was_np else out
+
+    # -- rollouts that run until each instance has converged ------------------------------------------------------
+    def converge_batch(self, robot_var, input_var=None, tol=1e-6, max_ticks=1000, dt=0.008, max_speed=0.0,
+                       virtual_var=None, time_var=0.0, min_step=0.0):
+        """Closed-loop inverse kinematics for a batch in ONE launch: every instance ticks (solve -> clamp(+-max_speed)
+        -> ``q += dq * dt``, explicit Euler) with the time ``time_var`` and its target ``input_var [B, n_y]`` frozen,
+        until it has converged or cannot go on; a wave of 64 instances leaves the loop when all of them have stopped.
+
+        Before tick r = 0, 1, ... of an instance every constraint is evaluated at its state: ``dist_i = |e_i|``, on the
+        rows of a ``SetConstraint`` the distance outside ``[set_min, set_max]`` (as ``viol_max`` of
+        ``constraint_summary_batch``).  The instance stops with ``status``
+
+        * 4 when some ``e_i`` is non-finite;
+        * 0 when ``dist_i <= tol_i`` on every row - ``tol`` is a scalar or ``[M_tot]`` values >= 0, rows as
+          ``constraint_rows()``; a row with ``tol_i = +inf`` cannot block (give that to the rows of velocity constraints
+          and of lower-priority tasks that cannot be met);
+        * 1 when r == ``max_ticks``;
+        * 3 (ReactiveQPController) when the QP of tick r is infeasible, 2 when ``min_step > 0`` and ``max_j |dq_j| * dt
+          <= min_step`` over the robot variables - the state stays as it was in both cases.
+
+        Returns ``(q, dq, mode, info)``, with virtual variables ``(q, x, dq, dx, mode, info)`` (ReactiveQPController: the
+        worst QP status met in place of ``mode``): the state at the stop, the velocity and mode of the last tick that was
+        integrated (zeros and -1 when there was none), and ``info = {"ticks": int32 [B], "status": int32 [B], "residual":
+        float64 [B, M_tot]}`` - the number of ticks integrated, the status above and the ``dist_i`` of the returned
+        state.  For status 4 every component of the instance's rows of ``q``, ``dq`` and ``residual`` is NaN; no other
+        instance changes.  Numpy when ``robot_var`` is numpy, device tensors otherwise; the same bits on every call and
+        in every batch.  ValueError for a bad ``tol`` (negative, NaN, wrong length), ``max_ticks < 0``, and a 3-D
+        ``input_var`` (targets are fixed here); NotImplementedError when no kernel could be instantiated for the skill,
+        when its block does not fit the LDS of a compute unit or when its kernel would spill."""
+        self._require_handle()
+        torch = _torch()
+        d, dev = self.descriptor, self._device
+        m_tot = sum(int(t["m"]) for t in d.tasks)
+        tol_np, max_ticks = converge_request(tol, max_ticks, min_step, input_var, m_tot)
+        Q, X, Y, B, was_np = self._batch_inputs(robot_var, virtual_var, input_var, clone=True)
+        if B < 1:
+            raise ValueError("converge_batch needs at least one instance")
+        dQ = torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
+        dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
+        mode = torch.empty((B,), dtype=torch.int32, device=dev)
+        info = {"ticks": torch.empty((B,), dtype=torch.int32, device=dev),
+                "status": torch.empty((B,), dtype=torch.int32, device=dev),
+                "residual": torch.empty((B, m_tot), dtype=torch.float64, device=dev)}
+        tol_dev = torch.from_numpy(tol_np).to(dev)
+        tt, ttp = _capi.tterms_arg(d.time_terms(float(scalar_of(time_var))))
+        self._require_kernel("converge")
+        extra = (None,) if self._kind == "qp" else ()       # (QP: slack, not returned)
+        with torch.cuda.device(dev):
+            rc = getattr(self._lib, "clik_%s_converge_batch" % self._kind)(
+                self._handle, B, max_ticks, float(dt), float(max_speed), float(min_step), ttp, ptr(Q), ptr(X), ptr(Y),
+                ptr(dQ), ptr(dX), ptr(mode), *extra, ptr(tol_dev), ptr(info["ticks"]), ptr(info["status"]),
+                ptr(info["residual"]), current_stream(dev))
+        _capi.check(self._lib, rc)
+        outs = (Q, X, dQ, dX, mode) if d.n_x > 0 else (Q, dQ, mode)
+        return self._rollout_result(outs, info, was_np)
+
+    def ik_batch(self, input_var, seeds, **converge_kwargs):
+        """Multi-seed inverse kinematics: ``T`` targets ``input_var [T, n_y]``, each started from ``S`` seeds - ``seeds
+        [S, n_q]`` shared by all targets or ``[T, S, n_q]`` - in ONE ``converge_batch`` launch of ``T * S`` instances
+        (instance ``t * S + s``); ``converge_kwargs`` are its other arguments.  Returns ``(q [T, n_q], info)``: per
+        target the state and ``converge_batch``'s info of the seed ``select_seeds`` picks, and ``info["seed"]`` (int32
+        ``[T]``) which one that was.  Numpy when ``seeds`` is numpy, device tensors otherwise.  For skills without
+        virtual variables (ValueError otherwise)."""
+        self._require_handle()
+        torch = _torch()
+        d, dev = self.descriptor, self._device
+        if d.n_x > 0 or "virtual_var" in converge_kwargs:
+            raise ValueError("ik_batch serves skills without virtual variables")
+        if "robot_var" in converge_kwargs:
+            raise ValueError("ik_batch starts from seeds, not from robot_var")
+        was_np = not isinstance(seeds, torch.Tensor)
+        sd = (seeds if not was_np else torch.from_numpy(np.ascontiguousarray(np.asarray(seeds, dtype=np.float64)))).to(
+            device=dev, dtype=torch.float64)
+        Y, _ = to_device_matrix(input_var, d.n_y, dev, "input_var")
+        T = Y.shape[0]
+        if sd.dim() == 2 and sd.shape[1] == d.n_q:
+            sd = sd.unsqueeze(0).expand(T, -1, -1)
+        if sd.dim() != 3 or sd.shape[0] != T or sd.shape[2] != d.n_q or sd.shape[1] < 1:
+            raise ValueError("seeds must be [S, %d] or [%d, S, %d], got shape %s" % (d.n_q, T, d.n_q, tuple(sd.shape)))
+        S = sd.shape[1]
+        Q0 = sd.reshape(T * S, d.n_q).contiguous()
+        Ys = Y.unsqueeze(1).expand(T, S, d.n_y).reshape(T * S, d.n_y).contiguous()
+        tol = converge_kwargs.get("tol", 1e-6)
+        q, _, _, info = self.converge_batch(Q0, Ys, **converge_kwargs)
+        m_tot = info["residual"].shape[1]
+        pick = select_seeds(info["ticks"], info["status"], info["residual"], converge_tolerances(tol, m_tot), S)
+        at = torch.arange(T, device=dev) * S + pick
+        out = {k: v.index_select(0, at) for k, v in info.items()}
+        out["seed"] = pick.to(torch.int32)
+        res = q.index_select(0, at)
+        if was_np:
+            return res.cpu().numpy(), {k: v.cpu().numpy() for k, v in out.items()}
+        return res, out
 
     # -- resident ticks -----------------------------------------------------------------------------------------
     def _resident_setup(self, waves, ring_depth, publish_ahead, stream, time_var):

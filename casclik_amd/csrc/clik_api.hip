@@ -94,6 +94,12 @@ typedef hipError_t (*clik_rollsum_fn)(const clik::LaunchArgs*, const double*, in
                                       const double*, double*, int32_t*, hipStream_t, const double*, double*, int32_t*,
                                       double*, double*, double*, int32_t*, int32_t*);
 
+// clik_jit_converge (casclik_amd/jit.py, clik_converge.hpp): one TickArgs record, B, max_ticks, dt, max_speed, min_step,
+// q, y, dq, mode, the stream, then tol, ticks, stop_status, residual (all device)
+typedef hipError_t (*clik_converge_fn)(const clik::LaunchArgs*, const TickArgs*, long long, int, double, double, double,
+                                       double*, const double*, double*, int32_t*, hipStream_t, const double*, int32_t*,
+                                       int32_t*, double*);
+
 typedef hipError_t (*clik_jit_value_fn)(const clik::LaunchArgs*, const TickArgs*, long long, const double*,
                                         const double*, double*, int32_t*, hipStream_t);
 
@@ -127,6 +133,8 @@ struct clik_pinv {
     clik_summary_work_fn summary_work_fn = nullptr;
     // the rollout that summarises them while it runs (clik_pinv_attach_rollout_summary_kernel)
     clik_rollsum_fn rollsum_fn = nullptr;
+    // the rollout that runs until each instance has converged (clik_pinv_attach_converge_kernel)
+    clik_converge_fn converge_fn = nullptr;
 };
 
 // clik_jit_qp_rollout_rec / clik_jit_qp_value_rollout_rec: the rollouts' arguments and the RollRec
@@ -138,6 +146,12 @@ typedef hipError_t (*clik_qp_value_rec_fn)(const double*, int, double, double, l
 typedef hipError_t (*clik_qp_rollsum_fn)(const void*, const double*, int, double, double, long long, double*, const double*,
                                          double*, double*, int32_t*, double*, double*, hipStream_t, int, const clik::RollRec*,
                                          const double*, double*, int32_t*, double*, double*, double*, int32_t*, int32_t*);
+
+// clik_jit_qp_converge: the skill image, one TickArgs record, B, max_ticks, dt, max_speed, min_step, q, y, dq, slack,
+// status, x, dx, the stream, then tol, ticks, stop_status, residual
+typedef hipError_t (*clik_qp_converge_fn)(const void*, const TickArgs*, long long, int, double, double, double, double*,
+                                          const double*, double*, double*, int32_t*, double*, double*, hipStream_t,
+                                          const double*, int32_t*, int32_t*, double*);
 
 struct clik_qp {
     DevSkill  host;
@@ -161,6 +175,7 @@ struct clik_qp {
     clik_summary_fn summary_fn = nullptr;    // their per-instance summaries (clik_qp_attach_summary_kernel)
     clik_summary_work_fn summary_work_fn = nullptr;
     clik_qp_rollsum_fn rollsum_fn = nullptr; // the rollout that summarises them (clik_qp_attach_rollout_summary_kernel)
+    clik_qp_converge_fn converge_fn = nullptr; // the rollout that runs to convergence (clik_qp_attach_converge_kernel)
     char      jit_name[64];
     // work area of the global-workspace kernels (clik_workspace.hpp): belongs to this handle, released by clik_qp_destroy
     clik::GwsOwner* gws;
@@ -1631,6 +1646,58 @@ extern "C" int clik_pinv_rollout_batch_sum(const clik_pinv* h, int64_t B, int32_
     return CLIK_OK;
 }
 
+// ---- rollouts that run until each instance has converged (clik_*_converge_batch; the kernels: clik_converge.hpp) --------
+// what both controllers check before anything else
+static int converge_checks(int64_t B, int32_t max_ticks, const double* tol, const int32_t* ticks,
+                           const int32_t* stop_status, const double* residual)
+{
+    if (B < 1) return fail(CLIK_EINVAL, "a converging rollout needs at least one instance, got %lld", (long long)B);
+    if (max_ticks < 0) return fail(CLIK_EINVAL, "max_ticks must be >= 0, got %d", max_ticks);
+    if (!tol) return fail(CLIK_EINVAL, "tol (device, one value per constraint row) required");
+    if (!ticks || !stop_status || !residual)
+        return fail(CLIK_EINVAL, "ticks, stop_status and residual must be device pointers");
+    return CLIK_OK;
+}
+
+extern "C" int clik_pinv_attach_converge_kernel(clik_pinv* h, void* converge_fn)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    if (converge_fn) {
+        CLIK_NEEDS_DEVICE_HANDLE(h);
+        int rc = pinv_attach_checks(h, "converging rollouts exist for skills a shape-specialised kernel serves");
+        if (rc) return rc;
+    }
+    h->converge_fn = (clik_converge_fn)converge_fn;
+    return CLIK_OK;
+}
+
+extern "C" int clik_pinv_converge_batch(const clik_pinv* h, int64_t B, int32_t max_ticks, double dt, double max_speed,
+                                        double min_step, const double* tterms, double* q, double* x, const double* y,
+                                        double* dq, double* dx, int32_t* mode, const double* tol, int32_t* ticks,
+                                        int32_t* stop_status, double* residual, void* stream)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    CLIK_NEEDS_DEVICE_HANDLE(h);
+    const DevSkill& S = h->host;
+    int rc = converge_checks(B, max_ticks, tol, ticks, stop_status, residual);
+    if (rc) return rc;
+    if (!h->converge_fn)
+        return fail(CLIK_EUNSUPPORTED, "no converging rollout instantiated for this skill "
+                                       "(clik_pinv_attach_converge_kernel: skills of the shape-specialised family have one)");
+    if (S.d.n_x > 0 && (!x || !dx)) return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required");
+    if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
+    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    TickArgs tk;
+    rc = fill_tick(S, tterms, &tk);
+    if (rc) return rc;
+    const clik::LaunchArgs la = {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->policy, x, dx, 1, nullptr,
+                                 nullptr};
+    const hipError_t e = h->converge_fn(&la, &tk, (long long)B, max_ticks, dt, max_speed, min_step, q, y, dq, mode,
+                                        (hipStream_t)stream, tol, ticks, stop_status, residual);
+    if (e != hipSuccess) return hipfail(e, "pinv converging rollout launch");
+    return CLIK_OK;
+}
+
 // ---------------------------------------------------------------------------- QP
 static int qp_upload_image(clik_qp* h)
 {
@@ -2051,6 +2118,43 @@ extern "C" int clik_qp_rollout_batch_sum(const clik_qp* h, int64_t B, int32_t n_
                                        o.viol_max, o.viol_count, o.settled_at);
     if (d_tt) (void)hipFreeAsync(d_tt, (hipStream_t)stream);
     if (e != hipSuccess) return hipfail(e, "qp summarising rollout launch");
+    return CLIK_OK;
+}
+
+extern "C" int clik_qp_attach_converge_kernel(clik_qp* h, void* converge_fn)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    if (converge_fn) {
+        CLIK_NEEDS_DEVICE_HANDLE(h);
+        int rc = qp_attach_checks(h);
+        if (rc) return rc;
+    }
+    h->converge_fn = (clik_qp_converge_fn)converge_fn;
+    return CLIK_OK;
+}
+
+extern "C" int clik_qp_converge_batch(const clik_qp* h, int64_t B, int32_t max_ticks, double dt, double max_speed,
+                                      double min_step, const double* tterms, double* q, double* x, const double* y,
+                                      double* dq, double* dx, int32_t* status, double* slack, const double* tol,
+                                      int32_t* ticks, int32_t* stop_status, double* residual, void* stream)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    CLIK_NEEDS_DEVICE_HANDLE(h);
+    const DevSkill& S = h->host;
+    int rc = converge_checks(B, max_ticks, tol, ticks, stop_status, residual);
+    if (rc) return rc;
+    if (!h->converge_fn || !h->d_img)
+        return fail(CLIK_EUNSUPPORTED, "no converging rollout instantiated for this skill "
+                                       "(clik_qp_attach_converge_kernel: skills of the shape-specialised family have one)");
+    if (S.d.n_x > 0 && (!x || !dx)) return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required");
+    if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
+    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    TickArgs tk;
+    rc = fill_tick(S, tterms, &tk);
+    if (rc) return rc;
+    const hipError_t e = h->converge_fn(h->d_img, &tk, (long long)B, max_ticks, dt, max_speed, min_step, q, y, dq, slack,
+                                        status, x, dx, (hipStream_t)stream, tol, ticks, stop_status, residual);
+    if (e != hipSuccess) return hipfail(e, "qp converging rollout launch");
     return CLIK_OK;
 }
 

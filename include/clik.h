@@ -475,6 +475,41 @@ int clik_pinv_rollout_batch_sum(const clik_pinv* h, int64_t B, int32_t n_ticks, 
                                 const double* times, const double* tol, double* abs_max, int32_t* abs_max_at,
                                 double* last, double* rms, double* viol_max, int32_t* viol_count, int32_t* settled_at);
 
+/* A rollout that runs until each instance has converged: closed-loop inverse kinematics for a batch in ONE launch (the
+ * kernels: casclik_amd/csrc/clik_converge.hpp, instantiated by casclik_amd/jit.py as clik_jit_converge and attached here;
+ * NULL detaches).  Explicit Euler; the time and the target are frozen: every tick reads the one time-slot record tterms
+ * (host, [2 * n_tslots], as clik_pinv_solve_batch; NULL for a skill without time slots) and the rows y the launch came
+ * with.  Instance b, with r = 0, 1, ...:
+ *   1. every constraint is evaluated at (t, z_r, y): dist_i = |e_i|, on the rows of a SetConstraint
+ *      dist_i = max(set_min_i - e_i, e_i - set_max_i, 0) with the bounds the ticks use (expressions evaluated at the
+ *      state; an infinite bound is "no bound").  Rows as clik_pinv_constraint_values, M_tot of them;
+ *   2. a non-finite e_i stops the instance with CLIK_CONVERGE_NONFINITE;
+ *   3. dist_i <= tol_i on every row stops it with CLIK_CONVERGE_OK - a row with tol_i = +inf cannot block (what the rows
+ *      of velocity constraints and of lower-priority tasks that cannot be met get);
+ *   4. r == max_ticks stops it with CLIK_CONVERGE_MAX_TICKS;
+ *   5. otherwise tick r is solved and clamped to +-max_speed (0: no clamp) as the rollouts do.  min_step > 0 and
+ *      max_j |dq_j| * dt <= min_step over the robot variables stops it with CLIK_CONVERGE_STALLED, the state unchanged;
+ *      any other step is integrated, z += d * dt (virtual variables alongside, unclamped), and r += 1.
+ * A stopped instance keeps its state; a wave of 64 instances leaves the loop when all of them have stopped, so a launch
+ * costs a wave the ticks of its own slowest instance.  Outputs per instance: q (and x) the state at the stop, in place;
+ * dq (and dx) the velocity of the last tick that was integrated (tick ticks - 1; zeros when ticks == 0) and mode its mode
+ * (-1 when ticks == 0); ticks [B] = r at the stop, the number of ticks integrated; stop_status [B] one of CLIK_CONVERGE_*;
+ * residual [B][M_tot] the dist_i of the returned state.  For CLIK_CONVERGE_NONFINITE every component of the instance's
+ * q, x, dq, dx and residual rows is a quiet NaN; no other instance changes.  One lane owns one instance: the same bits
+ * on every call and in every batch.  CLIK_EINVAL for B < 1, max_ticks < 0, a NULL tol or a NULL output;
+ * CLIK_EUNSUPPORTED for a handle without an attached kernel (one served by the built-in dynamic-shape kernel has
+ * none).                                                                                                              */
+#define CLIK_CONVERGE_OK          0   /* every row within its tolerance                      */
+#define CLIK_CONVERGE_MAX_TICKS   1   /* max_ticks ticks integrated, some row still outside  */
+#define CLIK_CONVERGE_STALLED     2   /* a step of at most min_step                          */
+#define CLIK_CONVERGE_INFEASIBLE  3   /* (QP) the tick's QP is infeasible                    */
+#define CLIK_CONVERGE_NONFINITE   4   /* a constraint value is NaN or infinite               */
+int clik_pinv_attach_converge_kernel(clik_pinv* h, void* converge_fn);
+int clik_pinv_converge_batch(const clik_pinv* h, int64_t B, int32_t max_ticks, double dt, double max_speed,
+                             double min_step, const double* tterms, double* q, double* x, const double* y,
+                             double* dq, double* dx, int32_t* mode, const double* tol, int32_t* ticks,
+                             int32_t* stop_status, double* residual, void* stream);
+
 /* ---- ReactiveQPController path ----------------------------------------- */
 /* replaces setup_problem_functions()+setup_solver() (reactive_qp.py:248-298) */
 int clik_qp_create(const clik_skill_desc* desc, const clik_qp_opts* opts,
@@ -610,6 +645,16 @@ int clik_qp_rollout_batch_sum(const clik_qp* h, int64_t B, int32_t n_ticks, int3
                               double* rec_x, double* rec_dx, double* rec_slack, int32_t* rec_status,
                               const double* times, const double* tol, double* abs_max, int32_t* abs_max_at,
                               double* last, double* rms, double* viol_max, int32_t* viol_count, int32_t* settled_at);
+
+/* The converging rollout, as clik_pinv_attach_converge_kernel / clik_pinv_converge_batch, the ticks hot-started from
+ * r = 1 on as in the rollouts.  In step 5 a tick whose QP is infeasible (status 2) stops the instance with
+ * CLIK_CONVERGE_INFEASIBLE, the state unchanged.  status [B] is the worst QP status the instance met, slack [B][n_slack]
+ * (may be NULL) and dq that of the last tick that was integrated.                                                      */
+int clik_qp_attach_converge_kernel(clik_qp* h, void* converge_fn);
+int clik_qp_converge_batch(const clik_qp* h, int64_t B, int32_t max_ticks, double dt, double max_speed,
+                           double min_step, const double* tterms, double* q, double* x, const double* y,
+                           double* dq, double* dx, int32_t* status, double* slack, const double* tol,
+                           int32_t* ticks, int32_t* stop_status, double* residual, void* stream);
 
 /* QP data only (H diag, A, lbA, ubA as the reference's H_func/A_func/Blb/Bub,
  * reactive_qp.py:283-298) for inspection and parity tests:

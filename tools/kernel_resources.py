@@ -4,7 +4,9 @@ remarks (no GPU needed).      python tools/kernel_resources.py [stack|pose|qp] [
 --rec: the recording / per-tick-target rollouts of that skill (jit._VALUE_REC_TEMPLATE / _QP_VALUE_REC_TEMPLATE) instead.
 --summary: the two constraint-summary kernels of that skill (jit._SUMMARY_TEMPLATE: image-reading, no numbers compiled in).
 --rollsum: the two summarising rollouts of that skill (jit._ROLLSUM_TEMPLATE / _QP_ROLLSUM_TEMPLATE: image-reading, Euler and
-Runge-Kutta; their LDS is dynamic - tools/rollout_summary_bench.py prints the launcher's figure)."""
+Runge-Kutta; their LDS is dynamic - tools/rollout_summary_bench.py prints the launcher's figure).
+--converge: the converging rollout of that skill (jit._CONVERGE_TEMPLATE / _QP_CONVERGE_TEMPLATE: pinv_converge_static_kernel /
+qp_converge_static_kernel, image-reading, Euler; LDS dynamic - tools/converge_bench.py prints the launcher's figure)."""
 import os
 import subprocess
 import sys
@@ -57,6 +59,8 @@ if "--summary" in sys.argv:
     template, words, value_flag = jit._SUMMARY_TEMPLATE, [], []
 if "--rollsum" in sys.argv:
     template, words, value_flag = (jit._QP_ROLLSUM_TEMPLATE if which == "qp" else jit._ROLLSUM_TEMPLATE), [], []
+if "--converge" in sys.argv:
+    template, words, value_flag = (jit._QP_CONVERGE_TEMPLATE if which == "qp" else jit._CONVERGE_TEMPLATE), [], []
 # (the scheduling strategy the shipped object is compiled with, casclik_amd/jit.py::sched_strategy - unless one is given)
 sched = jit.sched_strategy(template, init)
 if sched and not any("sched-strategy" in f for f in flags):
