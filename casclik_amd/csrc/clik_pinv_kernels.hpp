@@ -16,8 +16,9 @@
 //   conditioning of every solve is the reference's.  rJa = diag(s) Ja with
 //   s in {0,1} (multidim activation S, :289-298) is kept as a bit mask (wide
 //   stack) or as the second Gram matrix C = Ja^T diag(s) Ja (tall stack).
-//   The first EqualityConstraint is processed twice and stacked twice exactly
-//   as :317-326 + :382-396 do.
+//   The first EqualityConstraint is processed twice and stacked twice as
+//   :317-326 + :382-396 do; where the stack is kept as rows, the two copies are
+//   one block scaled by sqrt(2) (stack_push).
 //
 // One source, two instantiation styles (clik_device.hpp, "shape policies"):
 //   StaticShape<SD>  sizes / classes / feature flags / options are compile-time:
@@ -48,17 +49,26 @@ __device__ __forceinline__ void stack_push(Stack& st, double* wk, int lane, cons
                                            const uint32_t srow, const int times)
 {
     constexpr int NT = N * (N + 1) / 2;
-    if (!st.gram && st.r + times * m <= cap) {
+    // A block stacked twice ([J; J]: the first EqualityConstraint, :317-326 + :382-396) enters ONCE, scaled by sqrt(2):
+    // A'A, A' diag(s) A and the damped pinv(A) diag(s) A are the same functions of it.  Two copies made 2m > n rows on
+    // a redundant arm, so the projection went through the n x n Gram matrix of a stack of rank m < n, whose zero
+    // eigenvalue the damping lifts to lam for EVERY configuration: condition (2 smax^2 + lam) / lam = 1e8, and errors
+    // of 5e-10 where the problem's own conditioning allows 1e-12 (profiles/structural_parity.md).  Undamped, [J; J]
+    // has no inverse in the reference either: its rows stay as they are.
+    const bool merged = times == 2 && lam > 0.0;
+    const int copies = merged ? 1 : times;
+    if (!st.gram && st.r + copies * m <= cap) {
+        const double sc = merged ? 1.4142135623730951 : 1.0;
 #pragma unroll
         for (int rep = 0; rep < 2; ++rep) {
-            if (rep < times) {
+            if (rep < copies) {
                 const int r0 = st.r;
 #pragma unroll
                 for (int i = 0; i < N; ++i) {
                     if (i < m) {
 #pragma unroll
                         for (int j = 0; j < N; ++j)
-                            if (j < n) wk[((r0 + i) * N + j) * WAVE + lane] = J[i][j];
+                            if (j < n) wk[((r0 + i) * N + j) * WAVE + lane] = J[i][j] * sc;
                     }
                 }
                 st.sbits |= (srow & ((1u << m) - 1u)) << r0;

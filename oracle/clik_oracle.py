@@ -529,7 +529,7 @@ def tangent_cone_margin(e, set_min, set_max, dexpr):
 # PseudoInverseController
 # ==========================================================================
 def pinv_solve_batch(spec, options, t, Q, X=None, Y=None, return_all_modes=False, margins_out=None, _wrong=None,
-                     cond_out=None):
+                     cond_out=None, pinv_fn=None):
     """Literal PseudoInverseController: returns (dZ [B,n_state], mode [B]).
 
     dZ[:, :n_q] is robot_vel, the rest virtual_vel.
@@ -537,6 +537,11 @@ def pinv_solve_batch(spec, options, t, Q, X=None, Y=None, return_all_modes=False
     `cond_out` [B] (optional) receives, per instance, the SUM of the condition numbers of the matrices the reference's
     algorithm hands to its linear solver in the accepted mode (pseudo_inverse.py:92-105; the errors of successive solves add
     up): the yardstick of the stated parity tolerance (tests/tolerances.py).
+
+    `pinv_fn` (None = `dpinv`, the literal path) evaluates every pseudo-inverse of this call instead of `dpinv`, with its
+    signature `(J, opt, cond)`; what it adds to `cond` is what `cond_out` then holds.  The rest of the algorithm - stacking,
+    projections, mode scan - is unchanged.  For the yardsticks of tests/exact_yardstick.py (tests/tolerances.py: the
+    literal solve of a rank-deficient stack carries rounding noise of u * 1e8 that the problem itself does not have).
 
     `_wrong` (None = the reference's algorithm) names ONE deliberate deviation, for the tests that state what the
     reference-held figure pins resolve (tests/test_figure_pins.py): "no_S" stacks J instead of S J for an active
@@ -549,6 +554,7 @@ def pinv_solve_batch(spec, options, t, Q, X=None, Y=None, return_all_modes=False
     back to the bound with its gain instead of only freezing them (quirk D2)."""
     assert _wrong in (None, "no_S", "no_D1", "textbook_projection", "active_first", "cone_1d_rows", "boundary_flipped",
                       "multidim_loose", "set_pushes_back"), _wrong
+    pinv = dpinv if pinv_fn is None else pinv_fn
     cone_eps = -1e-12 if _wrong == "boundary_flipped" else 1e-12
     opt = default_pinv_options(options)
     Q = np.atleast_2d(np.asarray(Q, dtype=float))
@@ -612,14 +618,14 @@ def pinv_solve_batch(spec, options, t, Q, X=None, Y=None, return_all_modes=False
                     des = -_gain_apply(a.gain, e)
                     if ff:
                         des = des - Jt
-                    v = v + dpinv(Ji, opt, cnd).dot(des)
+                    v = v + pinv(Ji, opt, cnd).dot(des)
                     Ja.append(Ji); rJa.append(Ji)
                 # chain 2 (:327-443) - an independent if/elif ladder
                 if is_first and is_veleq:
                     des = _num(a.target, m).copy()
                     if ff:
                         des = des - Jt
-                    v = v + dpinv(Ji, opt, cnd).dot(des)
+                    v = v + pinv(Ji, opt, cnd).dot(des)
                     Ja.append(Ji); rJa.append(Ji)
                 elif is_set and is_last and conv_last:
                     if amap[mode_idx][set_idx]:
@@ -627,10 +633,10 @@ def pinv_solve_batch(spec, options, t, Q, X=None, Y=None, return_all_modes=False
                         if ff:
                             des = des - Jt
                         if Ja:
-                            N = I - dpinv(np.vstack(Ja), opt, cnd).dot(np.vstack(rJa))
+                            N = I - pinv(np.vstack(Ja), opt, cnd).dot(np.vstack(rJa))
                         else:
                             N = I   # never exercised by the reference (vertcat of nothing)
-                        v = v + N.dot(dpinv(Ji, opt, cnd)).dot(des)
+                        v = v + N.dot(pinv(Ji, opt, cnd)).dot(des)
                         Ja.append(Ji)
                         rJa.append(S.dot(Ji) if multidim else Ji)
                     else:
@@ -642,19 +648,19 @@ def pinv_solve_batch(spec, options, t, Q, X=None, Y=None, return_all_modes=False
                     des = -_gain_apply(a.gain, e)
                     if ff:
                         des = des - Jt
-                    N = I - dpinv(np.vstack(Ja), opt, cnd).dot(np.vstack(rJa))
+                    N = I - pinv(np.vstack(Ja), opt, cnd).dot(np.vstack(rJa))
                     if _wrong == "textbook_projection":
-                        v = v + dpinv(Ji.dot(N), opt, cnd).dot(des - Ji.dot(v))
+                        v = v + pinv(Ji.dot(N), opt, cnd).dot(des - Ji.dot(v))
                     else:
-                        v = v + N.dot(dpinv(Ji, opt, cnd)).dot(des)
+                        v = v + N.dot(pinv(Ji, opt, cnd)).dot(des)
                     Ja.append(Ji); rJa.append(Ji)
                 elif is_set:
                     if amap[mode_idx][set_idx]:
                         if _wrong == "set_pushes_back":
                             smin_, smax_ = _num(a.set_min, m), _num(a.set_max, m)
                             des = _gain_apply(a.gain, np.clip(e, smin_, smax_) - e)
-                            N = I - dpinv(np.vstack(Ja), opt, cnd).dot(np.vstack(rJa)) if Ja else I
-                            v = v + N.dot(dpinv(Ji, opt, cnd)).dot(des)
+                            N = I - pinv(np.vstack(Ja), opt, cnd).dot(np.vstack(rJa)) if Ja else I
+                            v = v + N.dot(pinv(Ji, opt, cnd)).dot(des)
                         Ja.append(Ji)
                         rJa.append(S.dot(Ji) if multidim else Ji)
                     else:
@@ -664,8 +670,8 @@ def pinv_solve_batch(spec, options, t, Q, X=None, Y=None, return_all_modes=False
                     des = _num(a.target, m).copy()
                     if ff:
                         des = des - Jt
-                    N = I - dpinv(np.vstack(Ja), opt, cnd).dot(np.vstack(rJa))
-                    v = v + N.dot(dpinv(Ji, opt, cnd)).dot(des)
+                    N = I - pinv(np.vstack(Ja), opt, cnd).dot(np.vstack(rJa))
+                    v = v + N.dot(pinv(Ji, opt, cnd)).dot(des)
                     Ja.append(Ji); rJa.append(Ji)
                 # VelocitySetConstraint: no branch -> ignored
             if return_all_modes:

@@ -31,6 +31,26 @@ of its instances - or all of them - FAILS: it compared nothing.  A NaN from the 
 fails.  Modes must be identical wherever the smallest tangent-cone decision
 margin of the instance (`clik_oracle.tangent_cone_margin`) exceeds MODE_MARGIN.
 
+TWO YARDSTICKS for the pseudo-inverse path, and when each applies:
+
+  the literal oracle with kappa (above)        pins WHAT is computed: branch choices, modes, the reference's quirks, the
+      order of the constraints - everything a wrong algorithm gets wrong by far more than rounding.  It is the numpy /
+      C restatement of the reference's own solves, so its answer carries their noise: for a task behind the first
+      equality that is u * 1e8 on a redundant arm whatever the configuration (measured against a 50-digit evaluation:
+      4.5e-10, tests/test_exact_yardstick.py), and the bound has to cover it: 3e-8 at the median.  `pinv_close`;
+      what bench.py and smoke() check, and every test written before the second one existed.
+  the stable evaluation with kappa_r           pins the ARITHMETIC.  The same algorithm with every pseudo-inverse taken
+      through the SVD filter factors, V diag(s / (s^2 + lam)) U' (tests/exact_yardstick.py::dpinv_stable, within 0.005
+      of the bound of the 50-digit evaluation), and kappa_r = the sum over the same pseudo-inverses of
+      (s1^2 + lam) / (sr^2 + lam), sr the smallest singular value above RANK_RTOL * s1 (`kappa_structural`): the
+      conditioning of the problem under perturbations that keep the stack's structure - a row that repeats stays
+      repeated.  Median bound on the 7-DoF stack 1.0e-12 - 1.4e-12, four orders below the first yardstick; on a
+      non-redundant arm the two coincide.  `pinv_close_structural`, same FACTOR / FLOOR / ILL_POSED / MAX_LEFT_OUT;
+      tests/test_gpu_structural_parity.py holds every tick kernel of the stack family to it.  It found the built-in
+      kernel 470 - 640 bounds out on the redundant arm (errors of 5e-10 from the n x n Gram matrix of [J; J]) where
+      the first yardstick had it at 0.02 of the bound; a Newton step less in `recip` moves the team kernels from
+      0.2 - 0.65 to 0.8 - 0.9 u kappa_r and stays inside FACTOR (profiles/structural_parity.md).
+
 Measured against the reference's own Python over the stand-in casadi (tests/golden/ref_pins.npz): err / (u kappa) <= 0.8
 for the oracle (tests/test_refpins.py); for the HIP kernels - different algebra: LDL' without pivoting, push-through and
 Woodbury forms, DESIGN.md section 3 - <= FACTOR with the margins recorded in profiles/r4_tolerance_sweep.txt."""
@@ -48,6 +68,7 @@ KKT_TOL = 1e-8
 PINV_RTOL = 1e-7          # = FACTOR u (2 smax^2 + lam) / lam at lam = 1e-7, smax^2 = 5.6
 QP_RTOL = 1e-8            # = FACTOR u kappa at kappa = 1.1e7 (cond(H) = 1001 with unit weights, mu = 1e-3)
 PINV_RTOL_TIGHT = 1e-10   # single well-conditioned task (kappa < 1e5)
+RANK_RTOL = 1e-8          # kappa_structural: singular values up to this share of the largest count as structurally zero
 
 
 def rtol_from_cond(kappa):
@@ -98,8 +119,8 @@ MAX_LEFT_OUT = 0.25     # a comparison that leaves more than this share of its i
 LAST = {}               # what the most recent *_close / worst_over_tol call did: {"rule", "checked", "left_out", "worst"}
 
 
-def _compare(a, ref, rows, kappa, ceiling, what):
-    """the shared body of pinv_close / qp_close.  `ref` rows that are NaN (the oracle's "infeasible") are no instances;
+def _compare(a, ref, rows, kappa, ceiling, what, rule="kappa"):
+    """the shared body of pinv_close / qp_close / pinv_close_structural.  `ref` rows that are NaN (the oracle's "infeasible") are no instances;
     a NaN in `a` where `ref` is finite is a FAILURE.  `rows`: boolean mask of the instances to compare (so that `ref` can
     stay the array the oracle returned and every instance keeps ITS kappa); `kappa`: condition numbers [B] given
     explicitly (`cond_out` of the oracle), else looked up from the oracle's last solve when `ref` is its result."""
@@ -123,7 +144,7 @@ def _compare(a, ref, rows, kappa, ceiling, what):
     assert tol.shape == err.shape, (what, "kappa does not belong to this batch", tol.shape, err.shape)
     posed = keep & (tol < ILL_POSED)
     left_out = int((keep & ~posed).sum())
-    LAST.update(rule="kappa", checked=int(posed.sum()), left_out=left_out,
+    LAST.update(rule=rule, checked=int(posed.sum()), left_out=left_out,
                 worst=float((err[posed] / tol[posed]).max()) if posed.any() else 0.0)
     if keep.any() and (not posed.any() or left_out > MAX_LEFT_OUT * keep.sum()):
         return False            # (nothing, or too little, was actually compared)
@@ -139,6 +160,30 @@ def pinv_close(a, ref, ceiling=PINV_RTOL, rows=None, kappa=None):
     no longer the oracle's array: it would silently fall back to the ceiling).  A NaN from the device where the
     reference is finite fails."""
     return _compare(a, ref, rows, kappa, ceiling, "pinv_close")
+
+
+def kappa_structural(J, lam):
+    """(s1^2 + lam) / (sr^2 + lam) of one damped pseudo-inverse of J: s1 the largest singular value, sr the smallest one
+    above RANK_RTOL * s1 (the numerical rank).  A row J repeats ([J; J]) or a row S zeroes ([S; J]) gives singular values
+    that are zero for EVERY configuration; they stay zero under perturbations that keep the stack's structure, and the
+    filter factor s / (s^2 + lam) carries them to zero, not to 1 / lam.  What `tests/exact_yardstick.py::dpinv_stable`
+    sums into `cond_out`."""
+    J = np.asarray(J, dtype=float)
+    if J.size == 0 or not np.isfinite(J).all():
+        return float("inf")     # (a poisoned instance: no condition number, and the SVD would raise)
+    s = np.linalg.svd(J, compute_uv=False)
+    if s[0] == 0.0:
+        return 1.0
+    sr = s[s > RANK_RTOL * s[0]][-1]
+    return float((s[0] ** 2 + lam) / (sr ** 2 + lam))
+
+
+def pinv_close_structural(a, ref, kappa_r, rows=None):
+    """`a` against `ref` = the oracle's algorithm evaluated with `exact_yardstick.dpinv_stable`, every instance held to
+    max(FLOOR, FACTOR u kappa_r), kappa_r [B] the `cond_out` of that evaluation.  The same body, constants, NaN rule
+    and `LAST` bookkeeping (rule "kappa_r") as `pinv_close`; there is no ceiling to fall back to."""
+    assert kappa_r is not None, "pinv_close_structural needs the cond_out of the stable evaluation"
+    return _compare(a, ref, rows, kappa_r, None, "pinv_close_structural", rule="kappa_r")
 
 
 def qp_close(a, ref, ceiling=QP_RTOL, rows=None, kappa=None):
