@@ -1,5 +1,5 @@
 // Rollouts that run until each instance has converged (clik_*_converge_batch, include/clik.h): closed-loop inverse
-// kinematics for a batch in one launch.  The lane-per-instance, image-in-LDS Euler loops of clik_rollout_summary.hpp with
+// kinematics for a batch in one launch.  The lane-per-instance, image-in-LDS Euler loop of the recording rollouts with
 // the time and the target frozen - every tick reads ONE TickArgs record and the target rows the launch came with - and a
 // stop test at the top of every tick.  A lane that has stopped keeps its state; a wave leaves the loop as soon as a
 // ballot shows none of its lanes active, so a launch costs every wave the ticks of its own slowest instance and no more.
@@ -133,33 +133,15 @@ __device__ __forceinline__ void converge_store(const ConvergeArgs& ca, const lon
 // A block is WV waves that share ONE copy of the skill image and of the tolerances; every wave owns 64 instances.
 // LDS: [skill image | tol (MT, even) | wave 0: zs (N slots) ys (n_y slots) | wave 1 ...], slot = 64 doubles
 template <const ShapeDesc& SD>
-constexpr int pinv_converge_wave_doubles()
-{
-    return (SD.n + (SD.n_y > 0 ? SD.n_y : 0)) * WAVE;
-}
-template <const ShapeDesc& SD>
 constexpr size_t pinv_converge_lds_bytes(int wv)
 {
     return ((size_t)StaticLayout<SD>::IMG_DOUBLES + SummaryLayout<SD>::TOL_DOUBLES
-            + (size_t)wv * pinv_converge_wave_doubles<SD>()) * sizeof(double);
+            + (size_t)wv * lane_wave_doubles<SD, false>(0)) * sizeof(double);
 }
-// waves per block: what puts most waves on a compute unit (four SIMDs, one wave each: the kernel holds the whole register
-// file), the fewest waves per block among equals; 0: not even one wave fits
 template <const ShapeDesc& SD>
 constexpr int pinv_converge_waves()
 {
-    int best = 0, best_cu = 0;
-    for (int wv = 1; wv <= 4; ++wv) {
-        const size_t bytes = pinv_converge_lds_bytes<SD>(wv);
-        if (bytes > kSummaryLdsCap) continue;
-        int cu = (int)(kSummaryLdsCap / bytes) * wv;
-        cu = cu > 4 ? 4 : cu;
-        if (cu > best_cu) {
-            best_cu = cu;
-            best = wv;
-        }
-    }
-    return best;
+    return waves_per_block<pinv_converge_lds_bytes<SD>>(kSummaryLdsCap);
 }
 
 template <const ShapeDesc& SD, int WV>
@@ -174,32 +156,23 @@ __global__ __launch_bounds__(WV * WAVE) CLIK_ROLL_ATTR void pinv_converge_static
     constexpr int NX = SD.n_x, NQ = N - NX;
     constexpr int NY = SD.n_y > 0 ? SD.n_y : 0;
     constexpr int MT = SL::MT;
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-    const long long b_own = ((long long)blockIdx.x * WV + wave) * WAVE;
-    const bool idle = b_own >= B;                       // (a wave past the end of the batch: loads the first rows, never
-    const long long b0 = idle ? 0 : b_own;              //  enters the loop, stores nothing)
-    const long long left = B - b0;                      // (> 0)
-    const int rows_valid = left < WAVE ? (int)left : WAVE;
-    const int rows_store = idle ? 0 : rows_valid;
-    const bool valid = !idle && lane < rows_valid;
+    const WavePlace<WV> w(B);       // (a wave past the end of the batch loads the first rows, never enters the loop, stores nothing)
+    const int lane = w.lane;
+    const long long b0 = w.b0;
+    const bool valid = w.valid;
     double* tols = lds + StaticLayout<SD>::IMG_DOUBLES;
-    double* zs = tols + SL::TOL_DOUBLES + wave * pinv_converge_wave_doubles<SD>();
+    double* zs = tols + SL::TOL_DOUBLES + w.wave * lane_wave_doubles<SD, false>(0);
     double* xs = zs + NQ * WAVE;
     double* ys = zs + N * WAVE;
     typedef double d2 __attribute__((ext_vector_type(2)));
     {
         const d2* src = (const d2*)img_g;
         d2* dst = (d2*)lds;
-        for (int k = wave; k < StaticLayout<SD>::IMG_CHUNKS; k += WV) dst[k * WAVE + lane] = src[k * WAVE + lane];
+        for (int k = w.wave; k < StaticLayout<SD>::IMG_CHUNKS; k += WV) dst[k * WAVE + lane] = src[k * WAVE + lane];
         for (int k = threadIdx.x; k < MT; k += WV * WAVE) tols[k] = ca.tol[k];
-        double qv[NQ], xv[NX > 0 ? NX : 1], yv[NY > 0 ? NY : 1];
-        stage_load<NQ>(q + b0 * NQ, NQ, rows_valid, lane, qv);
-        if constexpr (NX > 0) stage_load<NX>(x + b0 * NX, NX, rows_valid, lane, xv);
-        if constexpr (NY > 0) stage_load<NY>(y + b0 * NY, NY, rows_valid, lane, yv);
-        rows_to_lds<NQ>(qv, zs, lane);
-        if constexpr (NX > 0) rows_to_lds<NX>(xv, xs, lane);
-        if constexpr (NY > 0) rows_to_lds<NY>(yv, ys, lane);
+        StagedRows<NQ, NX, NY> rows;
+        rows.load(q, x, y, w);
+        rows.to_lds(zs, xs, ys, lane);
     }
     __syncthreads();
     const Img<SD>* __restrict__ S = (const Img<SD>*)lds;
@@ -223,14 +196,7 @@ __global__ __launch_bounds__(WV * WAVE) CLIK_ROLL_ATTR void pinv_converge_static
         double vt[N];
         int mt = -1;
         pinv_tick_static<SD>(S, tk, z, ysl, lane, active, vt, mt);
-        double step = 0.0;
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            double d = vt[j];
-            if (j < NQ && ca.max_speed > 0.0) d = fmax(fmin(d, ca.max_speed), -ca.max_speed);
-            vt[j] = d;
-            if (j < NQ) step = fmax(step, fabs(d) * ca.dt);
-        }
+        const double step = clamp_step_size<N, NQ>(vt, ca.max_speed, ca.dt);
         if (active && ca.min_step > 0.0 && step <= ca.min_step) {
             active = false;
             status = kConvStalled;
@@ -252,16 +218,8 @@ __global__ __launch_bounds__(WV * WAVE) CLIK_ROLL_ATTR void pinv_converge_static
         z[j] = nan_or(z[j], nan_hi);
         vout[j] = nan_or(vout[j], nan_hi);
     }
-    __syncthreads();
-    state_to_lds<NQ, NX>(z, zs, xs, lane);
-    __syncthreads();
-    rows_from_lds<NQ>(q + b0 * NQ, rows_store, zs, lane);
-    if constexpr (NX > 0) rows_from_lds<NX>(x + b0 * NX, rows_store, xs, lane);
-    __syncthreads();
-    state_to_lds<NQ, NX>(vout, zs, xs, lane);
-    __syncthreads();
-    rows_from_lds<NQ>(dq + b0 * NQ, rows_store, zs, lane);
-    if constexpr (NX > 0) rows_from_lds<NX>(dx + b0 * NX, rows_store, xs, lane);
+    rows_out<NQ, NX>(z, q, x, w, zs, xs);
+    rows_out<NQ, NX>(vout, dq, dx, w, zs, xs);
     if (mode_out != nullptr && valid) mode_out[b0 + lane] = acc_mode;
 }
 
@@ -297,15 +255,8 @@ inline hipError_t launch_converge_static(const LaunchArgs& a, const TickArgs& tk
         const long long per_block = (long long)WV * WAVE;
         const long long blocks = (B + per_block - 1) / per_block;
         if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-        const size_t shmem = converge_lds_bytes<SD>();
-        if (shmem > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(converge_kernel_ptr<SD>(), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)shmem);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((pinv_converge_static_kernel<SD, WV>), dim3((unsigned)blocks), dim3(WV * WAVE), shmem, stream,
-                           a.dImg, q, y, dq, mode, B, tk, a.roll_x, a.roll_dx, ca);
-        return hipGetLastError();
+        return launch_with_lds(pinv_converge_static_kernel<SD, WV>, (unsigned)blocks, WV * WAVE, converge_lds_bytes<SD>(),
+                               stream, a.dImg, q, y, dq, mode, B, tk, a.roll_x, a.roll_dx, ca);
     }
 }
 
@@ -335,11 +286,10 @@ __global__ __launch_bounds__(WAVE) void qp_converge_static_kernel(
     constexpr int NS = LY::NS;
     constexpr int NY = SD.n_y > 0 ? SD.n_y : 0;
     constexpr int MT = SL::MT;
-    const int lane = threadIdx.x;
-    const long long b0 = (long long)blockIdx.x * WAVE;
-    const long long left = B - b0;
-    const int rows_valid = left < WAVE ? (int)left : WAVE;
-    const bool valid = lane < rows_valid;
+    const WavePlace<1> w(B);
+    const int lane = w.lane;
+    const long long b0 = w.b0;
+    const bool valid = w.valid;
     double* slots = lds + LY::IMG_DOUBLES;
     double* zs = slots + LY::O_Z * WAVE;
     double* ys = slots + LY::O_Y * WAVE;
@@ -350,17 +300,13 @@ __global__ __launch_bounds__(WAVE) void qp_converge_static_kernel(
         const d2* src = (const d2*)img_g;
 #pragma unroll
         for (int k = 0; k < LY::IMG_CHUNKS; ++k) img[k] = src[k * WAVE + lane];
-        double qv[NQ], xv[NX > 0 ? NX : 1], yv[NY > 0 ? NY : 1];
-        stage_load<NQ>(q + b0 * NQ, NQ, rows_valid, lane, qv);
-        if constexpr (NX > 0) stage_load<NX>(x + b0 * NX, NX, rows_valid, lane, xv);
-        if constexpr (NY > 0) stage_load<NY>(y + b0 * NY, NY, rows_valid, lane, yv);
+        StagedRows<NQ, NX, NY> rows;
+        rows.load(q, x, y, w);
         d2* dst = (d2*)lds;
 #pragma unroll
         for (int k = 0; k < LY::IMG_CHUNKS; ++k) dst[k * WAVE + lane] = img[k];
         for (int k = lane; k < MT; k += WAVE) tols[k] = ca.tol[k];
-        rows_to_lds<NQ>(qv, zs, lane);
-        if constexpr (NX > 0) rows_to_lds<NX>(xv, zs + NQ * WAVE, lane);
-        if constexpr (NY > 0) rows_to_lds<NY>(yv, ys, lane);
+        rows.to_lds(zs, zs + NQ * WAVE, ys, lane);
     }
     __syncthreads();
     const Img<SD>* __restrict__ S = (const Img<SD>*)lds;
@@ -388,14 +334,7 @@ __global__ __launch_bounds__(WAVE) void qp_converge_static_kernel(
         if (__ballot(active) == 0ull) break;
         double vt[N], st_sl[LY::NSA];
         const int st = qp_tick_static<SD>(S, T, tk, z, ysl, lane, active, slots, vt, st_sl, &hot, r > 0);
-        double step = 0.0;
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            double d = vt[j];
-            if (j < NQ && ca.max_speed > 0.0) d = fmax(fmin(d, ca.max_speed), -ca.max_speed);
-            vt[j] = d;
-            if (j < NQ) step = fmax(step, fabs(d) * ca.dt);
-        }
+        const double step = clamp_step_size<N, NQ>(vt, ca.max_speed, ca.dt);
         if (active) {
             worst = st > worst ? st : worst;
             if (st == 2) {                  // an infeasible tick: the state stays where it is
@@ -425,25 +364,18 @@ __global__ __launch_bounds__(WAVE) void qp_converge_static_kernel(
         z[j] = nan_or(z[j], nan_hi);
         v[j] = nan_or(v[j], nan_hi);
     }
-    __syncthreads();
-    state_to_lds<NQ, NX>(z, zs, xs, lane);
-    __syncthreads();
-    rows_from_lds<NQ>(q + b0 * NQ, rows_valid, zs, lane);
-    if constexpr (NX > 0) rows_from_lds<NX>(x + b0 * NX, rows_valid, xs, lane);
-    __syncthreads();
-    state_to_lds<NQ, NX>(v, zs, xs, lane);
-    if constexpr (NS > 0) {
-        double* so = slots + LY::O_SL * WAVE;
-        if (slack_out != nullptr) {
+    rows_out<NQ, NX>(z, q, x, w, zs, xs);
+    rows_out<NQ, NX>(v, dq, dx, w, zs, xs, [&]() __attribute__((always_inline)) {
+        if constexpr (NS > 0) {
+            double* so = slots + LY::O_SL * WAVE;
+            if (slack_out != nullptr) {
 #pragma unroll
-            for (int k = 0; k < NS; ++k) so[lane * NS + k] = nan_or(sl[k], nan_hi);
+                for (int k = 0; k < NS; ++k) so[lane * NS + k] = nan_or(sl[k], nan_hi);
+            }
         }
-    }
-    __syncthreads();
-    rows_from_lds<NQ>(dq + b0 * NQ, rows_valid, zs, lane);
-    if constexpr (NX > 0) rows_from_lds<NX>(dx + b0 * NX, rows_valid, xs, lane);
+    });
     if constexpr (NS > 0) {
-        if (slack_out != nullptr) rows_from_lds<NS>(slack_out + b0 * NS, rows_valid, slots + LY::O_SL * WAVE, lane);
+        if (slack_out != nullptr) rows_from_lds<NS>(slack_out + b0 * NS, w.rows_store, slots + LY::O_SL * WAVE, lane);
     }
     if (status_out != nullptr && valid) status_out[b0 + lane] = worst;
 }
@@ -471,15 +403,8 @@ inline hipError_t launch_qp_converge_static(const void* d_img, const TickArgs& t
         if (SD.n_x != 0 && (x == nullptr || dx == nullptr)) return hipErrorInvalidValue;
         const long long blocks = (B + WAVE - 1) / WAVE;
         if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-        const size_t shmem = converge_lds_bytes<SD>();
-        if (shmem > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(converge_kernel_ptr<SD>(), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)shmem);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((qp_converge_static_kernel<SD>), dim3((unsigned)blocks), dim3(WAVE), shmem, stream, d_img, q, y,
-                           dq, slack, status, B, tk, x, dx, ca);
-        return hipGetLastError();
+        return launch_with_lds(qp_converge_static_kernel<SD>, (unsigned)blocks, WAVE, converge_lds_bytes<SD>(), stream,
+                               d_img, q, y, dq, slack, status, B, tk, x, dx, ca);
     }
 }
 #endif
@@ -495,12 +420,7 @@ inline long long converge_info(int what)
         if constexpr (!converge_fits<SD>()) {
             return -1;
         } else {
-            hipFuncAttributes fa;
-            if (hipFuncGetAttributes(&fa, converge_kernel_ptr<SD>()) != hipSuccess) {
-                (void)hipGetLastError();
-                return -1;
-            }
-            return (long long)fa.localSizeBytes;
+            return kernel_scratch_bytes(converge_kernel_ptr<SD>());
         }
     }
     return what == 0 ? LY::MT : what == 1 ? LY::MS : what == 2 ? (long long)converge_lds_bytes<SD>()

@@ -1,14 +1,14 @@
 // Rollouts that record their trajectory and read one target per tick (clik_pinv_rollout_batch_rec, include/clik.h; RollRec in
-// clik_device.hpp): the loops of clik_pinv_team.hpp and clik_pinv_kernels.hpp again, as bodies with a trailing parameter pack (empty: the
-// loop as it stands there; one RollRec: records and per-tick targets), the kernels that pass them one RollRec, and their
-// launchers.  A header of its own, included by the recording translation units only (casclik_amd/jit.py): the compiler's code
-// for a kernel depends on what else its translation unit declares - with these templates declared next to them, the rollouts
-// that record nothing fused their multiply-adds in another order, and their results are pinned to the tick kernels' (the
-// smoke test: q after one tick to 1e-12).
-// (pinv_rollout_static_body is written out once more, with a summary of every tick's state, in clik_rollout_summary.hpp: a change of
-// the loop here belongs there too.)
+// clik_device.hpp): the loops of clik_pinv_team.hpp and clik_pinv_kernels.hpp again, with one RollRec - records and per-tick
+// targets - and their launchers.  A header of its own, included by the on-demand translation units only (casclik_amd/jit.py):
+// the compiler's code for a kernel depends on what else its translation unit declares - with these templates declared next
+// to them, the rollouts that record nothing fused their multiply-adds in another order, and their results are pinned to the
+// tick kernels' (the smoke test: q after one tick to 1e-12).
+// The lane-per-instance loop (pinv_rollout_static_body) is the one text of the recording rollout and, with a hook that
+// folds every tick's state (clik_rollout_lane.hpp: NoTickHook), of the rollout that summarises its constraint values.
 #pragma once
 #include "clik_pinv_kernels.hpp"
+#include "clik_rollout_lane.hpp"
 namespace clik {
 
 // One record of a team rollout (RollRec): plain stores, nothing waits for them.  The state is replicated over the quad;
@@ -61,15 +61,14 @@ __device__ __forceinline__ void team_record(const RollRec& ra, const long long r
 // in registers (replicated over the quad).  stages = 1: explicit Euler; 4: classical Runge-Kutta with the
 // controller as the right-hand side (see pinv_rollout_static_kernel).  q is updated in place; dq / mode receive
 // the last tick (Runge-Kutta: the combined rate and the mode of the first stage).
-// REC: empty, or one RollRec (clik_device.hpp): records of the trajectory and one target row per tick.
-template <const ShapeDesc& SD, class IMGV, int STAGES, class... REC>
+// ra: records of the trajectory and one target row per tick (RollRec, clik_device.hpp).
+template <const ShapeDesc& SD, class IMGV, int STAGES>
 __device__ __forceinline__ void pinv_rollout_static_team_body(
     const void* __restrict__ img_g, double* __restrict__ q, const double* __restrict__ y,
     double* __restrict__ dq, int32_t* __restrict__ mode_out, const long long B,
-    const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed, const REC... rec)
+    const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed, const RollRec ra)
 {
     static_assert(STAGES == 1 || STAGES == 4, "explicit Euler or classical Runge-Kutta");
-    constexpr bool RECORD = sizeof...(REC) > 0;
     constexpr int stages = STAGES;
     static_assert(shape_team_ok(SD), "shape outside the team kernel's family");
     constexpr bool VALUES = !std::is_void<IMGV>::value;
@@ -142,20 +141,17 @@ __device__ __forceinline__ void pinv_rollout_static_team_body(
             if constexpr (2 * k + 1 < N) a1 = (r == k) ? zz[2 * k + 1] : a1;
         });
     };
-    [[maybe_unused]] RecClock clk;
+    RecClock clk;
     [[maybe_unused]] double ynext[NY > 0 ? NY : 1];
-    if constexpr (RECORD) {
-        clk.start(rec_of(rec...));
-        if constexpr (NY > 0) {
+    clk.start(ra);
+    if constexpr (NY > 0) {
 #pragma unroll
-            for (int k = 0; k < NY; ++k) ynext[k] = ydir[k];
-        }
+        for (int k = 0; k < NY; ++k) ynext[k] = ydir[k];
     }
 #pragma unroll 1
     for (int tick = 0; tick < n_ticks; ++tick) {
-        if constexpr (RECORD && NY > 0) {
+        if constexpr (NY > 0) {
             // per-tick target: the NEXT tick's row is requested here, a whole tick before it is used
-            const RollRec& ra = rec_of(rec...);
             if (ra.y_stride != 0) {
                 const double* yn = next_rows(y, ra, tick, n_ticks) + binst * NY;
 #pragma unroll
@@ -212,18 +208,15 @@ __device__ __forceinline__ void pinv_rollout_static_team_body(
         }
         acc_mode = mode0;
         }
-        if constexpr (RECORD) {
-            const RollRec& ra = rec_of(rec...);
-            if (clk.due(ra)) {
-                if (valid) team_record<N>(ra, clk.r * B + b0 + inst, r, z, vout, acc_mode);
-                ++clk.r;
-            }
-            if constexpr (NY > 0) {
+        if (clk.due(ra)) {
+            if (valid) team_record<N>(ra, clk.r * B + b0 + inst, r, z, vout, acc_mode);
+            ++clk.r;
+        }
+        if constexpr (NY > 0) {
 #pragma unroll
-                for (int k = 0; k < NY; ++k) {
-                    ydir[k] = ynext[k];
-                    if constexpr (!VALUES) ys[inst * NY + k] = ynext[k];
-                }
+            for (int k = 0; k < NY; ++k) {
+                ydir[k] = ynext[k];
+                if constexpr (!VALUES) ys[inst * NY + k] = ynext[k];
             }
         }
     }
@@ -237,14 +230,15 @@ __device__ __forceinline__ void pinv_rollout_static_team_body(
     }
 }
 
-// ... recording its trajectory / reading one target per tick (RollRec, clik_device.hpp)
+// (a body and a kernel that calls it, here and below, not one function: the compiler's code for the loop differs between
+// the two forms, and these kernels' code is held to what it was)
 template <const ShapeDesc& SD, class IMGV = void, int STAGES = 1>
 __global__ __launch_bounds__(TEAM_WAVES * WAVE) void pinv_rollout_static_team_rec_kernel(
     const void* __restrict__ img_g, double* __restrict__ q, const double* __restrict__ y,
     double* __restrict__ dq, int32_t* __restrict__ mode_out, const long long B,
     const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed, const RollRec rec)
 {
-    pinv_rollout_static_team_body<SD, IMGV, STAGES, RollRec>(img_g, q, y, dq, mode_out, B, tterms, n_ticks, dt, max_speed, rec);
+    pinv_rollout_static_team_body<SD, IMGV, STAGES>(img_g, q, y, dq, mode_out, B, tterms, n_ticks, dt, max_speed, rec);
 }
 
 // One record of a lane-per-instance rollout (RollRec): the lane stores its own rows with plain stores, nothing waits
@@ -282,15 +276,19 @@ __device__ __forceinline__ void lane_record(const RollRec& ra, const long long r
 // RK: classical Runge-Kutta (four controller evaluations per tick) instead of explicit Euler.  Two
 // instantiations, because the Runge-Kutta bookkeeping (start state and weighted sum of the stage velocities, kept
 // in LDS) would otherwise sit in the Euler loop's registers and push the widest stacks into scratch.
-// REC: empty, or one RollRec (clik_device.hpp): records of the trajectory and one target row per tick.
-template <const ShapeDesc& SD, bool RK, class... REC>
+// ra: records of the trajectory and one target row per tick (RollRec, clik_device.hpp).
+// WV: waves per block; they share ONE copy of the skill image, and every wave has a region of its own behind it:
+//   LDS: [skill image | wave 0: zs (N slots) ys (n_y slots) (Runge-Kutta: z0s, kss, N slots each) the hook's doubles | wave 1 ...]
+// REGIMG: the Euler loop reads the image from a register copy; otherwise from LDS in place, as the Runge-Kutta loop always
+// does (with the register copy the widest stacks spill there).
+// hook: see NoTickHook (clik_rollout_lane.hpp).
+template <const ShapeDesc& SD, bool RK, int WV, bool REGIMG, class HOOK>
 __device__ __forceinline__ void pinv_rollout_static_body(
     const void* __restrict__ img_g, double* __restrict__ q, const double* __restrict__ y,
     double* __restrict__ dq, int32_t* __restrict__ mode_out, const long long B,
     const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed,
-    double* __restrict__ x, double* __restrict__ dx, const REC... rec)
+    double* __restrict__ x, double* __restrict__ dx, const RollRec ra, HOOK& hook)
 {
-    constexpr bool RECORD = sizeof...(REC) > 0;
     // x / dx: virtual variables (path parameters, cart_on_track_1D...ipynb cells 56-60): integrated like the
     // robot variables, never clamped; unused (null) in skills without them.
     // Euler: the notebooks' loop.  Runge-Kutta: the controller as the right-hand side
@@ -299,63 +297,72 @@ __device__ __forceinline__ void pinv_rollout_static_body(
     extern __shared__ double lds[];
     constexpr int N = SD.n;
     constexpr int NX = SD.n_x, NQ = N - NX;
-    const int lane = threadIdx.x;
-    const long long b0 = (long long)blockIdx.x * WAVE;
-    const long long left = B - b0;
-    const int rows_valid = left < WAVE ? (int)left : WAVE;
-    const bool valid = lane < rows_valid;
+    constexpr int NY = SD.n_y > 0 ? SD.n_y : 0;
+    const WavePlace<WV> w(B);
+    const int lane = w.lane;
+    const long long b0 = w.b0;
+    const int rows_valid = w.rows_valid;
+    const bool valid = w.valid;
     double* zs = lds + StaticLayout<SD>::IMG_DOUBLES;
+    if constexpr (WV > 1) zs += w.wave * lane_wave_doubles<SD, RK>(HOOK::LDS_DOUBLES);
     double* xs = zs + NQ * WAVE;
     double* ys = zs + N * WAVE;
-    const Img<SD>* __restrict__ S = load_image<SD>(img_g, lds, lane);
-    {
-        double qv[NQ], xv[NX > 0 ? NX : 1], yv[SD.n_y > 0 ? SD.n_y : 1];
-        stage_load<NQ>(q + b0 * NQ, NQ, rows_valid, lane, qv);
-        if constexpr (NX > 0) stage_load<NX>(x + b0 * NX, NX, rows_valid, lane, xv);
-        if constexpr (SD.n_y > 0) stage_load<SD.n_y>(y + b0 * SD.n_y, SD.n_y, rows_valid, lane, yv);
-        rows_to_lds<NQ>(qv, zs, lane);
-        if constexpr (NX > 0) rows_to_lds<NX>(xv, xs, lane);
-        if constexpr (SD.n_y > 0) rows_to_lds<SD.n_y>(yv, ys, lane);
+    const Img<SD>* __restrict__ S = (const Img<SD>*)lds;
+    if constexpr (WV == 1) {
+        load_image<SD>(img_g, lds, lane);
+    } else {
+        // (the waves of a block share ONE copy of the image and load it together)
+        typedef double d2 __attribute__((ext_vector_type(2)));
+        const d2* src = (const d2*)img_g;
+        d2* dst = (d2*)lds;
+        for (int k = w.wave; k < StaticLayout<SD>::IMG_CHUNKS; k += WV) dst[k * WAVE + lane] = src[k * WAVE + lane];
     }
+    {
+        StagedRows<NQ, NX, NY> rows;
+        rows.load(q, x, y, w);
+        rows.to_lds(zs, xs, ys, lane);
+    }
+    hook.start(ys + (NY + (RK ? 2 * N : 0)) * WAVE, lane, valid, b0 + lane);
     __syncthreads();
     const int nts = S->n_tslots;
+    const double* ysl = ys + lane * NY;
     double z[N];
     state_from_lds<NQ, NX>(zs, xs, lane, z);
-    const Img<SD> Sreg = *S;                         // register copy, see pinv_solve_static_kernel
-    __builtin_amdgcn_sched_barrier(0);
+    [[maybe_unused]] Img<SD> Sreg;
+    if constexpr (REGIMG) {
+        Sreg = *S;                                   // register copy, see pinv_solve_static_kernel
+        __builtin_amdgcn_sched_barrier(0);
+    }
     double vout[N];
     int acc_mode = -1;
 #pragma unroll
     for (int j = 0; j < N; ++j) vout[j] = 0.0;
-    [[maybe_unused]] RecClock clk;
-    [[maybe_unused]] double ynext[SD.n_y > 0 ? SD.n_y : 1];
-    if constexpr (RECORD) clk.start(rec_of(rec...));
+    RecClock clk;
+    [[maybe_unused]] double ynext[NY > 0 ? NY : 1];
+    clk.start(ra);
     // per-tick target: the NEXT tick's block is requested at the top of a tick (coalesced, as the first one was) ...
     auto request_rows = [&](const int tick) __attribute__((always_inline)) {
-        if constexpr (RECORD && SD.n_y > 0) {
-            const RollRec& ra = rec_of(rec...);
+        if constexpr (NY > 0) {
             if (ra.y_stride != 0)
-                stage_load<SD.n_y>(next_rows(y, ra, tick, n_ticks) + b0 * SD.n_y, SD.n_y, rows_valid, lane, ynext);
+                stage_load<NY>(next_rows(y, ra, tick, n_ticks) + b0 * NY, NY, rows_valid, lane, ynext);
         }
     };
     // ... and replaces this tick's in LDS at its end, where the tick's record is stored too: every lane its own rows,
     // plain stores, nothing waits for them
     auto end_of_tick = [&]() __attribute__((always_inline)) {
-        if constexpr (RECORD) {
-            const RollRec& ra = rec_of(rec...);
-            if (clk.due(ra)) {
-                if (valid) lane_record<NQ, NX>(ra, clk.r * B + b0 + lane, z, vout, acc_mode);
-                ++clk.r;
-            }
-            if constexpr (SD.n_y > 0) {
-                if (ra.y_stride != 0) {
-                    rows_to_lds<SD.n_y>(ynext, ys, lane);
-                    __syncthreads();
-                }
+        if (clk.due(ra)) {
+            if (valid) lane_record<NQ, NX>(ra, clk.r * B + b0 + lane, z, vout, acc_mode);
+            ++clk.r;
+        }
+        if constexpr (NY > 0) {
+            if (ra.y_stride != 0) {
+                rows_to_lds<NY>(ynext, ys, lane);
+                __syncthreads();
             }
         }
     };
     if constexpr (!RK) {
+        const Img<SD>* __restrict__ Se = REGIMG ? &Sreg : S;       // (what the Euler tick reads)
 #pragma unroll 1
         for (int tick = 0; tick < n_ticks; ++tick) {
             request_rows(tick);
@@ -364,7 +371,8 @@ __device__ __forceinline__ void pinv_rollout_static_body(
             asm volatile("" ::: "memory");
             // time terms are read in place ([values | derivatives], 2*nts doubles per tick, never past them)
             const TickArgs& tk = *reinterpret_cast<const TickArgs*>(tterms + (size_t)tick * 2 * nts);
-            pinv_tick_static<SD>(&Sreg, tk, z, ys + lane * SD.n_y, lane, valid, vout, acc_mode);
+            hook.tick(S, tk, z, ysl, lane, tick, n_ticks, valid);
+            pinv_tick_static<SD>(Se, tk, z, ysl, lane, valid, vout, acc_mode);
 #pragma unroll
             for (int j = 0; j < N; ++j) {
                 double d = vout[j];
@@ -375,7 +383,7 @@ __device__ __forceinline__ void pinv_rollout_static_body(
             end_of_tick();
         }
     } else {
-        double* z0s = ys + SD.n_y * WAVE;       // [N][64] state at the start of the tick, then [N][64] sum of w_i k_i
+        double* z0s = ys + NY * WAVE;       // [N][64] state at the start of the tick, then [N][64] sum of w_i k_i
         double* kss = z0s + N * WAVE;
 #pragma unroll 1
         for (int tick = 0; tick < n_ticks; ++tick) {
@@ -386,13 +394,19 @@ __device__ __forceinline__ void pinv_rollout_static_body(
                 z0s[j * WAVE + lane] = z[j];
                 kss[j * WAVE + lane] = 0.0;
             }
+            if constexpr (HOOK::ACTIVE) {
+                // the tick's first stage: its time, the state before the tick
+                asm volatile("" ::: "memory");
+                const TickArgs& tk0 = *reinterpret_cast<const TickArgs*>(tterms + (size_t)tick * 4 * 2 * nts);
+                hook.tick(S, tk0, z, ysl, lane, tick, n_ticks, valid);
+            }
 #pragma unroll 1
             for (int st = 0; st < 4; ++st) {
                 asm volatile("" ::: "memory");
                 const TickArgs& tk = *reinterpret_cast<const TickArgs*>(tterms + ((size_t)tick * 4 + st) * 2 * nts);
                 // (the image is read from LDS in place: with the register copy of the Euler loop the widest stacks
                 // spill here)
-                pinv_tick_static<SD>(S, tk, z, ys + lane * SD.n_y, lane, valid, vout, acc_mode);
+                pinv_tick_static<SD>(S, tk, z, ysl, lane, valid, vout, acc_mode);
                 const double wgt = (st == 0 || st == 3) ? 1.0 : 2.0;
                 const double cnext = (st == 2) ? dt : 0.5 * dt;          // offset of the next stage's state
 #pragma unroll
@@ -413,16 +427,9 @@ __device__ __forceinline__ void pinv_rollout_static_body(
             end_of_tick();
         }
     }
-    __syncthreads();
-    state_to_lds<NQ, NX>(z, zs, xs, lane);
-    __syncthreads();
-    rows_from_lds<NQ>(q + b0 * NQ, rows_valid, zs, lane);
-    if constexpr (NX > 0) rows_from_lds<NX>(x + b0 * NX, rows_valid, xs, lane);
-    __syncthreads();
-    state_to_lds<NQ, NX>(vout, zs, xs, lane);
-    __syncthreads();
-    rows_from_lds<NQ>(dq + b0 * NQ, rows_valid, zs, lane);
-    if constexpr (NX > 0) rows_from_lds<NX>(dx + b0 * NX, rows_valid, xs, lane);
+    hook.finish(valid, n_ticks, b0 + lane);
+    rows_out<NQ, NX>(z, q, x, w, zs, xs);
+    rows_out<NQ, NX>(vout, dq, dx, w, zs, xs);
     if (mode_out != nullptr && valid) mode_out[b0 + lane] = acc_mode;
 }
 
@@ -434,20 +441,20 @@ __global__ __launch_bounds__(WAVE) CLIK_ROLL_ATTR void pinv_rollout_static_rec_k
     const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed,
     double* __restrict__ x, double* __restrict__ dx, const RollRec rec)
 {
-    pinv_rollout_static_body<SD, RK, RollRec>(img_g, q, y, dq, mode_out, B, tterms, n_ticks, dt, max_speed, x, dx, rec);
+    NoTickHook none;
+    pinv_rollout_static_body<SD, RK, 1, true>(img_g, q, y, dq, mode_out, B, tterms, n_ticks, dt, max_speed, x, dx, rec, none);
 }
 
 // ... and its on-device rollout (see pinv_rollout_static_kernel): state in registers from tick to tick, the rows
 // loaded once and stored once by the lane itself, no LDS (the Runge-Kutta bookkeeping lives in registers here: without
 // the image there is room)
-// REC: empty, or one RollRec (clik_device.hpp): records of the trajectory and one target row per tick.
-template <const ShapeDesc& SD, class IMGV, bool RK, class... REC>
+// ra: records of the trajectory and one target row per tick (RollRec, clik_device.hpp).
+template <const ShapeDesc& SD, class IMGV, bool RK>
 __device__ __forceinline__ void pinv_rollout_static_values_body(
     double* __restrict__ q, const double* __restrict__ y, double* __restrict__ dq, int32_t* __restrict__ mode_out,
     const long long B, const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed,
-    const REC... rec)
+    const RollRec ra)
 {
-    constexpr bool RECORD = sizeof...(REC) > 0;
     static_assert(SD.n_x == 0, "value-specialised lane kernel: robot variables only");
     constexpr int N = SD.n;
     constexpr Img<SD> Sval = IMGV::value;
@@ -466,20 +473,17 @@ __device__ __forceinline__ void pinv_rollout_static_values_body(
 #pragma unroll
     for (int j = 0; j < N; ++j) vout[j] = 0.0;
     // per-tick target (RollRec): the row lives in registers, and the NEXT tick's is requested at the top of a tick
-    [[maybe_unused]] RecClock clk;
+    RecClock clk;
     [[maybe_unused]] double ycur[SD.n_y > 0 ? SD.n_y : 1], ynext[SD.n_y > 0 ? SD.n_y : 1];
-    if constexpr (RECORD) {
-        clk.start(rec_of(rec...));
-        if constexpr (SD.n_y > 0) {
+    clk.start(ra);
+    if constexpr (SD.n_y > 0) {
 #pragma unroll
-            for (int k = 0; k < SD.n_y; ++k) ycur[k] = ynext[k] = ys[k];
-            ys = ycur;
-        }
+        for (int k = 0; k < SD.n_y; ++k) ycur[k] = ynext[k] = ys[k];
+        ys = ycur;
     }
 #pragma unroll 1
     for (int tick = 0; tick < n_ticks; ++tick) {
-        if constexpr (RECORD && SD.n_y > 0) {
-            const RollRec& ra = rec_of(rec...);
+        if constexpr (SD.n_y > 0) {
             if (ra.y_stride != 0) {
                 const double* yn = next_rows(y, ra, tick, n_ticks) + row * SD.n_y;
 #pragma unroll
@@ -526,16 +530,13 @@ __device__ __forceinline__ void pinv_rollout_static_values_body(
             }
             acc_mode = mode0;
         }
-        if constexpr (RECORD) {
-            const RollRec& ra = rec_of(rec...);
-            if (clk.due(ra)) {
-                if (valid) lane_record<N, 0>(ra, clk.r * B + inst, z, vout, acc_mode);
-                ++clk.r;
-            }
-            if constexpr (SD.n_y > 0) {
+        if (clk.due(ra)) {
+            if (valid) lane_record<N, 0>(ra, clk.r * B + inst, z, vout, acc_mode);
+            ++clk.r;
+        }
+        if constexpr (SD.n_y > 0) {
 #pragma unroll
-                for (int k = 0; k < SD.n_y; ++k) ycur[k] = ynext[k];
-            }
+            for (int k = 0; k < SD.n_y; ++k) ycur[k] = ynext[k];
         }
     }
     if (valid) {
@@ -548,13 +549,12 @@ __device__ __forceinline__ void pinv_rollout_static_values_body(
     }
 }
 
-// ... recording its trajectory / reading one target per tick (RollRec, clik_device.hpp)
 template <const ShapeDesc& SD, class IMGV, bool RK>
 __global__ __launch_bounds__(WAVE) CLIK_OCC_ATTR void pinv_rollout_static_values_rec_kernel(
     double* __restrict__ q, const double* __restrict__ y, double* __restrict__ dq, int32_t* __restrict__ mode_out,
     const long long B, const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed, const RollRec rec)
 {
-    pinv_rollout_static_values_body<SD, IMGV, RK, RollRec>(q, y, dq, mode_out, B, tterms, n_ticks, dt, max_speed, rec);
+    pinv_rollout_static_values_body<SD, IMGV, RK>(q, y, dq, mode_out, B, tterms, n_ticks, dt, max_speed, rec);
 }
 
 // The recording / per-tick-target instantiations of the rollouts above (a.roll_rec, clik_pinv_rollout_batch_rec).  They
@@ -567,31 +567,23 @@ inline hipError_t launch_rollout_values_rec(const LaunchArgs& a, const double* d
 {
     if (a.roll_rec == nullptr) return hipErrorInvalidValue;
     const RollRec rr = *a.roll_rec;
+    const bool rk = a.roll_stages == 4;
     switch (pinv_select(SD, a.policy, B, PinvOp::rollout)) {
     case PinvVariant::team4v:
         if constexpr (shape_team_ok(SD)) {
             const unsigned grid = (unsigned)((B + TEAM_INST - 1) / TEAM_INST);
-            if (a.roll_stages == 4)
-                hipLaunchKernelGGL((pinv_rollout_static_team_rec_kernel<SD, IMGV, 4>), dim3(grid),
-                                   dim3(TEAM_WAVES * WAVE), team_rollout_lds_bytes<SD>(true), stream, nullptr, q, y, dq, mode,
+            return launch_with_lds(rk ? pinv_rollout_static_team_rec_kernel<SD, IMGV, 4>
+                                      : pinv_rollout_static_team_rec_kernel<SD, IMGV, 1>,
+                                   grid, TEAM_WAVES * WAVE, team_rollout_lds_bytes<SD>(true), stream, nullptr, q, y, dq, mode,
                                    B, d_tterms, n_ticks, dt, max_speed, rr);
-            else
-                hipLaunchKernelGGL((pinv_rollout_static_team_rec_kernel<SD, IMGV, 1>), dim3(grid),
-                                   dim3(TEAM_WAVES * WAVE), team_rollout_lds_bytes<SD>(true), stream, nullptr, q, y, dq, mode,
-                                   B, d_tterms, n_ticks, dt, max_speed, rr);
-            return hipGetLastError();
         }
         break;
     case PinvVariant::lanev:
         if constexpr (shape_value_lane_ok(SD)) {
             const unsigned grid = (unsigned)((B + WAVE - 1) / WAVE);
-            if (a.roll_stages == 4)
-                hipLaunchKernelGGL((pinv_rollout_static_values_rec_kernel<SD, IMGV, true>), dim3(grid), dim3(WAVE), 0,
-                                   stream, q, y, dq, mode, B, d_tterms, n_ticks, dt, max_speed, rr);
-            else
-                hipLaunchKernelGGL((pinv_rollout_static_values_rec_kernel<SD, IMGV, false>), dim3(grid), dim3(WAVE), 0,
-                                   stream, q, y, dq, mode, B, d_tterms, n_ticks, dt, max_speed, rr);
-            return hipGetLastError();
+            return launch_with_lds(rk ? pinv_rollout_static_values_rec_kernel<SD, IMGV, true>
+                                      : pinv_rollout_static_values_rec_kernel<SD, IMGV, false>,
+                                   grid, WAVE, 0, stream, q, y, dq, mode, B, d_tterms, n_ticks, dt, max_speed, rr);
         }
         break;
     default:
@@ -607,36 +599,21 @@ inline hipError_t launch_rollout_static_rec(const LaunchArgs& a, const double* d
 {
     if (a.roll_rec == nullptr) return hipErrorInvalidValue;
     const RollRec rr = *a.roll_rec;
+    const bool rk = a.roll_stages == 4;
     const unsigned grid = (unsigned)((B + WAVE - 1) / WAVE);
     if constexpr (shape_team_ok(SD)) {
         PinvPolicy p = a.policy;
         p.values_attached = false;  // (see launch_solve_static)
-        if (pinv_select(SD, p, B, PinvOp::rollout) == PinvVariant::team4) {
-            if (a.roll_stages == 4)
-                hipLaunchKernelGGL((pinv_rollout_static_team_rec_kernel<SD, void, 4>), dim3(grid),
-                                   dim3(TEAM_WAVES * WAVE), team_rollout_lds_bytes<SD>(), stream, a.dImg, q, y, dq, mode, B,
+        if (pinv_select(SD, p, B, PinvOp::rollout) == PinvVariant::team4)
+            return launch_with_lds(rk ? pinv_rollout_static_team_rec_kernel<SD, void, 4>
+                                      : pinv_rollout_static_team_rec_kernel<SD, void, 1>,
+                                   grid, TEAM_WAVES * WAVE, team_rollout_lds_bytes<SD>(), stream, a.dImg, q, y, dq, mode, B,
                                    d_tterms, n_ticks, dt, max_speed, rr);
-            else
-                hipLaunchKernelGGL((pinv_rollout_static_team_rec_kernel<SD, void, 1>), dim3(grid),
-                                   dim3(TEAM_WAVES * WAVE), team_rollout_lds_bytes<SD>(), stream, a.dImg, q, y, dq, mode, B,
-                                   d_tterms, n_ticks, dt, max_speed, rr);
-            return hipGetLastError();
-        }
     }
-    if (a.roll_stages == 4) {
-        const size_t shmem = static_lds_bytes<SD>(a.ny) + (size_t)2 * SD.n * WAVE * sizeof(double);
-        if (shmem > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)pinv_rollout_static_rec_kernel<SD, true>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((pinv_rollout_static_rec_kernel<SD, true>), dim3(grid), dim3(WAVE), shmem, stream,
-                           a.dImg, q, y, dq, mode, B, d_tterms, n_ticks, dt, max_speed, a.roll_x, a.roll_dx, rr);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((pinv_rollout_static_rec_kernel<SD, false>), dim3(grid), dim3(WAVE), static_lds_bytes<SD>(a.ny),
-                       stream, a.dImg, q, y, dq, mode, B, d_tterms, n_ticks, dt, max_speed, a.roll_x, a.roll_dx, rr);
-    return hipGetLastError();
+    const size_t shmem = static_lds_bytes<SD>(a.ny) + (rk ? (size_t)2 * SD.n * WAVE * sizeof(double) : 0);
+    return launch_with_lds(rk ? pinv_rollout_static_rec_kernel<SD, true> : pinv_rollout_static_rec_kernel<SD, false>, grid,
+                           WAVE, shmem, stream, a.dImg, q, y, dq, mode, B, d_tterms, n_ticks, dt, max_speed, a.roll_x,
+                           a.roll_dx, rr);
 }
 
 }  // namespace clik

@@ -1,14 +1,14 @@
 // Rollouts that record their trajectory and read one target per tick (clik_qp_rollout_batch_rec, include/clik.h; RollRec in
-// clik_device.hpp): the loops of clik_qp_static.hpp again, as bodies with a trailing parameter pack (empty: the
-// loop as it stands there; one RollRec: records and per-tick targets), the kernels that pass them one RollRec, and their
-// launchers.  A header of its own, included by the recording translation units only (casclik_amd/jit.py): the compiler's code
+// clik_device.hpp): the loops of clik_qp_static.hpp again, with one RollRec - records and per-tick targets - and their
+// launchers.  A header of its own, included by the on-demand translation units only (casclik_amd/jit.py): the compiler's code
 // for a kernel depends on what else its translation unit declares - with these templates declared next to them, the rollouts
 // that record nothing fused their multiply-adds in another order, and their results are pinned to the tick kernels' (the
 // smoke test: q after one tick to 1e-12).
-// (qp_rollout_static_body is written out once more, with a summary of every tick's state, in clik_rollout_summary.hpp: a change of
-// the loop here belongs there too.)
+// The lane-per-instance loop (qp_rollout_static_body) is the one text of the recording rollout and, with a hook that folds
+// every tick's state (clik_rollout_lane.hpp: NoTickHook), of the rollout that summarises its constraint values.
 #pragma once
 #include "clik_qp_static.hpp"
+#include "clik_rollout_lane.hpp"
 namespace clik {
 
 // One record of a QP rollout (RollRec): what a launch ending at this tick returns - the state, the clamped velocity and
@@ -48,14 +48,15 @@ __device__ __forceinline__ void qp_record(const RollRec& ra, const long long row
 
 // ... and its on-device rollout (see qp_rollout_static_kernel): state, working set and Runge-Kutta bookkeeping in
 // registers from tick to tick, rows loaded once and stored once by the lane itself
-// REC: empty, or one RollRec (clik_device.hpp): records of the trajectory and one target row per tick.
-template <const ShapeDesc& SD, class IMGV, bool RK, class... REC>
+// ra: records of the trajectory and one target row per tick (RollRec, clik_device.hpp).
+// (a body and a kernel that calls it, here and below, not one function: the compiler's code for the loop differs between
+// the two forms, and these kernels' code is held to what it was)
+template <const ShapeDesc& SD, class IMGV, bool RK>
 __device__ __forceinline__ void qp_rollout_static_box_values_body(
     double* __restrict__ q, const double* __restrict__ y, double* __restrict__ dq, double* __restrict__ slack_out,
     int32_t* __restrict__ status_out, const long long B, const double* __restrict__ tterms, const int n_ticks,
-    const double dt, const double max_speed, double* __restrict__ x, double* __restrict__ dx, const REC... rec)
+    const double dt, const double max_speed, double* __restrict__ x, double* __restrict__ dx, const RollRec ra)
 {
-    constexpr bool RECORD = sizeof...(REC) > 0;
     using LY = QpLayout<SD>;
     static_assert(LY::BOX, "box family only");
     constexpr int N = SD.n, NX = SD.n_x, NQ = N - NX, NS = LY::NS;
@@ -82,20 +83,17 @@ __device__ __forceinline__ void qp_rollout_static_box_values_body(
     int32_t hot = 0;
     int worst = 0;
     // per-tick target (RollRec): the row lives in registers, and the NEXT tick's is requested at the top of a tick
-    [[maybe_unused]] RecClock clk;
+    RecClock clk;
     [[maybe_unused]] double ycur[SD.n_y > 0 ? SD.n_y : 1], ynext[SD.n_y > 0 ? SD.n_y : 1];
-    if constexpr (RECORD) {
-        clk.start(rec_of(rec...));
-        if constexpr (SD.n_y > 0) {
+    clk.start(ra);
+    if constexpr (SD.n_y > 0) {
 #pragma unroll
-            for (int k = 0; k < SD.n_y; ++k) ycur[k] = ynext[k] = ysl[k];
-            ysl = ycur;
-        }
+        for (int k = 0; k < SD.n_y; ++k) ycur[k] = ynext[k] = ysl[k];
+        ysl = ycur;
     }
 #pragma unroll 1
     for (int tick = 0; tick < n_ticks; ++tick) {
-        if constexpr (RECORD && SD.n_y > 0) {
-            const RollRec& ra = rec_of(rec...);
+        if constexpr (SD.n_y > 0) {
             if (ra.y_stride != 0) {
                 const double* yn = next_rows(y, ra, tick, n_ticks) + row * SD.n_y;
 #pragma unroll
@@ -150,16 +148,13 @@ __device__ __forceinline__ void qp_rollout_static_box_values_body(
                 z[j] = okl ? fma(d, dt, z0[j]) : z0[j];
             }
         }
-        if constexpr (RECORD) {
-            const RollRec& ra = rec_of(rec...);
-            if (clk.due(ra)) {
-                if (valid) qp_record<NQ, NX, NS, LY::NSA>(ra, clk.r * B + inst, z, v, sl, worst);
-                ++clk.r;
-            }
-            if constexpr (SD.n_y > 0) {
+        if (clk.due(ra)) {
+            if (valid) qp_record<NQ, NX, NS, LY::NSA>(ra, clk.r * B + inst, z, v, sl, worst);
+            ++clk.r;
+        }
+        if constexpr (SD.n_y > 0) {
 #pragma unroll
-                for (int k = 0; k < SD.n_y; ++k) ycur[k] = ynext[k];
-            }
+            for (int k = 0; k < SD.n_y; ++k) ycur[k] = ynext[k];
         }
     }
     if (valid) {
@@ -193,7 +188,7 @@ __global__ __launch_bounds__(WAVE) void qp_rollout_static_box_values_rec_kernel(
     int32_t* __restrict__ status_out, const long long B, const double* __restrict__ tterms, const int n_ticks,
     const double dt, const double max_speed, double* __restrict__ x, double* __restrict__ dx, const RollRec rec)
 {
-    qp_rollout_static_box_values_body<SD, IMGV, RK, RollRec>(q, y, dq, slack_out, status_out, B, tterms, n_ticks, dt, max_speed, x, dx, rec);
+    qp_rollout_static_box_values_body<SD, IMGV, RK>(q, y, dq, slack_out, status_out, B, tterms, n_ticks, dt, max_speed, x, dx, rec);
 }
 
 // n_ticks of (QP tick -> clamp(+-max_speed) -> explicit Euler q += dq dt) in one launch: the host
@@ -203,26 +198,28 @@ __global__ __launch_bounds__(WAVE) void qp_rollout_static_box_values_rec_kernel(
 // RK: classical Runge-Kutta with the controller as the right-hand side (integration_methods.py:17-23; four QP
 // solves per tick, the working set hot-started from stage to stage, tterms holds four records per tick) instead of
 // explicit Euler; a tick with an infeasible stage leaves the state where it was.
-// REC: empty, or one RollRec (clik_device.hpp): records of the trajectory and one target row per tick.
-template <const ShapeDesc& SD, bool RK, class... REC>
+// ra: records of the trajectory and one target row per tick (RollRec, clik_device.hpp).
+// LDS: [QP image | the tick's slots (QpLayout) | Runge-Kutta: z0s, kss (N slots each) | the hook's doubles]
+// hook: see NoTickHook (clik_rollout_lane.hpp).
+template <const ShapeDesc& SD, bool RK, class HOOK>
 __device__ __forceinline__ void qp_rollout_static_body(
     const void* __restrict__ img_g, double* __restrict__ q, const double* __restrict__ y,
     double* __restrict__ dq, double* __restrict__ slack_out, int32_t* __restrict__ status_out, const long long B,
     const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed,
-    double* __restrict__ x, double* __restrict__ dx, const REC... rec)
+    double* __restrict__ x, double* __restrict__ dx, const RollRec ra, HOOK& hook)
 {
-    constexpr bool RECORD = sizeof...(REC) > 0;
     // x / dx: virtual variables, integrated like the robot variables and never clamped (null without them)
     extern __shared__ double lds[];
     using LY = QpLayout<SD>;
     constexpr int N = SD.n;
     constexpr int NX = SD.n_x, NQ = N - NX;
     constexpr int NS = LY::NS;
-    const int lane = threadIdx.x;
-    const long long b0 = (long long)blockIdx.x * WAVE;
-    const long long left = B - b0;
-    const int rows_valid = left < WAVE ? (int)left : WAVE;
-    const bool valid = lane < rows_valid;
+    constexpr int NY = SD.n_y > 0 ? SD.n_y : 0;
+    const WavePlace<1> w(B);
+    const int lane = w.lane;
+    const long long b0 = w.b0;
+    const int rows_valid = w.rows_valid;
+    const bool valid = w.valid;
     double* slots = lds + LY::IMG_DOUBLES;
     double* zs = slots + LY::O_Z * WAVE;
     double* ys = slots + LY::O_Y * WAVE;
@@ -232,22 +229,23 @@ __device__ __forceinline__ void qp_rollout_static_body(
         const d2* src = (const d2*)img_g;
 #pragma unroll
         for (int k = 0; k < LY::IMG_CHUNKS; ++k) img[k] = src[k * WAVE + lane];
-        double qv[NQ], xv[NX > 0 ? NX : 1], yv[SD.n_y > 0 ? SD.n_y : 1];
+        double qv[NQ], xv[NX > 0 ? NX : 1], yv[NY > 0 ? NY : 1];
         stage_load<NQ>(q + b0 * NQ, NQ, rows_valid, lane, qv);
         if constexpr (NX > 0) stage_load<NX>(x + b0 * NX, NX, rows_valid, lane, xv);
-        if constexpr (SD.n_y > 0) stage_load<SD.n_y>(y + b0 * SD.n_y, SD.n_y, rows_valid, lane, yv);
+        if constexpr (NY > 0) stage_load<NY>(y + b0 * NY, NY, rows_valid, lane, yv);
         d2* dst = (d2*)lds;
 #pragma unroll
         for (int k = 0; k < LY::IMG_CHUNKS; ++k) dst[k * WAVE + lane] = img[k];
         rows_to_lds<NQ>(qv, zs, lane);
         if constexpr (NX > 0) rows_to_lds<NX>(xv, zs + NQ * WAVE, lane);
-        if constexpr (SD.n_y > 0) rows_to_lds<SD.n_y>(yv, ys, lane);
+        if constexpr (NY > 0) rows_to_lds<NY>(yv, ys, lane);
     }
+    hook.start(slots + (LY::SLOTS + (RK ? 2 * N : 0)) * WAVE, lane, valid, b0 + lane);
     __syncthreads();
     const Img<SD>* __restrict__ S = (const Img<SD>*)lds;
     const QpTail* __restrict__ T = (const QpTail*)((const char*)lds + LY::TAIL_OFF);
     const int nts = S->n_tslots;
-    const double* ysl = ys + lane * SD.n_y;
+    const double* ysl = ys + lane * NY;
     double* xs = zs + NQ * WAVE;
     double z[N];
     state_from_lds<NQ, NX>(zs, xs, lane, z);
@@ -258,30 +256,26 @@ __device__ __forceinline__ void qp_rollout_static_body(
     for (int k = 0; k < LY::NSA; ++k) sl[k] = 0.0;
     int32_t hot = 0;
     int worst = 0;
-    [[maybe_unused]] RecClock clk;
-    [[maybe_unused]] double ynext[SD.n_y > 0 ? SD.n_y : 1];
-    if constexpr (RECORD) clk.start(rec_of(rec...));
+    RecClock clk;
+    [[maybe_unused]] double ynext[NY > 0 ? NY : 1];
+    clk.start(ra);
     // per-tick target: the NEXT tick's block is requested at the top of a tick (coalesced, as the first one was) and
     // replaces this tick's in LDS at its end, where the tick's record is stored too (see pinv_rollout_static_kernel)
     auto request_rows = [&](const int tick) __attribute__((always_inline)) {
-        if constexpr (RECORD && SD.n_y > 0) {
-            const RollRec& ra = rec_of(rec...);
+        if constexpr (NY > 0) {
             if (ra.y_stride != 0)
-                stage_load<SD.n_y>(next_rows(y, ra, tick, n_ticks) + b0 * SD.n_y, SD.n_y, rows_valid, lane, ynext);
+                stage_load<NY>(next_rows(y, ra, tick, n_ticks) + b0 * NY, NY, rows_valid, lane, ynext);
         }
     };
     auto end_of_tick = [&]() __attribute__((always_inline)) {
-        if constexpr (RECORD) {
-            const RollRec& ra = rec_of(rec...);
-            if (clk.due(ra)) {
-                if (valid) qp_record<NQ, NX, NS, LY::NSA>(ra, clk.r * B + b0 + lane, z, v, sl, worst);
-                ++clk.r;
-            }
-            if constexpr (SD.n_y > 0) {
-                if (ra.y_stride != 0) {
-                    rows_to_lds<SD.n_y>(ynext, ys, lane);
-                    __syncthreads();
-                }
+        if (clk.due(ra)) {
+            if (valid) qp_record<NQ, NX, NS, LY::NSA>(ra, clk.r * B + b0 + lane, z, v, sl, worst);
+            ++clk.r;
+        }
+        if constexpr (NY > 0) {
+            if (ra.y_stride != 0) {
+                rows_to_lds<NY>(ynext, ys, lane);
+                __syncthreads();
             }
         }
     };
@@ -291,6 +285,7 @@ __device__ __forceinline__ void qp_rollout_static_body(
             request_rows(tick);
             asm volatile("" ::: "memory");      // (keeps the image reads inside the loop, see pinv_rollout_static_kernel)
             const TickArgs& tk = *reinterpret_cast<const TickArgs*>(tterms + (size_t)tick * 2 * nts);
+            hook.tick(S, tk, z, ysl, lane, tick, n_ticks, valid);
             const int st = qp_tick_static<SD>(S, T, tk, z, ysl, lane, valid, slots, v, sl, &hot, tick > 0);
             worst = st > worst ? st : worst;
             const bool okl = st != 2;           // an infeasible tick leaves the state where it is
@@ -313,6 +308,12 @@ __device__ __forceinline__ void qp_rollout_static_body(
             for (int j = 0; j < N; ++j) {
                 z0s[j * WAVE + lane] = z[j];
                 kss[j * WAVE + lane] = 0.0;
+            }
+            if constexpr (HOOK::ACTIVE) {
+                // the tick's first stage: its time, the state before the tick
+                asm volatile("" ::: "memory");
+                const TickArgs& tk0 = *reinterpret_cast<const TickArgs*>(tterms + (size_t)tick * 4 * 2 * nts);
+                hook.tick(S, tk0, z, ysl, lane, tick, n_ticks, valid);
             }
             bool okl = true;
 #pragma unroll 1
@@ -341,29 +342,21 @@ __device__ __forceinline__ void qp_rollout_static_body(
             end_of_tick();
         }
     }
+    hook.finish(valid, n_ticks, b0 + lane);
     const unsigned bad = (worst == 2) ? 0x7ff80000u : 0u;      // (nan_or: the NaN of an infeasible instance, as bits)
-    __syncthreads();
-    state_to_lds<NQ, NX>(z, zs, xs, lane);
-    __syncthreads();
-    rows_from_lds<NQ>(q + b0 * NQ, rows_valid, zs, lane);
-    if constexpr (NX > 0) rows_from_lds<NX>(x + b0 * NX, rows_valid, xs, lane);
-    __syncthreads();
-    {
-        double vb[N];
+    rows_out<NQ, NX>(z, q, x, w, zs, xs);
+    double vb[N];
 #pragma unroll
-        for (int j = 0; j < N; ++j) vb[j] = nan_or(v[j], bad);
-        state_to_lds<NQ, NX>(vb, zs, xs, lane);
-    }
-    if constexpr (NS > 0) {
-        double* so = slots + LY::O_SL * WAVE;
-        if (slack_out != nullptr) {
+    for (int j = 0; j < N; ++j) vb[j] = nan_or(v[j], bad);
+    rows_out<NQ, NX>(vb, dq, dx, w, zs, xs, [&]() __attribute__((always_inline)) {
+        if constexpr (NS > 0) {
+            double* so = slots + LY::O_SL * WAVE;
+            if (slack_out != nullptr) {
 #pragma unroll
-            for (int k = 0; k < NS; ++k) so[lane * NS + k] = nan_or(sl[k], bad);
+                for (int k = 0; k < NS; ++k) so[lane * NS + k] = nan_or(sl[k], bad);
+            }
         }
-    }
-    __syncthreads();
-    rows_from_lds<NQ>(dq + b0 * NQ, rows_valid, zs, lane);
-    if constexpr (NX > 0) rows_from_lds<NX>(dx + b0 * NX, rows_valid, xs, lane);
+    });
     if constexpr (NS > 0) {
         if (slack_out != nullptr) rows_from_lds<NS>(slack_out + b0 * NS, rows_valid, slots + LY::O_SL * WAVE, lane);
     }
@@ -378,7 +371,8 @@ __global__ __launch_bounds__(WAVE) void qp_rollout_static_rec_kernel(
     const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed,
     double* __restrict__ x, double* __restrict__ dx, const RollRec rec)
 {
-    qp_rollout_static_body<SD, RK, RollRec>(img_g, q, y, dq, slack_out, status_out, B, tterms, n_ticks, dt, max_speed, x, dx, rec);
+    NoTickHook none;
+    qp_rollout_static_body<SD, RK>(img_g, q, y, dq, slack_out, status_out, B, tterms, n_ticks, dt, max_speed, x, dx, rec, none);
 }
 
 // The recording / per-tick-target instantiations of the two rollouts (clik_qp_rollout_batch_rec): in translation units

@@ -96,7 +96,7 @@ def test_the_monitor_kernel_stays_out_of_the_other_translation_units():
 # what the source stamp of every OTHER instantiation is made of: the kernel headers before this one existed
 _STAMP_HEADERS = ("clik_device.hpp", "clik_pinv_select.hpp", "clik_pinv_static.hpp", "clik_pinv_kernels.hpp",
                   "clik_pinv_team.hpp", "clik_qp_select.hpp", "clik_qp_static.hpp", "clik_qp_resident.hpp",
-                  "clik_pinv_rec.hpp", "clik_qp_rec.hpp", "clik_time.hpp")
+                  "clik_pinv_rec.hpp", "clik_qp_rec.hpp", "clik_rollout_lane.hpp", "clik_time.hpp")
 
 
 def test_existing_templates_keep_their_request_ids_and_cache_tags():
