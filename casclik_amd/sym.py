@@ -134,22 +134,41 @@ def _s_neg(a):
     return Scalar("neg", (a,))
 
 
-def _nan_outside(f):
-    """IEEE result like CasADi's (asin(2) is nan, not an exception)"""
+def _ieee(f, overflow=float("inf"), pole=None):
+    """``f`` of the math module with the IEEE result where Python raises, like CasADi's evaluator and the device code:
+    nan outside the domain (asin(2), log(-1), sqrt(-1), tan(inf)), ``overflow`` where the result is too large
+    (exp(800)), ``pole`` at a singularity that math reports as a domain error (log(0))"""
     def g(v):
         try:
             return f(v)
+        except OverflowError:
+            return overflow
         except ValueError:
-            return float("nan")
+            return pole if pole is not None and v == 0.0 else float("nan")
     return g
 
 
 _UNARY_NUMERIC = {
-    "sin": math.sin, "cos": math.cos, "sqrt": math.sqrt, "exp": math.exp,
-    "log": math.log, "fabs": abs, "tan": math.tan,
+    "sin": _ieee(math.sin), "cos": _ieee(math.cos), "sqrt": _ieee(math.sqrt), "exp": _ieee(math.exp),
+    "log": _ieee(math.log, pole=float("-inf")), "fabs": abs, "tan": _ieee(math.tan),
     "sign": lambda v: float(v > 0) - float(v < 0),
-    "asin": _nan_outside(math.asin), "acos": _nan_outside(math.acos), "atan": math.atan, "tanh": math.tanh,
+    "asin": _ieee(math.asin), "acos": _ieee(math.acos), "atan": math.atan, "tanh": math.tanh,
 }
+
+
+def _ieee_pow(a, b):
+    """a ** b as IEEE pow gives it (CasADi, the device): Python's ``**`` raises for 0 ** -1 and for a result too large,
+    and leaves the reals for a negative base with a fractional exponent"""
+    try:
+        return math.pow(a, b)
+    except OverflowError:
+        return float("-inf") if a < 0.0 and b % 2.0 == 1.0 else float("inf")
+    except ValueError:
+        if a == 0.0 and b < 0.0:        # a pole: the sign of the zero counts for an odd integer exponent only
+            return math.copysign(float("inf"), a) if b % 2.0 == 1.0 else float("inf")
+        return float("nan")
+
+
 # two-argument functions (casadi.atan2 / fmin / fmax: angle-type task errors, saturations)
 _BINARY_NUMERIC = {"atan2": math.atan2, "fmin": min, "fmax": max}
 
@@ -168,7 +187,7 @@ def _s_unary(op, a):
 
 def _s_pow(a, b):
     if a.is_const() and b.is_const():
-        return _c(a.value ** b.value)
+        return _c(_ieee_pow(a.value, b.value))
     return Scalar("pow", (a, b))
 
 
@@ -421,6 +440,9 @@ class MX(object):
 
     def __pow__(self, o):
         return _elementwise(_s_pow, self, o)
+
+    def __rpow__(self, o):
+        return _elementwise(_s_pow, o, self)
 
     def __matmul__(self, o):
         return mtimes(self, o)
@@ -1022,7 +1044,7 @@ def _eval_scalar(s, env, memo):
         elif op == "neg":
             r = -a[0]
         elif op == "pow":
-            r = a[0] ** a[1]
+            r = _ieee_pow(a[0], a[1])
         elif op in _BINARY_NUMERIC:
             r = _BINARY_NUMERIC[op](a[0], a[1])
         elif op == "norm2":

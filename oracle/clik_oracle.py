@@ -271,10 +271,25 @@ class ExprEvaluator(object):
                 first = (a[0].v <= a[1].v) if op == "fmin" else (a[0].v >= a[1].v)
                 r = Dual(np.where(first, a[0].v, a[1].v), np.where(first[:, None], a[0].d, a[1].d))
             elif op == "pow":
-                if np.any(a[1].d != 0.0):
-                    raise NotImplementedError("oracle: pow with variable exponent")
                 ex = a[1].v
-                r = Dual(a[0].v ** ex, a[0].d * (ex * a[0].v ** (ex - 1.0))[:, None])
+                val = a[0].v ** ex
+                dd = a[0].d * (ex * a[0].v ** (ex - 1.0))[:, None]
+                moving = np.any(a[1].d != 0.0, axis=1)
+                if moving.any():
+                    # a variable exponent: d = v (b da / a + log(a) db); the second term only where the exponent
+                    # depends on (t, z) - the logarithm of a negative base under a constant exponent is never asked for
+                    with np.errstate(divide="ignore", invalid="ignore"):
+                        term = (val * np.log(a[0].v))[:, None] * a[1].d
+                    dd = np.where(moving[:, None], dd + term, dd)
+                r = Dual(val, dd)
+            elif op in ("cmp_lt", "cmp_le", "cmp_eq", "cmp_ne"):
+                # a truth value, 0 or 1, that does not move with (t, z)
+                holds = {"cmp_lt": np.less, "cmp_le": np.less_equal, "cmp_eq": np.equal, "cmp_ne": np.not_equal}[op]
+                r = Dual(holds(a[0].v, a[1].v).astype(float), np.zeros((B, nd)))
+            elif op == "if_else":
+                # value and derivative of the branch the condition's VALUE selects (true: not 0), per instance
+                taken = a[0].v != 0.0
+                r = Dual(np.where(taken, a[1].v, a[2].v), np.where(taken[:, None], a[1].d, a[2].d))
             elif op == "norm2":
                 ss = np.zeros(B)
                 dd = np.zeros((B, nd))

@@ -1,5 +1,7 @@
 """Skills whose constraints lie outside the affine-in-features row table (they run as generated
 device code, casclik_amd/codegen.py); shared by the CPU code-generation tests and the GPU parity tests."""
+import numpy as np
+
 import casclik_amd as cc
 from casclik_amd import sym as cs
 
@@ -118,6 +120,53 @@ def dual_quaternion_skill(fk, which="Q_dist2", for_pinv=False):
               cc.VelocitySetConstraint(label="Joint_speed_limits", expression=q,
                                        set_min=-cs.vertcat([max_speed] * 6), set_max=cs.vertcat([max_speed] * 6))]
     return cc.SkillSpecification(label=which, time_var=t, robot_var=q, robot_vel_var=dq, constraints=cn)
+
+
+def ops_skill(parts=False):
+    """No robot: four variables q, a three-entry input y and the time, under the operations the other skills here never
+    emit - tan, log, pow in every form the emitter tells apart (a square, a root, an integer >= 3, a negative integer, a
+    fraction, a variable exponent, a constant base), sign, fabs, fmax, fmin, asin, acos, atan, atan2, tanh, if_else on
+    `<=` and on a logic_and - as one soft six-row equality and one soft four-row set.  The time sits inside a sin and
+    inside a tanh.  For q and y as ``ops_inputs`` draws them (0.15 <= |q_i| <= 2, y in [0.3, 1.7]) every logarithm,
+    root and fractional power has an argument of at least 0.5, asin / acos see +-0.9 at most, tan +-1.4.
+    ``parts``: (spec, (t, q, y), (equality expression, set expression))."""
+    t, q, y = cs.MX.sym("t"), cs.MX.sym("q", 4), cs.MX.sym("y", 3)
+    eq = cs.vertcat(0.2 * cs.tan(0.7 * q[0]) + (1.5 + 0.5 * q[2]) ** (1.0 + 0.2 * q[1]) - cs.sin(0.5 * t),
+                    cs.log(y[0] + q[1] * q[1]) + 0.1 * (2.5 + q[1]) ** 2.5 + cs.tanh(q[3] - 0.3 * t),
+                    (2.5 + q[3]) ** -2 + (2.5 + q[0]) ** 0.5 + 0.1 * q[2] ** 3,
+                    2.0 ** q[2] + (q[0] * y[1]) ** 2 + cs.sign(q[3]) * q[1],
+                    cs.fabs(q[2] * q[3]) + cs.fmax(q[0], q[1] * y[0]) + cs.fmin(q[2], q[3]),
+                    cs.asin(0.45 * q[0]) + cs.acos(0.45 * q[1]) + cs.atan(q[2] * y[2]) + cs.atan2(q[3], q[0]))
+    st = cs.vertcat(cs.if_else(q[0] <= q[1], q[2] * y[0], cs.sin(q[3])),
+                    cs.if_else(cs.logic_and(q[0] < q[2], q[1] != q[3]), cs.log(y[2] + q[0] * q[0]), cs.tan(0.3 * q[1])),
+                    cs.tanh(q[1] - y[1]) * q[0],
+                    q[0] / (y[1] + q[1] * q[1]) + 0.1 * cs.sin(0.5 * t) * q[3])
+    cn = [cc.EqualityConstraint("ops_eq", eq, gain=1.5, priority=1, constraint_type="soft"),
+          cc.SetConstraint("ops_set", st, set_min=-0.5 * np.ones(4), set_max=0.5 * np.ones(4), gain=2.0, priority=0,
+                           constraint_type="soft")]
+    spec = cc.SkillSpecification("ops", t, q, input_var=y, constraints=cn)
+    return (spec, (t, q, y), (eq, st)) if parts else spec
+
+
+def ops_inputs(B, seed, t=0.0):
+    """(Q [B, 4], Y [B, 3]) for ``ops_skill``, drawn as the ops_* pools of function_cases.py are, every row at least
+    ``function_cases.SWITCH_MARGIN`` away from each switch of the skill's expressions at time ``t`` (a row that is not
+    is drawn again; the stream is fixed by the seed)"""
+    import function_cases as fc
+    _, sym, exprs = ops_skill(parts=True)
+    fn = cs.Function("ops_switches", list(sym), list(exprs))
+    rng = np.random.default_rng(seed)
+    Q, Y = np.empty((B, 4)), np.empty((B, 3))
+    for b in range(B):
+        while True:
+            Q[b] = rng.uniform(0.15, 2.0, 4) * rng.choice([-1.0, 1.0], 4)
+            Y[b] = rng.uniform(0.3, 1.7, 3)
+            try:
+                fc.assert_no_switch_nearby(fn, (t, Q[b], Y[b]))
+                break
+            except AssertionError:
+                continue
+    return Q, Y
 
 
 def random_expression(rng, leaves, depth, angles=False):

@@ -7,6 +7,20 @@ project's own words: 'fk_d' expansion, three outputs, an input nothing reads), `
 if_else, exp and tanh) and ``wide`` (a 14-column, a 3 x 2 matrix and a 1-entry input: index mapping, even and odd
 widths).
 
+Five more hold what those four never emit.  ``ops_pow``, ``ops_libm`` and ``ops_sel`` together hold every operation
+``codegen.TaskEmitter._op`` emits - tan, log, pow with exponent 2, 0.5, 5, -3, 2.5, a variable exponent and a constant
+base, sign, fabs, fmax, fmin, asin, acos, atan, atan2, tanh, exp, sqrt, division, negation, norm_2, if_else on each of the
+four comparisons, on logic_and / logic_or / logic_not and on a product - each as a value column and its Jacobians with
+respect to both inputs (three functions: inputs together and the widest output stay below DeviceFunction's 80 entries).
+``trig`` is ``[sin x, cos x]``, that is ``sincos_joint`` alone, on a pool of its own: 0, +-5e-324, +-1e-310, +-1e-300,
++-1e-8, the nearest double to k pi / 2 and both its neighbours for k = 1 ... 64 and 111 further k up to 63661, +-1e5 (the last
+argument of the straight-line path), the next double, 1e5 + 1, 1e6, 1e9, 1e15, 2^53, 1e22 and 1e300, each with both signs,
+the rest uniform in +-pi and in +-1e5.  ``ties`` holds pure selections AT their switches - fmin / fmax of equal inputs
+and of neighbouring doubles with their derivatives, sign and the derivative of fabs at +0.0, the four comparisons on
+equal inputs, if_else on 0.0 and 0.3: it bypasses the switch-margin check, every bound of it is 0, and it is compared
+bit for bit, also with its outputs written out by hand (``ties_expected``).  There is no negative zero in it: device code
+is built with -fno-signed-zeros.  (``edges``, not among ``NAMES``: finite inputs with infinite or exact results.)
+
 The test points are one pool per function, ``[R_MAX, B_MAX, ...]`` from a fixed seed; every shape a test uses is the
 leading ``[:R, :B]`` corner of it, so the host reference is computed once.
 
@@ -27,7 +41,12 @@ products on the device (``__builtin_powi``): local max(4, |n|) u |v|.  Fused mul
 An output entry passes when |dev - host| <= 2 (bound_dev + bound_host): both sides get the same bound (the host's libm
 is at least as accurate as assumed, and its numpy forward kinematics multiplies the same matrices in the same order as
 the written-out chain), and the factor 2 covers the truncation of the bound to first order.  ``exact_eval`` (mpmath, 40
-digits) checks the reference side alone against the rule: |host - exact| <= 2 bound.
+digits) checks the reference side alone against the rule: |host - exact| <= 2 bound.  The cases of ``EXACT`` (``ops_*``,
+``trig``) hold the DEVICE to that rule as well, |device - exact| <= 2 bound, the exact values computed once per case
+(``exact_reference``).  Measured on one MI355X (profiles/function_batch.md): worst ratio 0.492 / 0.386 / 0.497 for
+``ops_pow`` / ``ops_libm`` / ``ops_sel`` and 0.198 for ``trig`` (sincos_joint: 0.91 ulp for sin and 0.93 ulp for cos up to
+1e5 rad, 0.43 and 0.52 ulp on the library path beyond), so no operation's local term (``LOCAL_ULP``) was raised above the
+2 ulp.
 """
 import functools
 import math
@@ -39,11 +58,27 @@ from casclik_amd import sym as cs
 
 U = 2.0 ** -53
 TINY = 2.0 ** -1022
-NAMES = ["tool", "manip", "pend", "wide"]
+OPS = ["ops_pow", "ops_libm", "ops_sel"]
+NAMES = ["tool", "manip", "pend", "wide"] + OPS + ["trig", "ties"]
+EXACT = OPS + ["trig"]                  # held to |device - exact| <= 2 bound as well
 R_MAX, B_MAX = 3, 257
 SHAPES = [(R, B) for R in (1, 3) for B in (1, 63, 64, 65, 257)]
+# the one case whose pool is not [R_MAX, B_MAX]: the listed points of `trig` alone are more than 3 x 257
+_LEAD = {"trig": (3, 449)}
 SWITCH_MARGIN = 1e-6
 _LIBM = ("sin", "cos", "exp", "log", "tan", "atan", "atan2", "asin", "acos", "tanh")
+# the local term of a library function and of pow with a non-integer exponent, in ulp (module text)
+LOCAL_ULP = dict.fromkeys(_LIBM + ("pow",), 2.0)
+
+
+def lead(name):
+    """(R, B) of a case's pool"""
+    return _LEAD.get(name, (R_MAX, B_MAX))
+
+
+def shapes(name):
+    """the (R, B) corners of its pool a case is run at: SHAPES, ending at the pool's own B"""
+    return [(R, B) for R in (1, 3) for B in sorted({1, 63, 64, 65, lead(name)[1]})]
 
 
 @functools.lru_cache(maxsize=None)
@@ -88,7 +123,81 @@ def make(name):
             for j in range(2):
                 acc = acc + (1.0 + i + 3.0 * j) * M[i, j]
         return cs.Function("wide", [a, M, s], [col, acc])
+    if name in OPS:
+        # a: 4 entries of either sign, 0.15 <= |a_i| <= 2; b: 3 entries in [0.3, 1.7] (`pool`).  Arguments of log and
+        # sqrt and the bases of non-integer powers are >= 0.3, asin / acos see +-0.9 at most, tan +-1.4.
+        a, b = cs.MX.sym("a", 4), cs.MX.sym("b", 3)
+        if name == "ops_pow":
+            rows = [cs.tan(0.7 * a[0]), cs.log(b[0] + b[1] * b[1]), b[0] ** b[1], b[1] ** 2.5, b[2] ** -3,
+                    (2.5 + a[1]) ** 0.5, a[0] ** 5, 2.0 ** a[2], cs.sign(a[3]) * a[0], cs.fabs(a[2] * a[3]),
+                    cs.fmax(a[0], a[1] * b[0]), cs.fmin(a[2], a[3]), (b[0] + a[3] * a[3]) ** 2,
+                    (b[1] + 0.5) ** (a[1] * b[2])]
+        elif name == "ops_libm":
+            rows = [cs.asin(0.45 * a[0]), cs.acos(0.45 * a[1]), cs.atan(a[2] * b[2]), cs.atan2(a[3], a[0]),
+                    cs.tanh(a[1] - b[1]), cs.exp(-a[2] * a[2]), cs.sqrt(b[0] + a[3] * a[3]), a[0] / (b[1] + a[1] * a[1]),
+                    -a[3] * cs.cos(a[0]), cs.sin(a[1] * b[1]) * b[2], cs.norm_2(cs.vertcat(a[0], a[1], b[2])),
+                    cs.log(b[2]) * cs.tan(0.3 * a[1])]
+        else:
+            rows = [cs.if_else(a[0] <= a[1], a[2] * b[0], cs.sin(a[3])),
+                    cs.if_else(cs.logic_and(a[0] < a[2], a[1] != a[3]), cs.log(b[2]), cs.tan(0.3 * a[1])),
+                    cs.if_else(a[2] == a[3], 1.0, b[0] * a[2]),
+                    cs.if_else(cs.logic_or(a[0] > 0.0, cs.logic_not(a[1] >= 0.0)), a[0] * a[1], b[1]),
+                    cs.if_else(a[0] < a[2], cs.exp(a[1]), b[1] * b[2]),
+                    cs.if_else(a[1] != a[3], a[0] * b[2], cs.cos(a[2])),
+                    cs.if_else(a[1] * b[0], a[2] / b[1], a[3]),             # (a condition that is no comparison)
+                    cs.if_else(cs.logic_not(a[2] < a[3]), cs.fmin(a[0], b[0]), cs.fmax(a[1] * a[1], b[1]))]
+        col = cs.vertcat(*rows)
+        return cs.Function(name, [a, b], [col, cs.jacobian(col, a), cs.jacobian(col, b)])
+    if name == "trig":
+        x = cs.MX.sym("x")
+        return cs.Function("trig", [x], [cs.vertcat(cs.sin(x), cs.cos(x))])
+    if name == "ties":
+        x, z, w, c = cs.MX.sym("x", 2), cs.MX.sym("z"), cs.MX.sym("w", 2), cs.MX.sym("c", 2)
+        col = cs.vertcat(cs.fmin(x[0], x[1]), cs.fmax(x[0], x[1]), cs.sign(z), cs.if_else(x[0] <= x[1], w[0], w[1]),
+                         cs.if_else(x[0] == x[1], w[0], w[1]), cs.if_else(x[0] != x[1], w[0], w[1]),
+                         cs.if_else(x[0] < x[1], w[0], w[1]), cs.if_else(c[0], w[0], w[1]), cs.if_else(c[1], w[0], w[1]))
+        return cs.Function("ties", [x, z, w, c], [col, cs.jacobian(col[:2], x), cs.jacobian(cs.fabs(z), z)])
+    if name == "edges":
+        # (not among NAMES: finite inputs whose results are infinite or exact - no bound applies, compared by bits)
+        x = cs.MX.sym("x", 5)
+        return cs.Function("edges", [x], [cs.vertcat(cs.log(x[0]), cs.exp(x[1]), 1.0 / x[2], cs.tanh(x[3]), x[4] ** -1)])
     raise KeyError(name)
+
+
+EDGE_POINTS = np.array([[0.0, 800.0, 0.0, 1e3, 0.0], [1.0, 0.0, 2.0, 0.0, 4.0], [0.0, -800.0, 0.0, -1e3, 0.0]])
+EDGE_VALUES = np.array([[-np.inf, np.inf, np.inf, 1.0, np.inf], [0.0, 1.0, 0.5, 0.0, 0.25],
+                        [-np.inf, 0.0, np.inf, -1.0, np.inf]])
+
+
+def ties_expected(args):
+    """the outputs of ``ties`` at one point, written out by hand: CasADi's rules (fmin / fmax give the FIRST argument's
+    derivative where it is the one taken, ties included; sign(0) = 0 and so is the derivative of fabs there; a
+    condition counts as true when it is not 0)"""
+    x, z, w, c = (np.asarray(v, dtype=float).reshape(-1) for v in args)
+    assert z[0] == 0.0
+
+    def pick(cond):
+        return w[0] if cond else w[1]
+    le, ge = x[0] <= x[1], x[0] >= x[1]
+    col = [x[0] if le else x[1], x[0] if ge else x[1], 0.0, pick(le), pick(x[0] == x[1]), pick(x[0] != x[1]),
+           pick(x[0] < x[1]), pick(c[0] != 0.0), pick(c[1] != 0.0)]
+    return [np.array(col).reshape(-1, 1), np.array([[float(le), float(not le)], [float(ge), float(not ge)]]),
+            np.zeros((1, 1))]
+
+
+def _trig_points():
+    """the listed arguments of ``trig`` (module text)"""
+    import mpmath
+    mp = mpmath.mp.clone()
+    mp.dps = 60
+    inf = float("inf")
+    pts = [5e-324, 1e-310, 1e-300, 1e-8]
+    ks = sorted(set(range(1, 65)) | {int(round(k)) for k in np.geomspace(65.0, 63661.0, 110)} | {63660, 63661})
+    for k in ks:
+        m = float(mp.mpf(k) * mp.pi / 2)                      # (the nearest double to k pi / 2)
+        pts += [m, float(np.nextafter(m, inf)), float(np.nextafter(m, -inf))]
+    pts += [1e5, float(np.nextafter(1e5, inf)), 1e5 + 1.0, 1e6, 1e9, 1e15, 2.0 ** 53, 1e22, 1e300]
+    return np.array([0.0] + pts + [-p for p in pts])
 
 
 @functools.lru_cache(maxsize=None)
@@ -98,17 +207,36 @@ def get(name):
 
 @functools.lru_cache(maxsize=None)
 def pool(name):
-    """the test points of a case: one array per input, ``[R_MAX, B_MAX, *value dims]`` (a 1-entry input: ``[R_MAX,
-    B_MAX]``), fixed seed"""
-    rng = np.random.default_rng({"tool": 11, "manip": 12, "pend": 13, "wide": 14}[name])
-    lead = (R_MAX, B_MAX)
+    """the test points of a case: one array per input, ``[*lead(name), *value dims]`` (a 1-entry input:
+    ``[*lead(name)]``), fixed seed"""
+    rng = np.random.default_rng({"tool": 11, "manip": 12, "pend": 13, "wide": 14, "ops_pow": 15, "ops_libm": 16,
+                                 "ops_sel": 17, "trig": 18, "ties": 19}[name])
+    shape = lead(name)
+    if name in OPS:
+        return (rng.uniform(0.15, 2.0, shape + (4,)) * rng.choice([-1.0, 1.0], shape + (4,)),
+                rng.uniform(0.3, 1.7, shape + (3,)))
+    if name == "trig":
+        # the listed points, the rest half uniform in +-pi and half in +-1e5, in an order that gives every corner of
+        # the pool some of each
+        pts = _trig_points()
+        rest = shape[0] * shape[1] - len(pts)
+        assert rest >= 200, rest
+        x = np.concatenate([pts, rng.uniform(-math.pi, math.pi, rest // 2), rng.uniform(-1e5, 1e5, rest - rest // 2)])
+        return (rng.permutation(x).reshape(shape),)
+    if name == "ties":
+        # x_1 is x_0 (instance 0, 3, ...), the next double above it (1, 4, ...) or below it (2, 5, ...)
+        x0 = rng.uniform(-2.0, 2.0, shape)
+        step = np.array([0.0, np.inf, -np.inf])[np.arange(shape[1]) % 3]
+        x1 = np.where(step == 0.0, x0, np.nextafter(x0, step))
+        return (np.stack([x0, x1], axis=-1), np.zeros(shape), rng.uniform(-2.0, 2.0, shape + (2,)),
+                np.broadcast_to(np.array([0.0, 0.3]), shape + (2,)).copy())
     if name == "tool":
-        return (rng.uniform(-2.8, 2.8, lead + (6,)),)
+        return (rng.uniform(-2.8, 2.8, shape + (6,)),)
     if name == "manip":
-        return (rng.uniform(0.0, 80.0, lead), rng.uniform(-2.8, 2.8, lead + (6,)))
+        return (rng.uniform(0.0, 80.0, shape), rng.uniform(-2.8, 2.8, shape + (6,)))
     if name == "pend":
-        return (rng.uniform(-3.0, 3.0, lead + (2,)), rng.uniform(-1.5, 1.5, lead + (2,)))
-    return (rng.uniform(-2.0, 2.0, lead + (14,)), rng.uniform(-1.0, 1.0, lead + (3, 2)), rng.uniform(0.5, 2.0, lead))
+        return (rng.uniform(-3.0, 3.0, shape + (2,)), rng.uniform(-1.5, 1.5, shape + (2,)))
+    return (rng.uniform(-2.0, 2.0, shape + (14,)), rng.uniform(-1.0, 1.0, shape + (3, 2)), rng.uniform(0.5, 2.0, shape))
 
 
 def point(name, r, b):
@@ -209,7 +337,7 @@ def running_bound(fn, args):
         elif op == "sqrt":
             b = U * abs(v) + e[0] / (2.0 * abs(v))
         elif op in _LIBM:
-            local = 4.0 * U * max(abs(v), TINY)
+            local = 2.0 * LOCAL_ULP[op] * U * max(abs(v), TINY)
             if op == "sin":
                 b = local + abs(math.cos(a[0])) * e[0]
             elif op == "cos":
@@ -230,7 +358,9 @@ def running_bound(fn, args):
                 b = local + (abs(a[1]) * e[0] + abs(a[0]) * e[1]) / (a[0] * a[0] + a[1] * a[1])
         elif op == "pow":
             expo = n.args[1]
-            rounds = max(4.0, abs(expo.value)) if expo.is_const() and float(expo.value).is_integer() else 4.0
+            rounds = 2.0 * LOCAL_ULP["pow"]
+            if expo.is_const() and float(expo.value).is_integer():
+                rounds = max(4.0, abs(expo.value))
             b = rounds * U * max(abs(v), TINY) + abs(a[1] * a[0] ** (a[1] - 1.0)) * e[0]
             if not expo.is_const():
                 b += abs(v * math.log(a[0])) * e[1]
@@ -250,22 +380,33 @@ def running_bound(fn, args):
             for out in expanded(fn)]
 
 
+def _is_truth_value(n):
+    """a node that is 0 or 1 (or a count of such) EXACTLY on both sides: a comparison, the constants 0 and 1, sums and
+    products of these - what logic_and / logic_or / logic_not build and compare with 0.0"""
+    return (n.op.startswith("cmp_") or (n.op == "const" and n.value in (0.0, 1.0))
+            or (n.op in ("add", "mul") and all(_is_truth_value(x) for x in n.args)))
+
+
 def assert_no_switch_nearby(fn, args, margin=SWITCH_MARGIN):
-    """no comparison, if_else, fmin, fmax, fabs or sign of the expanded DAG is within ``margin`` of switching"""
+    """no comparison, if_else, fmin, fmax, fabs or sign of the expanded DAG is within ``margin`` of switching; a
+    comparison among truth values cannot switch by rounding and is left alone"""
     val = _node_values(fn, args)
     for n in _order(fn):
         a = [val[id(x)] for x in n.args]
         if n.op.startswith("cmp_") or n.op in ("fmin", "fmax"):
+            if n.op.startswith("cmp_") and all(_is_truth_value(x) for x in n.args):
+                continue
             assert abs(a[0] - a[1]) > margin, (n.op, a)
         elif n.op in ("fabs", "sign"):
             assert abs(a[0]) > margin, (n.op, a)
-        elif n.op == "if_else" and not n.args[0].op.startswith("cmp_"):
+        elif n.op == "if_else" and not _is_truth_value(n.args[0]):
             assert abs(a[0]) > margin, (n.op, a)
 
 
-def exact_eval(fn, args, digits=40):
+def exact_eval(fn, args, digits=40, shift=None):
     """the expanded DAG at one point in ``digits``-digit arithmetic (mpmath): a list of ``[size1, size2]`` object
-    arrays of mpf.  The inputs and the constants are the float64 numbers, exactly."""
+    arrays of mpf.  The inputs and the constants are the float64 numbers, exactly; ``shift`` = (input, entry, h) moves
+    one entry of one input (numbered as ``MX.sym`` numbers them) by the mpf ``h``."""
     import mpmath
     mp = mpmath.mp.clone()
     mp.dps = digits
@@ -273,6 +414,9 @@ def exact_eval(fn, args, digits=40):
           "acos": mp.acos, "tanh": mp.tanh, "sqrt": mp.sqrt, "fabs": abs, "neg": lambda x: -x,
           "sign": lambda x: mp.mpf((x > 0) - (x < 0))}
     env = env_of(fn, args, conv=mp.mpf)
+    if shift is not None:
+        fam = cs._as_array(fn._inputs[shift[0]]).T.reshape(-1)[shift[1]]
+        env[id(fam.family)][fam.index] += shift[2]
     val = {}
     for n in _order(fn):
         op = n.op
@@ -323,18 +467,31 @@ def exact_eval(fn, args, digits=40):
     return outs
 
 
+def central_difference(fn, args, k, j, digits=80, h="1e-25"):
+    """d (first output of ``fn``, a column) / d (entry ``j`` of input ``k``) at one point by central differences in
+    ``digits``-digit arithmetic: a list of mpf.  Nothing of autodiff.py takes part."""
+    import mpmath
+    h = mpmath.mpf(h)
+    up = exact_eval(fn, args, digits, (k, j, h))[0]
+    down = exact_eval(fn, args, digits, (k, j, -h))[0]
+    mp = mpmath.mp.clone()
+    mp.dps = digits
+    return [mp.fdiv(mp.fsub(up[i, 0], down[i, 0]), 2 * h) for i in range(up.shape[0])]
+
+
 @functools.lru_cache(maxsize=None)
 def reference(name):
     """(values, bounds) of a case over its whole pool, computed once and never changed: per output an array ``[R_MAX,
     B_MAX, size1, size2]`` of ``Function.__call__`` results and one of ``running_bound``.  Every point is checked to be
     away from a switch."""
     fn = get(name)
-    vals = [np.empty((R_MAX, B_MAX) + mx.shape) for mx in fn._outputs]
-    bnds = [np.empty((R_MAX, B_MAX) + mx.shape) for mx in fn._outputs]
-    for r in range(R_MAX):
-        for b in range(B_MAX):
+    vals = [np.empty(lead(name) + mx.shape) for mx in fn._outputs]
+    bnds = [np.empty(lead(name) + mx.shape) for mx in fn._outputs]
+    for r in range(lead(name)[0]):
+        for b in range(lead(name)[1]):
             args = point(name, r, b)
-            assert_no_switch_nearby(fn, args)
+            if name != "ties":          # (pure selections AT their switches: exact on both sides, compared by bits)
+                assert_no_switch_nearby(fn, args)
             for k, (v, e) in enumerate(zip(host_call(fn, args), running_bound(fn, args))):
                 vals[k][r, b] = v
                 bnds[k][r, b] = e
@@ -352,4 +509,35 @@ def worst_ratio(got, want, bound):
     with np.errstate(divide="ignore", invalid="ignore"):
         ratio = np.where(tol > 0.0, np.abs(got - want) / np.where(tol > 0.0, tol, 1.0),
                          np.where(got == want, 0.0, np.inf))
+    return float(ratio.max()) if ratio.size else 0.0
+
+
+@functools.lru_cache(maxsize=None)
+def exact_reference(name):
+    """``exact_eval`` of a case over its whole pool, computed once: per output two float64 arrays ``[R, B, size1,
+    size2]``, the exact value rounded to a double and the rest of it rounded to a double (together 106 bits, far below
+    any bound here)"""
+    fn = get(name)
+    his = [np.empty(lead(name) + mx.shape) for mx in fn._outputs]
+    los = [np.empty(lead(name) + mx.shape) for mx in fn._outputs]
+    for r in range(lead(name)[0]):
+        for b in range(lead(name)[1]):
+            for k, ex in enumerate(exact_eval(fn, point(name, r, b))):
+                for idx in np.ndindex(ex.shape):
+                    h = float(ex[idx])
+                    his[k][(r, b) + idx] = h
+                    los[k][(r, b) + idx] = float(ex[idx] - h)
+    for a in his + los:
+        a.setflags(write=False)
+    return his, los
+
+
+def worst_exact_ratio(got, hi, lo, bound):
+    """max over entries of |got - exact| / (2 bound), exact = hi + lo (``exact_reference``): the rule of the module
+    text for one side alone.  An entry whose bound is 0 must be exact."""
+    got = np.asarray(got, dtype=float).reshape(np.shape(hi))
+    assert np.isfinite(got).all()
+    err = np.abs((hi - got) + lo)           # (hi - got is exact where got is within a factor 2 of hi)
+    tol = 2.0 * bound
+    ratio = np.where(tol > 0.0, err / np.where(tol > 0.0, tol, 1.0), np.where(err == 0.0, 0.0, np.inf))
     return float(ratio.max()) if ratio.size else 0.0

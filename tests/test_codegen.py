@@ -16,7 +16,8 @@ import casclik_amd as cc
 from casclik_amd import sym as cs, skills
 from casclik_amd.lowering import lower_skill, OUT_EXTERN, OUT_AFFINE
 from oracle import clik_oracle
-from extern_skills import double_pendulum_skill, mixed_frame_skill, random_expression as _random_expression
+from extern_skills import (double_pendulum_skill, mixed_frame_skill, ops_inputs, ops_skill,
+                           random_expression as _random_expression)
 
 HARNESS = r"""
 #include <cmath>
@@ -132,6 +133,24 @@ def test_generated_code_with_tool_frame_time_input_and_virtual_terms(tmp_path):
     rng = np.random.default_rng(1)
     Z = np.concatenate([rng.uniform(-1.5, 1.5, size=(8, 7)), rng.uniform(-1, 1, size=(8, 1))], axis=1)
     _check(spec, d, lib, 0.8, Z, rng.uniform(-1, 1, size=(8, 3)), fk=fk, tol=1e-11)
+
+
+def test_generated_code_of_the_operations_no_other_skill_emits(tmp_path):
+    """tan, log, every form of pow, sign, fabs, fmax, fmin, the inverse trigonometric functions, tanh and if_else on
+    `<=` and on a logic_and: the generated bodies against the oracle's dual numbers, away from every switch"""
+    spec = ops_skill()
+    d = lower_skill(spec)
+    assert [tk["out_kind"][0] for tk in d.tasks] == [OUT_EXTERN, OUT_EXTERN]
+    assert d.n_tslots > 0 and not d.uses_fk and not d.joints         # (sin(0.5 t), 0.3 t and their rates)
+    assert sorted(int(tk["m"]) for tk in d.tasks) == [4, 6] and d.n_state == 4
+    text = d.extern_source()
+    for call in ("tan(", "log(", "pow(", "__builtin_powi(", "sqrt(", "asin(", "acos(", "atan(", "atan2(", "tanh(", "fabs(",
+                 "fmax(", "fmin(", " <= ", " < ", " != ", "> 0.0) - ("):
+        assert call in text, call
+    lib = _compile(d, tmp_path)
+    for t in (0.0, 1.3):
+        Q, Y = ops_inputs(24, 31, t=t)
+        _check(spec, d, lib, t, Q, Y, tol=1e-11)
 
 
 def test_what_generated_code_cannot_express_is_refused():

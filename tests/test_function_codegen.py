@@ -4,6 +4,7 @@ translation unit no other kernel shares - and what `DeviceFunction` does without
 marshalling, refusals."""
 import ctypes as C
 import hashlib
+import math
 import os
 import re
 import shutil
@@ -20,7 +21,8 @@ from casclik_amd.function_batch import DeviceFunction, output_shape, plan_argume
 
 import function_cases as fc
 
-SINCOS_PAIRS = {"tool": 6, "manip": 6, "pend": 2, "wide": 14}       # distinct arguments of sin / cos
+SINCOS_PAIRS = {"tool": 6, "manip": 6, "pend": 2, "wide": 14,        # distinct arguments of sin / cos
+                "ops_pow": 1, "ops_libm": 3, "ops_sel": 3, "trig": 1, "ties": 0}
 
 
 # ---- emitted text ----------------------------------------------------------------------------------------------------------
@@ -119,8 +121,8 @@ def test_emitted_text_as_host_code_matches_the_host_evaluator(host_code, name):
     run = host_code(name)
     vals, bnds = fc.reference(name)
     worst = 0.0
-    for r in range(fc.R_MAX):
-        for b in range(fc.B_MAX):
+    for r in range(fc.lead(name)[0]):
+        for b in range(fc.lead(name)[1]):
             for got, want, bound in zip(run(fc.point(name, r, b)), vals, bnds):
                 ratio = fc.worst_ratio(got, want[r, b], bound[r, b])
                 worst = max(worst, ratio)
@@ -147,18 +149,15 @@ def test_the_jacobian_output_is_the_chains_numeric_derivative(host_code):
 def test_the_reference_side_stays_within_the_running_bound(name):
     """the same DAG at 40 digits (mpmath): |Function.__call__ - exact| <= 2 running_bound at every point of the pool -
     the rule the device is held to, applied to the host evaluator alone"""
-    fn = fc.get(name)
     vals, bnds = fc.reference(name)
+    his, los = fc.exact_reference(name)
     worst = 0.0
-    for r in range(fc.R_MAX):
-        for b in range(fc.B_MAX):
-            for exact, want, bound in zip(fc.exact_eval(fn, fc.point(name, r, b)), vals, bnds):
-                for idx in np.ndindex(exact.shape):
-                    err = abs(float(exact[idx] - want[r, b][idx]))
-                    tol = 2.0 * bound[r, b][idx]
-                    assert err <= tol, (name, r, b, idx, err, tol)
-                    if tol > 0.0:
-                        worst = max(worst, err / tol)
+    for k, (want, hi, lo, bound) in enumerate(zip(vals, his, los, bnds)):
+        for r in range(fc.lead(name)[0]):
+            for b in range(fc.lead(name)[1]):
+                ratio = fc.worst_exact_ratio(want[r, b], hi[r, b], lo[r, b], bound[r, b])
+                assert ratio <= 1.0, (name, k, r, b, want[r, b], hi[r, b], bound[r, b])
+                worst = max(worst, ratio)
     print("%s: worst |host - exact| in units of 2 bound: %.3g" % (name, worst))
 
 
@@ -170,6 +169,104 @@ def test_the_bound_sees_cancellation_and_the_switch_helper_fires():
     fc.assert_no_switch_nearby(f, (np.array([1.0, 2.0]),))
     with pytest.raises(AssertionError):
         fc.assert_no_switch_nearby(f, (np.array([1.0, 1.0 + 1e-9]),))
+    # the logic helpers compare truth values with 0.0: no switch that rounding could flip, but their own arguments are
+    g = cs.Function("l", [x], [cs.if_else(cs.logic_or(cs.logic_and(x[0] < 1.5, x[1] != 0.25), cs.logic_not(x[0] >= x[1])),
+                                          x[0], x[1])])
+    fc.assert_no_switch_nearby(g, (np.array([1.0, 2.0]),))
+    fc.assert_no_switch_nearby(g, (np.array([2.0, 1.0]),))          # (every truth value 0 but the last)
+    for near in ([1.5 - 1e-9, 2.0], [1.0, 0.25 + 1e-9], [1.0, 1.0 - 1e-9]):
+        with pytest.raises(AssertionError):
+            fc.assert_no_switch_nearby(g, (np.array(near),))
+    with pytest.raises(AssertionError):                              # a condition that is no truth value
+        fc.assert_no_switch_nearby(cs.Function("m", [x], [cs.if_else(x[0] * x[1], x[0], x[1])]), (np.array([1e-4, 1e-4]),))
+
+
+# ---- derivatives, selections at their ties, IEEE edges -----------------------------------------------------------------------
+@pytest.mark.parametrize("name", fc.OPS)
+def test_jacobian_outputs_are_the_central_differences_of_the_value_column(name):
+    """autodiff.diff_scalar without a second implementation of its rules: the Jacobian outputs of `Function.__call__`
+    against central differences (h = 1e-25) of the VALUE column alone at 80 digits, whose truncation (h^2 f''' / 6,
+    1e-50) and rounding (1e-80 / h) are far below the rule |J - exact| <= 2 running_bound of the Jacobian entry"""
+    fn = fc.get(name)
+    value = cs.Function("value", fn._inputs, [fn._outputs[0]])
+    vals, bnds = fc.reference(name)
+    m = fn._outputs[0].shape[0]
+    worst = 0.0
+    for r, b in [(0, 0), (0, 1), (0, 64), (1, 2), (1, 100), (2, 3), (2, 200), (2, 256)]:
+        args = fc.point(name, r, b)
+        for k, n_k in ((0, 4), (1, 3)):
+            for j in range(n_k):
+                d = fc.central_difference(value, args, k, j)
+                for i in range(m):
+                    err = abs(float(d[i] - mpmath.mpf(vals[1 + k][r, b][i, j])))
+                    tol = 2.0 * bnds[1 + k][r, b][i, j]
+                    assert err <= (tol if tol > 0.0 else 1e-40), (name, r, b, k, i, j, err, tol)
+                    if tol > 0.0:
+                        worst = max(worst, err / tol)
+    print("%s: worst |host Jacobian - central difference| in units of 2 bound: %.3g" % (name, worst))
+
+
+def test_selections_at_their_ties_follow_the_stated_rules(host_code):
+    """`ties`: fmin / fmax of equal arguments and of neighbouring doubles, their derivatives (the first argument's at a
+    tie), sign and the derivative of fabs at +0.0, the four comparisons on equal arguments, if_else on 0.0 and 0.3 - the
+    host evaluator and the generated text against the outputs written out by hand, bit for bit"""
+    fn = fc.get("ties")
+    run = host_code("ties")
+    vals, bnds = fc.reference("ties")
+    assert all((b == 0.0).all() for b in bnds)
+    tied = 0
+    for r in range(fc.lead("ties")[0]):
+        for b in range(fc.lead("ties")[1]):
+            args = fc.point("ties", r, b)
+            tied += args[0][0] == args[0][1]
+            for want, host, code in zip(fc.ties_expected(args), fc.host_call(fn, args), run(args)):
+                assert want.tobytes() == host.tobytes() == code.tobytes(), (r, b, args, want, host, code)
+    assert tied == 3 * 86
+    # at a tie: both take the first argument's derivative, <= and == hold, != and < do not, 0.3 is true
+    x, w = np.array([0.75, 0.75]), np.array([-1.0, 2.0])
+    col, J, d = fc.host_call(fn, (x, 0.0, w, np.array([0.0, 0.3])))
+    assert col[:, 0].tolist() == [0.75, 0.75, 0.0, -1.0, -1.0, 2.0, 2.0, 2.0, -1.0]
+    assert J.tolist() == [[1.0, 0.0], [1.0, 0.0]] and d.tolist() == [[0.0]]
+
+
+def test_the_host_evaluator_answers_as_ieee_does_where_python_raises():
+    """log(0), log(-1), sqrt(-1), exp(800), 0 ** -1, tan / sin of inf, a negative base under a fractional exponent:
+    what CasADi and the device return, not an exception; and a constant base (`2.0 ** x`)"""
+    inf = float("inf")
+    x = cs.MX.sym("x")
+    one = {"log": cs.log, "sqrt": cs.sqrt, "exp": cs.exp, "tan": cs.tan, "sin": cs.sin, "cos": cs.cos, "asin": cs.asin,
+           "acos": cs.acos, "atan": cs.atan, "tanh": cs.tanh, "fabs": cs.fabs, "sign": cs.sign}
+
+    def at(op, v):
+        return float(cs.Function("f", [x], [one[op](x)])(v))
+    assert at("log", 0.0) == -inf and np.isnan(at("log", -1.0)) and at("log", inf) == inf
+    assert np.isnan(at("sqrt", -1.0)) and at("sqrt", 0.0) == 0.0 and at("sqrt", inf) == inf
+    assert at("exp", 800.0) == inf and at("exp", -800.0) == 0.0 and at("exp", -inf) == 0.0
+    assert all(np.isnan(at(op, s * inf)) for op in ("tan", "sin", "cos") for s in (1.0, -1.0))
+    assert np.isnan(at("asin", 1.5)) and np.isnan(at("acos", -1.5))
+    assert at("atan", inf) == math.pi / 2 and at("tanh", 1e3) == 1.0 and at("tanh", -inf) == -1.0
+    assert at("fabs", -inf) == inf and at("sign", -inf) == -1.0 and at("sign", 0.0) == 0.0
+    for op in one:                      # a NaN goes through every one of them, sign excepted (no comparison holds)
+        assert np.isnan(at(op, float("nan"))) or op == "sign"
+    # pow
+    y = cs.MX.sym("y")
+    p = cs.Function("p", [x, y], [x ** y])
+    assert float(p(0.0, -1.0)) == inf and float(p(0.0, -2.0)) == inf and float(p(0.0, -0.5)) == inf
+    assert float(p(1e200, 2.0)) == inf and float(p(-1e200, 3.0)) == -inf and float(p(-1e200, 2.0)) == inf
+    assert np.isnan(float(p(-8.0, 0.5))) and float(p(-8.0, 3.0)) == -512.0 and float(p(0.0, 0.0)) == 1.0
+    assert float(cs.Function("q", [x], [x ** -1])(0.0)) == inf
+    # a constant base
+    r = 2.0 ** cs.vertcat(x, y)
+    assert isinstance(r, cs.MX) and r.shape == (2, 1)
+    assert cs.Function("r", [x, y], [r])(3.0, -1.0).toarray().ravel().tolist() == [8.0, 0.5]
+    assert float(cs.Function("s", [x], [cs.jacobian(2.0 ** x, x)])(3.0)) == 8.0 * math.log(2.0)
+    folded = cs.Function("c", [x], [cs.vertcat(cs.MX(2.0) ** cs.MX(-1075.0), cs.MX(0.0) ** cs.MX(-1.0), cs.log(cs.MX(0.0)))])
+    assert folded(1.0).toarray().ravel().tolist() == [0.0, inf, -inf]
+    # 1 / 0 as before
+    assert float(cs.Function("d", [x], [1.0 / x])(0.0)) == inf
+    # the points of the device's edge test (test_gpu_function_batch.py)
+    for point, want in zip(fc.EDGE_POINTS, fc.EDGE_VALUES):
+        assert fc.host_call(fc.get("edges"), (point,))[0].tobytes() == want.reshape(5, 1).tobytes()
 
 
 # ---- device compilation ----------------------------------------------------------------------------------------------------
@@ -244,7 +341,8 @@ def test_existing_units_keep_their_stamps_and_the_new_one_follows_its_headers_co
 def test_the_request_id_is_a_function_of_the_expression_only():
     ids = {name: jit.function_request_id(fc.get(name)) for name in fc.NAMES}
     assert len(set(ids.values())) == len(fc.NAMES)
-    for name in fc.NAMES:
+    ids["edges"] = jit.function_request_id(fc.get("edges"))
+    for name in fc.NAMES + ["edges"]:
         assert jit.function_request_id(fc.make(name)) == ids[name]       # new symbols, new nodes, the same request
         assert ids[name] == jit._request_id("", codegen.emit_function(fc.get(name)), False, [], jit._FUNCTION_TEMPLATE)
         # the instantiations the GPU tests ask for are recorded: build() replays them

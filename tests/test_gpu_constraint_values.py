@@ -3,7 +3,8 @@ whole trajectory of states, from the kernel of clik_monitor.hpp - against the or
 (``ExprEvaluator.vector``), for both controllers.
 
 Tolerances: the ones tests/test_gpu_qp.py holds the same quantities to - device Jacobian rows max |d| < 1e-12, and 1e-12
-for the unscaled e and e_t; every fixture here is O(1) (max |ref| below 4), none is scaled."""
+for the unscaled e and e_t; every fixture here is O(1) (max |ref| below 4; below 15 for the `ops` skill, whose rows add
+up to three library functions), none is scaled."""
 import os
 import subprocess
 import sys
@@ -17,7 +18,7 @@ from oracle import clik_oracle
 
 import notebook_figures as cf
 import time_skills
-from extern_skills import double_pendulum_skill, dual_quaternion_skill, mixed_frame_skill
+from extern_skills import double_pendulum_skill, dual_quaternion_skill, mixed_frame_skill, ops_inputs, ops_skill
 from test_figure_pins import PIXELS
 
 pytestmark = pytest.mark.gpu
@@ -47,6 +48,12 @@ def _make(name, iiwa_fk, ur5_fk, **options):
         spec, ctrl = time_skills.tracking_spec(ur5_fk), None    # (time slots: e_t != 0)
     elif name == "tracking_qp":
         spec = time_skills.track_qp_spec(ur5_fk)
+        ctrl = cc.ReactiveQPController(skill_spec=spec, options=dict(options))
+    elif name == "ops":
+        spec = ops_skill()          # (the operations no other skill emits, no kinematics: generated code throughout)
+        ctrl = cc.PseudoInverseController(skill_spec=spec, options=dict({"multidim_sets": True}, **options))
+    elif name == "ops_qp":
+        spec = ops_skill()
         ctrl = cc.ReactiveQPController(skill_spec=spec, options=dict(options))
     else:
         spec = mixed_frame_skill(iiwa_fk)                       # (a virtual variable: J has n_q + n_x columns)
@@ -133,6 +140,33 @@ def test_values_and_jacobians_match_the_oracle(ctrls, iiwa_fk, name):
     for label, sl in ctrl.constraint_rows().items():
         assert one[label].toarray().shape == (sl.stop - sl.start, 1)
         assert np.array_equal(one[label].toarray()[:, 0], first[0, sl])
+
+
+@pytest.mark.parametrize("name", ["ops", "ops_qp"])
+def test_generated_operations_match_the_oracle(ctrls, name):
+    """tan, log, every form of pow, sign, fabs, fmax, fmin, asin, acos, atan, atan2, tanh and if_else on `<=` and on a
+    logic_and as a skill's constraints: e, J and d e / d t against the oracle's dual numbers under the bound of this
+    file, a batch and a trajectory, states away from every switch"""
+    spec, ctrl = ctrls(name)
+    stamps = np.array([0.4, 1.3, 2.9])
+    recs = [ops_inputs(65, 40 + r, t=stamps[r]) for r in range(3)]
+    Q3, Y3 = np.stack([r[0] for r in recs]), np.stack([r[1] for r in recs])
+    refs = [_oracle(spec, ctrl, stamps[r], Q3[r], None, Y3[r]) for r in range(3)]
+    assert refs[0][0].shape == (65, 10) and max(np.abs(a).max() for ref in refs for a in ref) < 15.0
+    assert min(np.abs(ref[2]).max() for ref in refs) > 1e-2         # (the time terms move)
+    for B in (1, 65):
+        got = ctrl.constraint_values_batch(stamps[1], Q3[1][:B], input_var=Y3[1][:B], jacobian=True)
+        assert got[0].shape == (B, 10) and got[1].shape == (B, 10, 4) and got[2].shape == (B, 10)
+        for what, a, ref in zip(("e", "J", "e_t"), got, refs[1]):
+            _close(name, "%s B=%d" % (what, B), a, ref[:B])
+        traj = ctrl.constraint_values_batch(stamps, Q3[:, :B], input_var=Y3[:, :B], jacobian=True)
+        for r in range(3):
+            for what, a, ref in zip(("e", "J", "e_t"), traj, refs[r]):
+                _close(name, "%s R=3 B=%d record %d" % (what, B, r), a[r], ref[:B])
+        if B == 65:         # R = 1: the middle record as a trajectory of one
+            single = ctrl.constraint_values_batch(stamps[1:2], Q3[1:2], input_var=Y3[1:2], jacobian=True)
+            for a, b in zip(single, got):
+                assert np.array_equal(a[0], b)
 
 
 # ---- 2: trajectory shapes ------------------------------------------------------------------------------------------------

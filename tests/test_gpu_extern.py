@@ -11,7 +11,7 @@ import pytest
 import casclik_amd as cc
 from casclik_amd import skills
 from casclik_amd import sym as cs
-from extern_skills import double_pendulum_skill, mixed_frame_skill, dual_quaternion_skill
+from extern_skills import double_pendulum_skill, mixed_frame_skill, dual_quaternion_skill, ops_inputs, ops_skill
 from tolerances import PINV_RTOL, QP_RTOL, pinv_close, qp_close
 
 pytestmark = pytest.mark.gpu
@@ -122,6 +122,41 @@ def test_tool_frame_products_virtual_input_and_time(iiwa_fk):
     ok = rst == 0
     assert ok.sum() > 900
     assert _rel(np.hstack([qdq, qdx])[ok], np.hstack([rdq, rdx])[ok]).max() < 1e-7
+
+
+def test_the_operations_no_other_skill_emits_pseudo_inverse():
+    """`ops_skill` (tan, log, every form of pow, sign, fabs, fmax, fmin, asin, acos, atan, atan2, tanh, if_else on `<=`
+    and on a logic_and) through PseudoInverseController, the four-row set as a multidimensional one: the oracle's modes,
+    its velocities under the stated rule; states away from every switch"""
+    from oracle import clik_oracle
+    spec = ops_skill()
+    opts = {"multidim_sets": True}
+    ctrl = cc.PseudoInverseController(skill_spec=spec, options=dict(opts))
+    ctrl.setup_problem_functions()
+    assert ctrl.kernel_name.startswith("jit_")
+    t = 1.3
+    Q, Y = ops_inputs(128, 21, t=t)
+    dq, _, mode = ctrl.solve_batch(t, Q, input_var=Y)
+    ref, rmode = clik_oracle.pinv_solve_batch(spec, opts, t, Q, Y=Y)
+    assert np.array_equal(mode, rmode)
+    assert pinv_close(dq, ref), _rel(dq, ref).max()
+
+
+def test_the_operations_no_other_skill_emits_reactive_qp():
+    """the same skill through ReactiveQPController: the oracle's statuses, its velocities and slacks under the stated
+    rule"""
+    from oracle import clik_oracle
+    spec = ops_skill()
+    ctrl = cc.ReactiveQPController(skill_spec=spec)
+    ctrl.setup_problem_functions()
+    ctrl.setup_solver()
+    assert ctrl.kernel_name.startswith("jit_")
+    t = 1.3
+    Q, Y = ops_inputs(128, 21, t=t)
+    dq, _, slack, status = ctrl.solve_batch(t, Q, input_var=Y)
+    rdq, _, rsl, rst = clik_oracle.qp_solve_batch(spec, t, Q, Y=Y)
+    assert np.array_equal(status, rst) and (rst == 0).all()
+    assert qp_close(dq, rdq) and qp_close(slack, rsl)
 
 
 def test_initial_problem_of_a_skill_with_generated_rows_and_a_virtual_variable(iiwa_fk):

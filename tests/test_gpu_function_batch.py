@@ -1,6 +1,8 @@
 """GPU: `DeviceFunction` - a cs.Function at every row of a batch or a recorded trajectory in one launch - against
 `Function.__call__` under the derived tolerance of function_cases.py, at the wave and block tails, with every form of
-broadcasting, in place over the records of a rollout, and with a poisoned row."""
+broadcasting, in place over the records of a rollout, and with a poisoned row; the cases that hold every operation the
+code generator emits, and sincos_joint alone, also against the exact value; selections at their ties and the infinite
+results of finite inputs bit for bit."""
 import numpy as np
 import pytest
 
@@ -39,7 +41,7 @@ def test_every_entry_matches_the_host_evaluator_under_the_derived_bound(dfn, nam
     assert f.scratch_bytes == 0
     vals, bnds = fc.reference(name)
     worst = 0.0
-    for R, B in fc.SHAPES:
+    for R, B in fc.shapes(name):
         for three_d in ((True, False) if R == 1 else (True,)):
             outs = _as_tuple(f(*_args(name, R, B, three_d)))
             lead = (R, B) if three_d else (B,)
@@ -50,6 +52,64 @@ def test_every_entry_matches_the_host_evaluator_under_the_derived_bound(dfn, nam
                 worst = max(worst, ratio)
                 assert ratio <= 1.0, (name, R, B, ratio)
     print("%s: worst |device - host| in units of 2 (bound + bound): %.3g" % (name, worst))
+
+
+def _ulp(x):
+    """the spacing of the doubles at |x|, normal or not"""
+    return np.maximum(np.spacing(np.abs(x)), 2.0 ** -1074)
+
+
+@pytest.mark.parametrize("name", fc.EXACT)
+def test_every_entry_is_within_twice_the_running_bound_of_the_exact_value(dfn, name):
+    """|device - exact| <= 2 running_bound, entry by entry, against the same DAG at 40 digits: the rule the host
+    evaluator is held to in test_function_codegen.py, for the device alone"""
+    f = dfn(name)
+    _, bnds = fc.reference(name)
+    his, los = fc.exact_reference(name)
+    R, B = fc.lead(name)
+    full = _as_tuple(f(*_args(name, R, B)))
+    worst = 0.0
+    for k, (got, hi, lo, bound) in enumerate(zip(full, his, los, bnds)):
+        ratio = fc.worst_exact_ratio(got, hi, lo, bound)
+        worst = max(worst, ratio)
+        assert ratio <= 1.0, (name, k, ratio)
+    # the smaller shapes give the bits of the full one, row by row (so they are within the rule as well)
+    for R_, B_ in fc.shapes(name):
+        for got, whole in zip(_as_tuple(f(*_args(name, R_, B_))), full):
+            assert got.tobytes() == np.ascontiguousarray(whole[:R_, :B_]).tobytes(), (name, R_, B_)
+    print("%s: worst |device - exact| in units of 2 bound: %.3g" % (name, worst))
+    if name == "trig":
+        # sincos_joint itself, in units in the last place of the exact value: its straight-line path (|x| <= 1e5) and
+        # the library path beyond
+        x = fc.pool(name)[0]
+        err = np.abs((his[0] - full[0].reshape(his[0].shape)) + los[0]) / _ulp(his[0])
+        fast = np.abs(x) <= 1e5
+        assert fast.sum() > 1300 and (~fast).sum() == 16
+        for what, sel in (("fast", fast), ("library", ~fast)):
+            print("trig: sincos_joint, %s path: worst error %.3f ulp (sin), %.3f ulp (cos) over %d arguments"
+                  % (what, err[sel][:, 0, 0].max(), err[sel][:, 1, 0].max(), sel.sum()))
+
+
+def test_selections_at_their_ties_match_the_written_out_rules_bit_for_bit(dfn):
+    f = dfn("ties")
+    vals, _ = fc.reference("ties")
+    R, B = fc.lead("ties")
+    outs = _as_tuple(f(*_args("ties", R, B)))
+    for got, want, (s1, s2) in zip(outs, vals, f.output_sizes):
+        assert got.reshape(want.shape).tobytes() == want.tobytes()
+    for r, b in [(0, 0), (0, 1), (0, 2), (1, 63), (2, 256)]:
+        for got, want in zip(outs, fc.ties_expected(fc.point("ties", r, b))):
+            assert got[r, b].reshape(want.shape).tobytes() == want.tobytes(), (r, b)
+
+
+def test_finite_inputs_with_infinite_or_exact_results_give_the_hosts_bits(dfn):
+    """log(0), exp(+-800), 1 / 0, tanh(+-1e3), 0 ** -1: -inf, inf or 0, inf, +-1, inf - and the exact results at 1, 0,
+    2, 0, 4.  (Nothing is promised for a NaN result: the device code is built with -fno-honor-nans.)"""
+    f = dfn("edges")
+    got = f(fc.EDGE_POINTS)
+    assert got.shape == (3, 5) and got.tobytes() == fc.EDGE_VALUES.tobytes(), got
+    host = np.stack([fc.host_call(fc.get("edges"), (p,))[0][:, 0] for p in fc.EDGE_POINTS])
+    assert got.tobytes() == host.tobytes()
 
 
 # ---- broadcasting ----------------------------------------------------------------------------------------------------------

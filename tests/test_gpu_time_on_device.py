@@ -52,7 +52,7 @@ def track_qp(ur5_fk):
 def table_ctrls(track):
     import notebook_figures
     return {"tracking": track[1], "moe": _pinv(time_skills.moe_spec(notebook_figures.moe_fk()), True),
-            "mixed": _pinv(time_skills.mixed_spec(), True)}
+            "mixed": _pinv(time_skills.mixed_spec(), True), "ops": _pinv(time_skills.ops_time_spec(), True)}
 
 
 def _start(B, seed):
@@ -64,7 +64,7 @@ def _host_table(d, times, dt, method):
     return np.stack([d.time_terms(float(t)) for t in rollout_stage_times(times, dt, method)])
 
 
-@pytest.mark.parametrize("name", ["tracking", "moe", "mixed"])
+@pytest.mark.parametrize("name", ["tracking", "moe", "mixed", "ops"])
 def test_table_equals_the_host_evaluator(table_ctrls, name):
     ctrl = table_ctrls[name]
     d = ctrl.descriptor
@@ -86,6 +86,24 @@ def test_table_equals_the_host_evaluator(table_ctrls, name):
                 assert np.array_equal(rows[:, 1], rows[:, 2])
                 assert np.array_equal(rows[:, 0], ctrl.time_terms_batch(times)), "stage 0 is the tick's own time"
     print("%s: worst ratio %.3f" % (name, worst))
+
+
+@pytest.mark.parametrize("t", time_skills.TIMES_BEYOND_THE_FAST_RANGE)
+def test_table_beyond_the_straight_line_range_of_sincos_joint(table_ctrls, t):
+    """0.1 t = +-2e5 rad: `TimeSlots` takes the library path of sincos_joint (|x| > 1e5), under the same bound; alone,
+    among ordinary times (the branch is per lane) and at the four stages of an rk4 tick"""
+    ctrl = table_ctrls["tracking"]
+    d = ctrl.descriptor
+    assert abs(0.1 * t) > 1e5
+    for times in (np.array([t]), np.concatenate([time_skills.TIMES[:31], [t], time_skills.TIMES[31:], [t + 0.25]])):
+        for method, stages in (("euler", 1), ("rk4", 4)):
+            dev = ctrl.time_terms_batch(times, dt=DT, method=method)
+            host = _host_table(d, times, DT, method)
+            assert dev.shape == host.shape == (times.size * stages, 2 * d.n_tslots) and np.isfinite(host).all()
+            ratio = np.abs(dev - host) / (U * (1.0 + np.abs(host)))
+            print("tracking t=%g %s n=%d: worst |dev - host| / (u (1 + |host|)) = %.3f" % (t, method, times.size, ratio.max()))
+            assert (ratio <= C_ULP).all()
+    assert np.abs(_host_table(d, np.array([t]), DT, "euler")).max() > 0.1       # (the slots are not all zero there)
 
 
 # ---- B2 ---------------------------------------------------------------------------------------------------------------

@@ -96,6 +96,40 @@ def test_ad_jacobian_vs_finite_differences(robot, iiwa_fk, ur5_fk):
     assert np.abs(Jt).max() == 0.0
 
 
+def test_ad_of_selections_comparisons_and_a_variable_exponent_vs_finite_differences():
+    """if_else (on `<=`, on a logic_and, on a condition that is no comparison), the comparisons themselves and pow with
+    an exponent that moves: the dual numbers against central differences in the state and in time, away from every
+    switch; a comparison is a truth value with derivative 0"""
+    from extern_skills import ops_inputs, ops_skill
+    spec, (t, q, y), (eq, st) = ops_skill(parts=True)
+    extra = cs.vertcat(q[1] ** (1.0 + 0.2 * q[0] * cs.sin(0.5 * t)), (q[0] < q[1]) + 2.0 * (q[2] >= q[3]) + 4.0 * (q[0] == q[1])
+                       + 8.0 * (q[2] != q[3]), cs.if_else(q[0] * y[0], q[1] * q[2], cs.exp(q[3])),
+                       cs.if_else(cs.logic_or(q[0] > q[3], cs.logic_not(q[1] < q[2])), cs.cos(q[0] * t), q[3] ** -3))
+    t0, h = 0.7, 1e-6
+    Q, Y = ops_inputs(12, 5, t=t0)
+    Q[:, 1] = np.abs(Q[:, 1])                       # (the base of the extra row's power)
+    expr = cs.vertcat(eq, st, extra)
+    e, Jt, J = orc.ExprEvaluator(spec, t0, Q, Y).vector(expr)
+    assert np.isfinite(e).all() and np.isfinite(J).all() and np.isfinite(Jt).all()
+    assert set(np.unique(e[:, 11])) <= set(range(16)) and len(np.unique(e[:, 11])) > 2
+    assert np.abs(J[:, 11]).max() == 0.0 and np.abs(Jt[:, 11]).max() == 0.0
+    for j in range(4):
+        Qp, Qm = Q.copy(), Q.copy()
+        Qp[:, j] += h
+        Qm[:, j] -= h
+        ep = orc.ExprEvaluator(spec, t0, Qp, Y).vector(expr)[0]
+        em = orc.ExprEvaluator(spec, t0, Qm, Y).vector(expr)[0]
+        assert np.abs((ep - em) / (2 * h) - J[:, :, j]).max() < 1e-8 * (1.0 + np.abs(J).max())
+    ep = orc.ExprEvaluator(spec, t0 + h, Q, Y).vector(expr)[0]
+    em = orc.ExprEvaluator(spec, t0 - h, Q, Y).vector(expr)[0]
+    assert np.abs((ep - em) / (2 * h) - Jt).max() < 1e-8
+    assert np.abs(Jt[:, [0, 1, 9, 10]]).min() > 1e-4      # (the rows that hold the time, and the moving exponent)
+    # the oracle's values are the host evaluator's
+    fn = cs.Function("rows", [t, q, y], [expr])
+    for b in range(len(Q)):
+        assert np.abs(fn(t0, Q[b], Y[b]).toarray()[:, 0] - e[b]).max() < 1e-13 * (1.0 + np.abs(e[b]).max())
+
+
 def test_time_derivative_feedforward():
     """d e/d t of a trajectory-tracking expression (moe2016 trajectory form)."""
     fk = skills.iiwa()

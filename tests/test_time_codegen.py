@@ -17,8 +17,8 @@ from casclik_amd.lowering import lower_skill
 
 import time_skills
 
-SKILLS = ["tracking", "moe", "mixed"]
-# the largest slot tree (value or derivative) of the three skills has this many distinct nodes at most: one rounding
+SKILLS = ["tracking", "moe", "mixed", "ops"]
+# the largest slot tree (value or derivative) of these skills has this many distinct nodes at most: one rounding
 # each, which is what the 1e-14 of the host comparison rests on
 MAX_NODES = 48
 
@@ -29,7 +29,7 @@ def descs():
     import notebook_figures
     return {"tracking": lower_skill(time_skills.tracking_spec(fk)),
             "moe": lower_skill(time_skills.moe_spec(notebook_figures.moe_fk())),
-            "mixed": lower_skill(time_skills.mixed_spec())}
+            "mixed": lower_skill(time_skills.mixed_spec()), "ops": lower_skill(time_skills.ops_time_spec())}
 
 
 @pytest.mark.parametrize("name", SKILLS)
@@ -83,16 +83,10 @@ extern "C" void time_terms(double t, double* tv) { TimeSlots::eval(t, tv); }
 """
 
 
-@pytest.mark.parametrize("name", SKILLS)
-def test_emitted_text_as_host_code_matches_the_host_evaluator(descs, name, tmp_path):
-    """Both sides run host libm in the same operation order; what differs is x * x for pow(x, 2), repeated
-    multiplication for pow(x, 3), sincos for separate sin / cos and nothing else: |a - b| <= 1e-14 (1 + |b|), some 90
-    units in the last place for trees of at most MAX_NODES nodes at one rounding each."""
+def _host_time_terms(d, tmp_path):
     gxx = shutil.which("g++")
     if gxx is None:
         pytest.skip("g++ not available")
-    d = descs[name]
-    assert max(max(time_skills.count_nodes(v), time_skills.count_nodes(g)) for v, g in d.tslots) <= MAX_NODES
     src = tmp_path / "ts.cpp"
     src.write_text(_HOST_WRAPPER % codegen.emit_time_slots(d))
     so = tmp_path / "ts.so"
@@ -100,8 +94,20 @@ def test_emitted_text_as_host_code_matches_the_host_evaluator(descs, name, tmp_p
     fn = C.CDLL(str(so)).time_terms
     fn.argtypes = [C.c_double, C.POINTER(C.c_double)]
     fn.restype = None
+    return fn
+
+
+@pytest.mark.parametrize("name", SKILLS)
+def test_emitted_text_as_host_code_matches_the_host_evaluator(descs, name, tmp_path):
+    """Both sides run host libm in the same operation order; what differs is x * x for pow(x, 2), repeated
+    multiplication for pow(x, 3), sincos for separate sin / cos and nothing else: |a - b| <= 1e-14 (1 + |b|), some 90
+    units in the last place for trees of at most MAX_NODES nodes at one rounding each."""
+    d = descs[name]
+    assert max(max(time_skills.count_nodes(v), time_skills.count_nodes(g)) for v, g in d.tslots) <= MAX_NODES
+    fn = _host_time_terms(d, tmp_path)
     worst = 0.0
-    for t in time_skills.TIMES:
+    # (the tracking skill also beyond the straight-line range of sincos_joint, where the device takes the library path)
+    for t in np.concatenate([time_skills.TIMES, time_skills.TIMES_BEYOND_THE_FAST_RANGE]) if name == "tracking" else time_skills.TIMES:
         ref = d.time_terms(float(t))
         assert np.isfinite(ref).all(), (name, t)
         got = np.full(2 * d.n_tslots, np.nan)

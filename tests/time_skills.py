@@ -16,6 +16,10 @@ if os.path.join(HERE, "golden") not in sys.path:
 # straight-line range of sincos_joint) and a rollout's stamps
 TIMES = np.concatenate([[0.0, 1e-3, 3.0, 29.7, -12.5, 1e4], 3.0 + 0.05 * np.arange(40)])
 
+# beyond it: 0.1 * 2e6 rad, where sincos_joint leaves its straight-line path for the library routine (the tracking skill
+# alone is evaluated there)
+TIMES_BEYOND_THE_FAST_RANGE = np.array([2.0e6, -2.0e6])
+
 UR5_HOME = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
 
 
@@ -60,6 +64,20 @@ def mixed_spec(n=3):
                         cs.if_else(t < 5.0, 0.3 * t, 1.5 + cs.sin(0.2 * t)))
     return cc.SkillSpecification("mixed_time", t, q, constraints=[
         cc.EqualityConstraint("follow", q - target[:n], gain=1.0, constraint_type="soft")])
+
+
+def ops_time_spec():
+    """joint-space targets built from the operations no other skill here puts into a time slot: tan(0.05 t) (its pole is
+    at t = 31.4, beyond the rollouts' times), log(2 + t t), atan2, tanh, a fractional power (its base held at 1 for
+    negative times by an fmax), and an if_else on t >= 5"""
+    t = cs.MX.sym("t")
+    q = cs.MX.sym("q", 4)
+    target = cs.vertcat(0.1 * cs.tan(0.05 * t) + 0.01 * cs.log(2.0 + t * t),
+                        cs.atan2(cs.sin(0.1 * t), 1.5 + cs.cos(0.1 * t)) + cs.tanh(0.2 * t - 1.0),
+                        1e-3 * (1.0 + 0.1 * cs.fmax(t, 0.0)) ** 2.5,
+                        cs.if_else(t >= 5.0, 0.3 + 0.1 * cs.tanh(0.1 * t), 0.06 * t))
+    return cc.SkillSpecification("ops_time", t, q, constraints=[
+        cc.EqualityConstraint("follow", q - target, gain=1.0, constraint_type="soft")])
 
 
 def count_nodes(tree):
