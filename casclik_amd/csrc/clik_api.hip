@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -24,43 +25,7 @@
 #include "clik_pinv_select.hpp"
 #include "clik_qp_select.hpp"
 #include "clik_workspace.hpp"
-
-namespace clik {
-int pinv_pick_kernel(const DevSkill& S, int allow_static);
-const char* pinv_kernel_name(int k);
-int pinv_kernel_width(int k);
-int pinv_kernel_is_static(int k);
-hipError_t pinv_launch_solve(int k, const LaunchArgs& a, const TickArgs& tk, long long B, const double* q,
-                             const double* x, const double* y, double* dq, double* dx, int32_t* mode,
-                             hipStream_t stream);
-hipError_t pinv_launch_rollout(int k, const LaunchArgs& a, const double* d_tterms, int n_ticks, double dt,
-                               double max_speed, long long B, double* q, const double* y, double* dq,
-                               int32_t* mode, hipStream_t stream);
-int pinv_lds_slots_host(int N, int ny);
-hipError_t qp_launch_solve(int k, const DevSkill* dS, const WarmArgs& wa, const TickArgs& tk, long long B, int ny,
-                           const double* q, const double* x, const double* y, double* dq, double* dx,
-                           double* slack, int32_t* status, hipStream_t stream, GwsOwner* owner);
-hipError_t qp_launch_data(int k, const DevSkill* dS, const WarmArgs& wa, const TickArgs& tk, long long B, int ny,
-                          const double* q, const double* x, const double* y, double* Hd, double* A, double* lb,
-                          double* ub, hipStream_t stream, GwsOwner* owner);
-bool qp_variant_uses_workspace(int k);
-int qp_pick_variant(int n, int nv, int nc);
-int qp_variant_width(int k);
-size_t qp_variant_lds(int k, int ny);
-int qp_pick_static(const ShapeDesc& sd);
-const char* qp_static_name(int k);
-int team_waves_rt(long long B);                 // (clik_pinv.hip)
-hipError_t launch_ticket_feed(void* ticket, const unsigned* done, int n_ticks, int closed_loop, unsigned waves_per_tick,
-                              unsigned long long timeout_ticks, hipStream_t stream);
-hipError_t qp_launch_static(int k, const void* d_img, const TickArgs& tk, long long B, const double* q,
-                            const double* x, const double* y, double* dq, double* dx, double* slack,
-                            int32_t* status, int32_t* hot_set, int use_hot, hipStream_t stream,
-                            const double* t_inst);
-hipError_t qp_launch_rollout_static(int k, const void* d_img, const double* d_tterms, int n_ticks, double dt,
-                                    double max_speed, long long B, double* q, const double* y, double* dq,
-                                    double* slack, int32_t* status, double* x, double* dx, hipStream_t stream,
-                                    int stages);
-}  // namespace clik
+#include "clik_launch.hpp"
 
 using clik::DevSkill;
 using clik::TickArgs;
@@ -103,35 +68,45 @@ typedef hipError_t (*clik_converge_fn)(const clik::LaunchArgs*, const TickArgs*,
 typedef hipError_t (*clik_jit_value_fn)(const clik::LaunchArgs*, const TickArgs*, long long, const double*,
                                         const double*, double*, int32_t*, hipStream_t);
 
-struct clik_pinv {
-    DevSkill  host;
-    DevSkill* dev;
-    clik::WarmArgs warm;
-    void*     d_img;        // static kernels: device copy of the compact skill image
-    clik::PinvPolicy policy; // the switches pinv_select reads
+// What both handles hold: the skill (host copy, device copy, warm-up ranges, image on the device) and the kernels that
+// do not depend on the controller.  The handle owns its device memory: `delete h` releases it.
+struct clik_handle {
+    DevSkill  host = {};
+    DevSkill* dev = nullptr;        // null: a host-only handle (clik_*_create_host)
+    clik::WarmArgs warm = {};
+    void*     d_img = nullptr;      // shape-specialised kernels: device copy of the skill image (QP: + the QP options)
+    char      jit_name[64] = "";
+    clik_time_fn time_fn = nullptr;         // the skill's time slots as device code (clik_*_attach_time_kernel)
+    clik_monitor_fn monitor_fn = nullptr;   // e, J, d e / d t of the constraints over a trajectory (clik_*_attach_monitor_kernel)
+    clik_summary_fn summary_fn = nullptr;   // per-instance summaries of them (clik_*_attach_summary_kernel)
+    clik_summary_work_fn summary_work_fn = nullptr;
+    clik_handle() = default;
+    clik_handle(const clik_handle&) = delete;
+    clik_handle& operator=(const clik_handle&) = delete;
+    ~clik_handle()
+    {
+        if (d_img) (void)hipFree(d_img);
+        if (dev) (void)hipFree(dev);
+    }
+};
+
+struct clik_pinv : clik_handle {
+    clik::PinvPolicy policy = {};   // the switches pinv_select reads
     // shape-specialised kernel attached at run time (clik_pinv_attach_kernel)
-    clik_jit_solve_fn   jit_solve;
-    clik_jit_rollout_fn jit_rollout;
-    char      jit_name[64];
-    int       kernel;       // index into the kernel table (static shape or dynamic)
+    clik_jit_solve_fn   jit_solve = nullptr;
+    clik_jit_rollout_fn jit_rollout = nullptr;
+    int       kernel = -1;          // index into the kernel table (static shape or dynamic)
     // team kernel with this skill's numbers compiled in (clik_pinv_attach_value_kernel), used for the batches the
     // image-reading team kernel would serve
-    clik_jit_value_fn   val_solve;
-    clik_jit_rollout_fn val_rollout;
+    clik_jit_value_fn   val_solve = nullptr;
+    clik_jit_rollout_fn val_rollout = nullptr;
     // ... and its resident form (clik_pinv_attach_resident_kernel)
     hipError_t (*val_resident)(const TickArgs*, long long, const double*, const double*, double*, int32_t*, void*,
-                               unsigned*, int, unsigned long long, hipStream_t);
+                               unsigned*, int, unsigned long long, hipStream_t) = nullptr;
     // the recording / per-tick-target rollouts (clik_pinv_attach_rec_kernel): image-reading and value-specialised
     clik_jit_rollout_fn rec_rollout = nullptr;
     clik_jit_rollout_fn val_rec_rollout = nullptr;
-    // the skill's time slots as device code (clik_pinv_attach_time_kernel)
-    clik_time_fn time_fn = nullptr;
-    // e, J, d e / d t of the skill's constraints over a trajectory (clik_pinv_attach_monitor_kernel)
-    clik_monitor_fn monitor_fn = nullptr;
-    // per-instance summaries of them over a trajectory (clik_pinv_attach_summary_kernel)
-    clik_summary_fn summary_fn = nullptr;
-    clik_summary_work_fn summary_work_fn = nullptr;
-    // the rollout that summarises them while it runs (clik_pinv_attach_rollout_summary_kernel)
+    // the rollout that summarises the constraint values while it runs (clik_pinv_attach_rollout_summary_kernel)
     clik_rollsum_fn rollsum_fn = nullptr;
     // the rollout that runs until each instance has converged (clik_pinv_attach_converge_kernel)
     clik_converge_fn converge_fn = nullptr;
@@ -153,38 +128,27 @@ typedef hipError_t (*clik_qp_converge_fn)(const void*, const TickArgs*, long lon
                                           const double*, double*, double*, int32_t*, double*, double*, hipStream_t,
                                           const double*, int32_t*, int32_t*, double*);
 
-struct clik_qp {
-    DevSkill  host;
-    DevSkill* dev;
-    clik::WarmArgs warm;
-    int       variant;      // dynamic kernel variant (qp_data and the fallback use it); -1: the skill only fits
-                            // the shape-specialised kernels
-    void*     d_img;        // shape-specialised kernels: skill image + QP options
-    int       static_k;     // AOT shape-specialised kernel, -1 none
-    clik::QpPolicy policy;  // the switches qp_select reads
-    clik::qp_jit_fn jit_solve;
-    clik::qp_static_rollout_fn jit_rollout;
-    clik::qp_value_fn val_solve;     // per-tick kernel with this skill's numbers and QP options compiled in
-    clik::qp_value_rollout_fn val_rollout;   // ... and its on-device rollout (box family), or null
-    clik::qp_value_resident_fn val_resident; // ... and its resident form (clik_qp_attach_resident_kernel), or null
+struct clik_qp : clik_handle {
+    int       variant = -1;     // dynamic kernel variant (qp_data and the fallback use it); -1: the skill only fits
+                                // the shape-specialised kernels
+    int       static_k = -1;    // AOT shape-specialised kernel, -1 none
+    clik::QpPolicy policy = {}; // the switches qp_select reads
+    clik::qp_jit_fn jit_solve = nullptr;
+    clik::qp_static_rollout_fn jit_rollout = nullptr;
+    clik::qp_value_fn val_solve = nullptr;     // per-tick kernel with this skill's numbers and QP options compiled in
+    clik::qp_value_rollout_fn val_rollout = nullptr;   // ... and its on-device rollout (box family), or null
+    clik::qp_value_resident_fn val_resident = nullptr; // ... and its resident form (clik_qp_attach_resident_kernel), or null
     // the recording / per-tick-target rollouts (clik_qp_attach_rec_kernel): image-reading and value-specialised (box)
     clik_qp_rec_fn rec_rollout = nullptr;
     clik_qp_value_rec_fn val_rec_rollout = nullptr;
-    clik_time_fn time_fn = nullptr;          // the skill's time slots as device code (clik_qp_attach_time_kernel)
-    clik_monitor_fn monitor_fn = nullptr;    // constraint values over a trajectory (clik_qp_attach_monitor_kernel)
-    clik_summary_fn summary_fn = nullptr;    // their per-instance summaries (clik_qp_attach_summary_kernel)
-    clik_summary_work_fn summary_work_fn = nullptr;
     clik_qp_rollsum_fn rollsum_fn = nullptr; // the rollout that summarises them (clik_qp_attach_rollout_summary_kernel)
     clik_qp_converge_fn converge_fn = nullptr; // the rollout that runs to convergence (clik_qp_attach_converge_kernel)
-    char      jit_name[64];
-    // work area of the global-workspace kernels (clik_workspace.hpp): belongs to this handle, released by clik_qp_destroy
-    clik::GwsOwner* gws;
+    // work area of the global-workspace kernels (clik_workspace.hpp): belongs to this handle, released with it
+    std::unique_ptr<clik::GwsOwner> gws;
+    // (runs before the base frees dev and d_img; the three allocations are independent, so the order does not matter)
     ~clik_qp()
     {
-        if (gws) {
-            gws->release();
-            delete gws;
-        }
+        if (gws) gws->release();
     }
 };
 
@@ -214,8 +178,9 @@ static int popcount32(unsigned v)
     return c;
 }
 
-// Structural validation shared by both controllers; fills the derived fields.
-static int validate_and_derive(const clik_skill_desc* d, DevSkill* S)
+// Structural validation shared by both controllers; fills the derived fields.  *used_rows (may be null): the number of
+// affine rows the constraints use, for the warm-up ranges.
+static int validate_and_derive(const clik_skill_desc* d, DevSkill* S, int* used_rows = nullptr)
 {
     if (!d) return fail(CLIK_EINVAL, "null skill descriptor");
     if (d->abi_version != CLIK_ABI_VERSION)
@@ -388,7 +353,7 @@ static int validate_and_derive(const clik_skill_desc* d, DevSkill* S)
     }
     S->shape.uses_fk = any_fk ? 1 : 0;
     S->shape.quat_src = any_o ? d->quat_src : 0;
-    S->lds_slots = last_row;   // (temporarily) number of used affine rows, for the warm-up ranges
+    if (used_rows) *used_rows = last_row;
     if (any_fk && d->n_joints == 0) return fail(CLIK_EINVAL, "rows use the tool frame but the chain is empty");
     if (any_o && d->quat_src == 0) return fail(CLIK_EINVAL, "rows use the orientation error but no target is set");
     S->d.uses_fk = any_fk ? 1 : 0;
@@ -678,10 +643,10 @@ static std::string shape_to_string(const clik::ShapeDesc& h)
 extern "C" int clik_shape_describe(const clik_skill_desc* desc, const clik_pinv_opts* opts, char* buf, int cap)
 {
     if (!opts || !buf || cap <= 0) return fail(CLIK_EINVAL, "bad arguments");
-    DevSkill* S = new (std::nothrow) DevSkill();
+    std::unique_ptr<DevSkill> S(new (std::nothrow) DevSkill());
     if (!S) return fail(CLIK_ENOMEM, "out of host memory");
-    int rc = validate_and_derive(desc, S);
-    if (rc) { delete S; return rc; }
+    int rc = validate_and_derive(desc, S.get());
+    if (rc) return rc;
     finish_pinv_shape(*S, opts);
     const clik::ShapeDesc& h = S->shape;
     const std::string o = shape_to_string(h);
@@ -713,7 +678,6 @@ extern "C" int clik_shape_describe(const clik_skill_desc* desc, const clik_pinv_
             r += h.m[ti];
         }
     }
-    delete S;
     if ((int)o.size() + 1 > cap) return fail(CLIK_EINVAL, "buffer too small");
     memcpy(buf, o.c_str(), o.size() + 1);
     return eligible ? 1 : 0;
@@ -736,46 +700,54 @@ static bool host_only_mode()
             return fail(CLIK_EINVAL, "this handle was created host-only (clik_*_create_host / CLIK_HOST_ONLY=1): host-side queries only"); \
     } while (0)
 
+// one copy of the skill image on the device, owned by the handle (h->d_img, null on failure)
+static hipError_t upload_image(clik_handle* h, const std::vector<char>& img)
+{
+    hipError_t e = hipMalloc(&h->d_img, img.size());
+    if (e == hipSuccess) e = hipMemcpy(h->d_img, img.data(), img.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess && h->d_img) {
+        (void)hipFree(h->d_img);
+        h->d_img = nullptr;
+    }
+    return e;
+}
+
+// the DevSkill record on the device (h->dev), unless the handle is host-only
+static int upload_skill(clik_handle* h)
+{
+    if (host_only_mode()) return CLIK_OK;
+    hipError_t e = hipMalloc((void**)&h->dev, sizeof(DevSkill));
+    if (e != hipSuccess) return hipfail(e, "hipMalloc(skill)");
+    e = hipMemcpy(h->dev, &h->host, sizeof(DevSkill), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hipfail(e, "hipMemcpy(skill)");
+    return CLIK_OK;
+}
+
 extern "C" int clik_pinv_create(const clik_skill_desc* desc, const clik_pinv_opts* opts, clik_pinv** out)
 {
     if (!out) return fail(CLIK_EINVAL, "null out pointer");
     *out = nullptr;
     if (!opts) return fail(CLIK_EINVAL, "null options");
-    clik_pinv* h = new (std::nothrow) clik_pinv();
+    std::unique_ptr<clik_pinv> h(new (std::nothrow) clik_pinv());
     if (!h) return fail(CLIK_ENOMEM, "out of host memory");
-    int rc = validate_and_derive(desc, &h->host);
-    if (rc) { delete h; return rc; }
+    int used_rows = 0;
+    int rc = validate_and_derive(desc, &h->host, &used_rows);
+    if (rc) return rc;
     DevSkill& S = h->host;
-    h->d_img = nullptr;
-    h->val_solve = nullptr;
-    h->val_rollout = nullptr;
-    h->val_resident = nullptr;
-    h->jit_solve = nullptr;
-    h->jit_rollout = nullptr;
-    h->val_solve = nullptr;
-    h->val_rollout = nullptr;
-    h->val_resident = nullptr;
-    h->jit_name[0] = 0;
     finish_pinv_shape(S, opts);
-    if (opts->pinv_method != CLIK_PINV_DAMPED && opts->pinv_method != CLIK_PINV_STANDARD) {
-        delete h;
+    if (opts->pinv_method != CLIK_PINV_DAMPED && opts->pinv_method != CLIK_PINV_STANDARD)
         return fail(CLIK_EINVAL, "pinv_method must be damped or standard");
-    }
-    if (S.n_sets > CLIK_MAX_SETS) {
-        delete h;
+    if (S.n_sets > CLIK_MAX_SETS)
         return fail(CLIK_EUNSUPPORTED, "%d SetConstraints give 2^%d modes (limit %d sets)", S.n_sets, S.n_sets,
                     CLIK_MAX_SETS);
-    }
     for (int ti = 0; ti < S.d.n_tasks; ++ti) {
         const clik_task& t = S.d.tasks[ti];
-        if (t.cls == CLIK_CLS_SET && t.m > 1 && !opts->multidim_sets) {
+        if (t.cls == CLIK_CLS_SET && t.m > 1 && !opts->multidim_sets)
             // same refusal as pseudo_inverse.py:299-312
-            delete h;
             return fail(CLIK_EUNSUPPORTED,
                         "PseudoInverseController does not yet have guaranteed stable support for "
                         "multidimensional SetConstraints (task %d has %d rows). Set the multidim_sets "
                         "field in options to True for experimental support.", ti, t.m);
-        }
     }
     // mode table (pseudo_inverse.py:107-130): bit k <-> k-th SetConstraint in
     // priority order; patterns stably sorted by the number of active sets
@@ -808,43 +780,25 @@ extern "C" int clik_pinv_create(const clik_skill_desc* desc, const clik_pinv_opt
         const char* noaot = getenv("CLIK_NO_AOT");
         h->kernel = clik::pinv_pick_kernel(S, ((force && force[0] == '1') || (noaot && noaot[0] == '1')) ? 0 : 1);
     }
-    if (h->kernel < 0 && !skill_has_wide_task(S) && S.n <= 8) {
-        delete h;
+    if (h->kernel < 0 && !skill_has_wide_task(S) && S.n <= 8)
         return fail(CLIK_EUNSUPPORTED, "no kernel variant for n = %d", S.n);
-    }
     // (kernel < 0 with a wide constraint or with more than eight state variables - a 7-DoF arm with two or three
     // virtual variables, CLIK_MAX_DOF = 10: no built-in kernel is wide enough; the handle solves once a kernel
     // instantiated for the skill is attached, and answers CLIK_EUNSUPPORTED until then)
-    compute_warm(S, S.lds_slots, h->warm);
-    S.zero_token = 0;
+    compute_warm(S, used_rows, h->warm);
     S.lds_slots = clik::pinv_lds_slots_host(clik::pinv_kernel_width(h->kernel), S.d.n_y);
-    if ((size_t)S.lds_slots * clik::WAVE * sizeof(double) > clik::kLdsBytesPerCu) {
-        delete h;
+    if ((size_t)S.lds_slots * clik::WAVE * sizeof(double) > clik::kLdsBytesPerCu)
         return fail(CLIK_EUNSUPPORTED, "skill needs %d LDS slots per lane (input_var too large)", S.lds_slots);
-    }
-    h->dev = nullptr;
-    const bool host_only = host_only_mode();
-    hipError_t e = hipSuccess;
-    if (!host_only) {
-        e = hipMalloc((void**)&h->dev, sizeof(DevSkill));
-        if (e != hipSuccess) { delete h; return hipfail(e, "hipMalloc(skill)"); }
-        e = hipMemcpy(h->dev, &S, sizeof(DevSkill), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(h->dev); delete h; return hipfail(e, "hipMemcpy(skill)"); }
-    }
-    if (!host_only && clik::pinv_kernel_is_static(h->kernel)) {
+    rc = upload_skill(h.get());
+    if (rc) return rc;
+    if (h->dev && clik::pinv_kernel_is_static(h->kernel)) {
         std::vector<char> img;
         if (!build_skill_image(S, img)) {
             // rows not laid out contiguously: serve the skill with the dynamic kernel
             h->kernel = clik::pinv_pick_kernel(S, 0);
         } else {
-            e = hipMalloc(&h->d_img, img.size());
-            if (e == hipSuccess) e = hipMemcpy(h->d_img, img.data(), img.size(), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                if (h->d_img) (void)hipFree(h->d_img);
-                (void)hipFree(h->dev);
-                delete h;
-                return hipfail(e, "skill image upload");
-            }
+            const hipError_t e = upload_image(h.get(), img);
+            if (e != hipSuccess) return hipfail(e, "skill image upload");
         }
     }
     {
@@ -866,10 +820,9 @@ extern "C" int clik_pinv_create(const clik_skill_desc* desc, const clik_pinv_opt
                                                                  : clik::PinvLanes::lane;
         h->policy.large_batch = !(lb && lb[0] == '0');
         h->policy.aot_large_batch_build = clik::pinv_kernel_is_static(h->kernel) != 0;
-        h->policy.values_attached = false;
         h->policy.quad_front = !(qf && qf[0] == '0');
     }
-    *out = h;
+    *out = h.release();
     return CLIK_OK;
 }
 
@@ -886,13 +839,8 @@ extern "C" int clik_pinv_attach_kernel(clik_pinv* h, void* solve_fn, void* rollo
         std::vector<char> img;
         if (!build_skill_image(h->host, img))
             return fail(CLIK_EUNSUPPORTED, "skill rows are not contiguous: no static kernel possible");
-        hipError_t e = hipMalloc(&h->d_img, img.size());
-        if (e == hipSuccess) e = hipMemcpy(h->d_img, img.data(), img.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            if (h->d_img) (void)hipFree(h->d_img);
-            h->d_img = nullptr;
-            return hipfail(e, "skill image upload");
-        }
+        const hipError_t e = upload_image(h, img);
+        if (e != hipSuccess) return hipfail(e, "skill image upload");
     }
     h->jit_solve = (clik_jit_solve_fn)solve_fn;
     h->jit_rollout = (clik_jit_rollout_fn)rollout_fn;
@@ -912,7 +860,64 @@ extern "C" int clik_pinv_attach_value_kernel(clik_pinv* h, void* solve_fn, void*
     return CLIK_OK;
 }
 
-static int fill_tick(const DevSkill& S, const double* tterms, TickArgs* tk);
+static int fill_tick(const DevSkill& S, const double* tterms, TickArgs* tk)
+{
+    memset(tk, 0, sizeof(*tk));
+    const int nts = S.d.n_tslots;
+    if (nts > 0) {
+        if (!tterms) return fail(CLIK_EINVAL, "skill has %d time slots but tterms is NULL", nts);
+        memcpy(tk->tv, tterms, sizeof(double) * 2 * nts);
+    }
+    return CLIK_OK;
+}
+
+// ---- what the launch paths check the same way ----------------------------------------------------------------------------
+static int input_var_check(const DevSkill& S, const double* y)
+{
+    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    return CLIK_OK;
+}
+
+// x / dx of a skill with virtual variables (`x_hint`: what a rollout's refusal adds - the entry point that takes x)
+static int virtual_var_check(const DevSkill& S, const double* x, const double* dx, const char* x_hint = "")
+{
+    if (S.d.n_x > 0 && (!x || !dx)) return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required%s", x_hint);
+    return CLIK_OK;
+}
+
+// q / dq, then y of a skill with input_var
+static int joint_args_check(const DevSkill& S, const double* q, const double* y, const double* dq)
+{
+    if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
+    return input_var_check(S, y);
+}
+
+// the state a tick or rollout reads and the rates it writes (device), checked in this order everywhere.  (The rollouts that
+// ask for x / dx BEFORE their kernel-presence checks call the two halves themselves, each at its place.)
+static int state_args_check(const DevSkill& S, const double* q, const double* x, const double* y, const double* dq,
+                            const double* dx)
+{
+    const int rc = virtual_var_check(S, x, dx);
+    return rc ? rc : joint_args_check(S, q, y, dq);
+}
+
+// controller evaluations per tick of an integration scheme (`who`: the prefix of the QP rollouts' refusal)
+static int stages_of(int32_t method, int* stages, const char* who = "")
+{
+    if (method != CLIK_INTEGRATE_EULER && method != CLIK_INTEGRATE_RK4)
+        return fail(CLIK_EINVAL, "%sunknown integration method %d", who, method);
+    *stages = method == CLIK_INTEGRATE_RK4 ? 4 : 1;
+    return CLIK_OK;
+}
+
+// what the pseudo-inverse launchers take next to the batch: the handle's skill and policy, the virtual variables of a
+// rollout, its stages, the per-instance times of a tick, the records of a recording rollout
+static clik::LaunchArgs launch_args(const clik_pinv* h, double* x, double* dx, int stages, const double* t_inst,
+                                    const clik::RollRec* rec)
+{
+    const DevSkill& S = h->host;
+    return {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->policy, x, dx, stages, t_inst, rec};
+}
 
 extern "C" int clik_pinv_attach_resident_kernel(clik_pinv* h, void* resident_fn)
 {
@@ -954,25 +959,35 @@ extern "C" int clik_pinv_resident_run_state(const clik_pinv* h, int64_t B, int32
                                stream);
 }
 
+// what the resident runs of both controllers check before they launch (`attached`: the handle has its resident kernel;
+// `missing`: what to say when not) and the one record of time terms they run with
+static int resident_checks(const clik_handle* h, bool attached, const char* missing, int64_t B, int32_t n_ticks,
+                           const double* tterms, const double* q, const double* y, const double* dq,
+                           const clik_ticket* ticket, const uint32_t* done, double timeout_s, TickArgs* tk)
+{
+    if (!attached) return fail(CLIK_EUNSUPPORTED, "%s", missing);
+    if (B <= 0 || n_ticks <= 0) return fail(CLIK_EINVAL, "B and n_ticks must be positive");
+    if (!q || !dq || !ticket || !done) return fail(CLIK_EINVAL, "q, dq, ticket and done must be device pointers");
+    const int rc = input_var_check(h->host, y);
+    if (rc) return rc;
+    if (!(timeout_s > 0.0) || timeout_s > 60.0) return fail(CLIK_EINVAL, "timeout_s must lie in (0, 60]");
+    return fill_tick(h->host, tterms, tk);
+}
+
 static int resident_run_common(const clik_pinv* h, int64_t B, int32_t n_ticks, const double* tterms, const double* q,
                                const double* y, double* dq, int32_t* mode, clik_ticket* ticket, uint32_t* done,
                                double integrate_dt, double max_speed, double timeout_s, void* stream)
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
     CLIK_NEEDS_DEVICE_HANDLE(h);
-    if (!h->val_resident)
-        return fail(CLIK_EUNSUPPORTED, "resident ticks need the value-specialised kernel of the four-lanes-per-instance "
-                                       "family attached to this handle (none is)");
-    if (B <= 0 || n_ticks <= 0) return fail(CLIK_EINVAL, "B and n_ticks must be positive");
-    if (!q || !dq || !ticket || !done) return fail(CLIK_EINVAL, "q, dq, ticket and done must be device pointers");
-    const DevSkill& S = h->host;
-    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
-    if (!(timeout_s > 0.0) || timeout_s > 60.0) return fail(CLIK_EINVAL, "timeout_s must lie in (0, 60]");
+    TickArgs tk;
+    const int rc = resident_checks(h, h->val_resident != nullptr,
+                                   "resident ticks need the value-specialised kernel of the four-lanes-per-instance "
+                                   "family attached to this handle (none is)",
+                                   B, n_ticks, tterms, q, y, dq, ticket, done, timeout_s, &tk);
+    if (rc) return rc;
     // (every wave of the launch must be resident at once: the launch wrapper of the instantiated kernel checks the grid
     // against that kernel's occupancy on this device and answers hipErrorNotSupported beyond it)
-    TickArgs tk;
-    int rc = fill_tick(S, tterms, &tk);
-    if (rc) return rc;
     // (watchdog budget: polls at a nominal 0.2 us each - a load that hits the L2 plus s_sleep 1; round 6 found the
     // budget of the earlier 2.5 us figure used up in a tenth of timeout_s)
     unsigned long long budget = (unsigned long long)(timeout_s * 5e6);
@@ -1026,7 +1041,6 @@ extern "C" int clik_pinv_create_host(const clik_skill_desc* desc, const clik_pin
     g_host_only_call = false;
     return rc;
 }
-
 extern "C" int clik_qp_create_host(const clik_skill_desc* desc, const clik_qp_opts* opts, clik_qp** out)
 {
     g_host_only_call = true;
@@ -1037,10 +1051,7 @@ extern "C" int clik_qp_create_host(const clik_skill_desc* desc, const clik_qp_op
 
 extern "C" int clik_pinv_destroy(clik_pinv* h)
 {
-    if (!h) return CLIK_OK;
-    if (h->d_img) (void)hipFree(h->d_img);
-    if (h->dev) (void)hipFree(h->dev);
-    delete h;
+    delete h;       // (the handle releases what it holds on the device)
     return CLIK_OK;
 }
 
@@ -1058,17 +1069,6 @@ extern "C" const char* clik_pinv_kernel_variant(const clik_pinv* h, int64_t B)
     return clik::kPinvVariantName[(int)clik::pinv_select(h->host.shape, h->policy, (long long)B, clik::PinvOp::tick)];
 }
 
-static int fill_tick(const DevSkill& S, const double* tterms, TickArgs* tk)
-{
-    memset(tk, 0, sizeof(*tk));
-    const int nts = S.d.n_tslots;
-    if (nts > 0) {
-        if (!tterms) return fail(CLIK_EINVAL, "skill has %d time slots but tterms is NULL", nts);
-        memcpy(tk->tv, tterms, sizeof(double) * 2 * nts);
-    }
-    return CLIK_OK;
-}
-
 static int pinv_solve_common(const clik_pinv* h, int64_t B, const double* tterms, const double* t_inst,
                              const double* q, const double* x, const double* y, double* dq, double* dx,
                              int32_t* mode, void* stream)
@@ -1078,22 +1078,20 @@ static int pinv_solve_common(const clik_pinv* h, int64_t B, const double* tterms
     if (B < 0) return fail(CLIK_EINVAL, "negative batch size");
     if (B == 0) return CLIK_OK;
     const DevSkill& S = h->host;
-    if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
-    if (S.d.n_x > 0 && (!x || !dx)) return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required");
-    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    int rc = state_args_check(S, q, x, y, dq, dx);
+    if (rc) return rc;
     const bool is_static = h->jit_solve || (h->kernel >= 0 && clik::pinv_kernel_is_static(h->kernel));
     if (!is_static && skill_needs_static(S)) return extern_needs_kernel("clik_pinv_solve_batch");
     if (h->kernel < 0 && !h->jit_solve) return no_kernel_for_wide_state(S, "clik_pinv_solve_batch");
     TickArgs tk;
     if (t_inst == nullptr) {
-        int rc = fill_tick(S, tterms, &tk);
+        rc = fill_tick(S, tterms, &tk);
         if (rc) return rc;
     } else if (!is_static) {
         return fail(CLIK_EUNSUPPORTED, "clik_pinv_solve_batch_t: per-instance time needs a shape-specialised kernel "
                                        "for the skill (none built in, none attached)");
     }
-    const clik::LaunchArgs la = {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->policy, nullptr, nullptr, 1,
-                                 t_inst};
+    const clik::LaunchArgs la = launch_args(h, nullptr, nullptr, 1, t_inst, nullptr);
     // (the value-specialised library evaluates its own batch limits - it may have been built with other
     // CLIK_VALUE_LANE_* settings than this one: hipErrorNotSupported means "not mine", and the image-reading
     // kernels take the call)
@@ -1139,14 +1137,29 @@ extern "C" int clik_pinv_solve_batch_t(const clik_pinv* h, int64_t B, const doub
 // no pinned slot: their tick times are a device array and the time kernel fills the records on the stream, see
 // rollout_tterms.)
 namespace {
+// The record buffer of one rollout call (null: the skill has no time slots).  Whoever holds it releases it in stream
+// order - hipFreeAsync on the stream it was made on - when it goes out of scope: a launch path keeps it until it
+// returns, so the release is enqueued behind the launch.
+struct TtBuffer {
+    double* ptr = nullptr;
+    hipStream_t stream = nullptr;
+    TtBuffer() = default;
+    TtBuffer(TtBuffer&& o) noexcept : ptr(o.ptr), stream(o.stream) { o.ptr = nullptr; }
+    TtBuffer(const TtBuffer&) = delete;
+    TtBuffer& operator=(const TtBuffer&) = delete;
+    TtBuffer& operator=(TtBuffer&&) = delete;
+    ~TtBuffer()
+    {
+        if (ptr) (void)hipFreeAsync(ptr, stream);
+    }
+};
 struct StageSlot { void* host = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool busy = false; int dev = -1; };
 std::mutex g_stage_mu;
 std::vector<StageSlot> g_stage_slots;
 }
 
-static int stage_tterms(const double* tterms, size_t count, hipStream_t stream, double** out)
+static int stage_tterms(const double* tterms, size_t count, hipStream_t stream, TtBuffer* out)
 {
-    *out = nullptr;
     if (count == 0) return CLIK_OK;
     if (!tterms) return fail(CLIK_EINVAL, "tterms required");
     const size_t bytes = count * sizeof(double);
@@ -1177,15 +1190,16 @@ static int stage_tterms(const double* tterms, size_t count, hipStream_t stream, 
         }
         slot->busy = true;
         std::memcpy(slot->host, tterms, bytes);
-        hipError_t e = hipMallocAsync((void**)out, bytes, stream);
-        if (e != hipSuccess) { *out = nullptr; slot->busy = false; return hipfail(e, "hipMallocAsync(tterms)"); }
-        e = hipMemcpyAsync(*out, slot->host, bytes, hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) e = hipEventRecord(slot->done, stream);
+        out->stream = stream;
+        hipError_t e = hipMallocAsync((void**)&out->ptr, bytes, stream);
         if (e != hipSuccess) {
-            (void)hipFreeAsync(*out, stream);
-            *out = nullptr;
-            return hipfail(e, "hipMemcpyAsync(tterms)");
+            out->ptr = nullptr;
+            slot->busy = false;
+            return hipfail(e, "hipMallocAsync(tterms)");
         }
+        e = hipMemcpyAsync(out->ptr, slot->host, bytes, hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) e = hipEventRecord(slot->done, stream);
+        if (e != hipSuccess) return hipfail(e, "hipMemcpyAsync(tterms)");       // (the caller leaves, and `out` releases it)
     }
     return CLIK_OK;
 }
@@ -1201,55 +1215,61 @@ struct TtSource {
 static TtSource tt_host(const double* tterms) { return TtSource{tterms, nullptr, nullptr, false}; }
 static TtSource tt_device(const double* times, clik_time_fn fn) { return TtSource{nullptr, times, fn, true}; }
 
-// the stream-ordered record buffer of one rollout call (*out; null when the skill has no time slots), filled from `src`
+// the stream-ordered record buffer of one rollout call, filled from `src` into `out` (an empty one, the caller's)
 static int rollout_tterms(const TtSource& src, int n_tslots, int n_ticks, int stages, double dt, hipStream_t stream,
-                          double** out)
+                          TtBuffer* out)
 {
     const size_t count = (size_t)n_ticks * stages * 2 * (size_t)n_tslots;
     if (!src.on_device) return stage_tterms(src.host, count, stream, out);
-    *out = nullptr;
     if (count == 0) return CLIK_OK;
     if (!src.times) return fail(CLIK_EINVAL, "times (device, [n_ticks]) required: the skill has time slots");
     if (!src.time_fn)
         return fail(CLIK_EUNSUPPORTED, "no time kernel attached for this skill (clik_*_attach_time_kernel)");
-    hipError_t e = hipMallocAsync((void**)out, count * sizeof(double), stream);
-    if (e != hipSuccess) { *out = nullptr; return hipfail(e, "hipMallocAsync(tterms)"); }
-    e = src.time_fn(src.times, (long long)n_ticks, stages, dt, *out, stream);
+    out->stream = stream;
+    hipError_t e = hipMallocAsync((void**)&out->ptr, count * sizeof(double), stream);
     if (e != hipSuccess) {
-        (void)hipFreeAsync(*out, stream);
-        *out = nullptr;
-        return hipfail(e, "time kernel launch");
+        out->ptr = nullptr;
+        return hipfail(e, "hipMallocAsync(tterms)");
     }
+    e = src.time_fn(src.times, (long long)n_ticks, stages, dt, out->ptr, stream);
+    if (e != hipSuccess) return hipfail(e, "time kernel launch");       // (the caller leaves, and `out` releases it)
     return CLIK_OK;
 }
 
-// what clik_*_time_terms check before they launch
-static int time_terms_common(clik_time_fn fn, int n_tslots, int64_t n_times, const double* times, int32_t stages, double dt,
-                             double* out, void* stream)
-{
-    if (n_times < 0) return fail(CLIK_EINVAL, "negative size");
-    if (stages != 1 && stages != 4) return fail(CLIK_EINVAL, "stages must be 1 or 4, got %d", stages);
-    if (n_tslots == 0 || n_times == 0) return CLIK_OK;
-    if (!fn) return fail(CLIK_EUNSUPPORTED, "no time kernel attached for this skill (clik_*_attach_time_kernel)");
-    if (!times || !out) return fail(CLIK_EINVAL, "times and out must be device pointers");
-    const hipError_t e = fn(times, (long long)n_times, stages, dt, out, (hipStream_t)stream);
-    if (e != hipSuccess) return hipfail(e, "time kernel launch");
-    return CLIK_OK;
-}
-
-extern "C" int clik_pinv_attach_time_kernel(clik_pinv* h, void* time_terms_fn)
+// ---- entry points that do not depend on the controller: written once over the base, forwarded to per controller -------
+static int attach_time_kernel(clik_handle* h, void* time_terms_fn)
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
     h->time_fn = (clik_time_fn)time_terms_fn;
     return CLIK_OK;
 }
 
-extern "C" int clik_pinv_time_terms(const clik_pinv* h, int64_t n_times, const double* times, int32_t stages, double dt,
-                                    double* out, void* stream)
+static int time_terms(const clik_handle* h, int64_t n_times, const double* times, int32_t stages, double dt, double* out,
+                      void* stream)
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
     CLIK_NEEDS_DEVICE_HANDLE(h);
-    return time_terms_common(h->time_fn, h->host.d.n_tslots, n_times, times, stages, dt, out, stream);
+    if (n_times < 0) return fail(CLIK_EINVAL, "negative size");
+    if (stages != 1 && stages != 4) return fail(CLIK_EINVAL, "stages must be 1 or 4, got %d", stages);
+    if (h->host.d.n_tslots == 0 || n_times == 0) return CLIK_OK;
+    if (!h->time_fn) return fail(CLIK_EUNSUPPORTED, "no time kernel attached for this skill (clik_*_attach_time_kernel)");
+    if (!times || !out) return fail(CLIK_EINVAL, "times and out must be device pointers");
+    const hipError_t e = h->time_fn(times, (long long)n_times, stages, dt, out, (hipStream_t)stream);
+    if (e != hipSuccess) return hipfail(e, "time kernel launch");
+    return CLIK_OK;
+}
+
+extern "C" int clik_pinv_attach_time_kernel(clik_pinv* h, void* fn) { return attach_time_kernel(h, fn); }
+extern "C" int clik_qp_attach_time_kernel(clik_qp* h, void* fn) { return attach_time_kernel(h, fn); }
+extern "C" int clik_pinv_time_terms(const clik_pinv* h, int64_t n_times, const double* times, int32_t stages, double dt,
+                                    double* out, void* stream)
+{
+    return time_terms(h, n_times, times, stages, dt, out, stream);
+}
+extern "C" int clik_qp_time_terms(const clik_qp* h, int64_t n_times, const double* times, int32_t stages, double dt,
+                                  double* out, void* stream)
+{
+    return time_terms(h, n_times, times, stages, dt, out, stream);
 }
 
 extern "C" int clik_pinv_rollout_batch(const clik_pinv* hc, int64_t B, int32_t n_ticks, double dt,
@@ -1331,26 +1351,103 @@ extern "C" int clik_pinv_rollout_batch_dev(const clik_pinv* h, int64_t B, int32_
     return pinv_rollout_common(h, B, n_ticks, method, dt, max_speed, tts, q, x, y, dq, dx, mode, stream, &rr);
 }
 
-// what the four clik_pinv_attach_*_kernel of the on-demand kernels check before they store a pointer: a shape-specialised
-// kernel serves this handle (`refusal` says what exists only then), and its image is on the device
-static int pinv_attach_checks(const clik_pinv* h, const char* refusal)
+// ---- attaching the on-demand kernels (recording, constraint values, summaries, summarising and converging rollouts) ---
+// The family check of a controller: does a shape-specialised kernel serve this handle (`refusal` says what exists only
+// then), and is its image on the device?
+static int pinv_attach_checks(clik_pinv* h, const char* refusal)
 {
     if (!h->jit_solve && !pinv_shape_served(h)) return fail(CLIK_EUNSUPPORTED, "%s", refusal);
     if (!h->d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device: attach the kernel first");
+    return CLIK_OK;
+}
+// ... of the QP controller: the skill is in the shape-specialised family; its image is uploaded here when no kernel of
+// that family runs yet (one refusal text for every kernel: kQpFamily)
+static int qp_attach_checks(clik_qp* h, const char* refusal);
+static const char* const kQpFamily = "skill is outside the shape-specialised QP family";
+
+// What every clik_*_attach_*_kernel of an on-demand kernel does: store `fn` in `slot` - attaching (fn non-null) needs a
+// device handle that passes the controller's family check, detaching needs nothing.
+template <class H, class Base, class Fn>
+static int attach_on_demand(H* h, Fn Base::*slot, void* fn, int (*family)(H*, const char*), const char* refusal)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    if (fn) {
+        CLIK_NEEDS_DEVICE_HANDLE(h);
+        const int rc = family(h, refusal);
+        if (rc) return rc;
+    }
+    h->*slot = (Fn)fn;
+    return CLIK_OK;
+}
+// ... the summary kernel comes with its work-size function
+template <class H>
+static int attach_summary_kernel(H* h, void* fn, void* work_bytes_fn, int (*family)(H*, const char*), const char* refusal)
+{
+    if (h && fn) {
+        CLIK_NEEDS_DEVICE_HANDLE(h);
+        if (!work_bytes_fn) return fail(CLIK_EINVAL, "the summary kernel comes with its work-size function");
+    }
+    const int rc = attach_on_demand(h, &clik_handle::summary_fn, fn, family, refusal);
+    if (rc) return rc;
+    h->summary_work_fn = fn ? (clik_summary_work_fn)work_bytes_fn : nullptr;
     return CLIK_OK;
 }
 
 extern "C" int clik_pinv_attach_rec_kernel(clik_pinv* h, void* rollout_rec_fn, void* value_rollout_rec_fn)
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
-    CLIK_NEEDS_DEVICE_HANDLE(h);        // (also when detaching, unlike the other three)
-    if (rollout_rec_fn) {
-        int rc = pinv_attach_checks(h, "recording rollouts exist for skills a shape-specialised kernel serves");
-        if (rc) return rc;
-    }
-    h->rec_rollout = (clik_jit_rollout_fn)rollout_rec_fn;
+    CLIK_NEEDS_DEVICE_HANDLE(h);        // (also when detaching, unlike the others)
+    const int rc = attach_on_demand(h, &clik_pinv::rec_rollout, rollout_rec_fn, pinv_attach_checks,
+                                    "recording rollouts exist for skills a shape-specialised kernel serves");
+    if (rc) return rc;
     h->val_rec_rollout = (clik_jit_rollout_fn)value_rollout_rec_fn;
     return CLIK_OK;
+}
+extern "C" int clik_qp_attach_rec_kernel(clik_qp* h, void* rollout_rec_fn, void* value_rollout_rec_fn)
+{
+    if (!h) return fail(CLIK_EINVAL, "null handle");
+    CLIK_NEEDS_DEVICE_HANDLE(h);        // (also when detaching, unlike the others)
+    const int rc = attach_on_demand(h, &clik_qp::rec_rollout, rollout_rec_fn, qp_attach_checks, kQpFamily);
+    if (rc) return rc;
+    // (the value-specialised rollout exists for the box family only)
+    h->val_rec_rollout = CLIK_QP_BOX_OK(h->host.shape) ? (clik_qp_value_rec_fn)value_rollout_rec_fn : nullptr;
+    return CLIK_OK;
+}
+extern "C" int clik_pinv_attach_monitor_kernel(clik_pinv* h, void* fn)
+{
+    return attach_on_demand(h, &clik_handle::monitor_fn, fn, pinv_attach_checks,
+                            "constraint values exist for skills a shape-specialised kernel serves");
+}
+extern "C" int clik_qp_attach_monitor_kernel(clik_qp* h, void* fn)
+{
+    return attach_on_demand(h, &clik_handle::monitor_fn, fn, qp_attach_checks, kQpFamily);
+}
+extern "C" int clik_pinv_attach_summary_kernel(clik_pinv* h, void* fn, void* work_bytes_fn)
+{
+    return attach_summary_kernel(h, fn, work_bytes_fn, pinv_attach_checks,
+                                 "constraint summaries exist for skills a shape-specialised kernel serves");
+}
+extern "C" int clik_qp_attach_summary_kernel(clik_qp* h, void* fn, void* work_bytes_fn)
+{
+    return attach_summary_kernel(h, fn, work_bytes_fn, qp_attach_checks, kQpFamily);
+}
+extern "C" int clik_pinv_attach_rollout_summary_kernel(clik_pinv* h, void* fn)
+{
+    return attach_on_demand(h, &clik_pinv::rollsum_fn, fn, pinv_attach_checks,
+                            "summarising rollouts exist for skills a shape-specialised kernel serves");
+}
+extern "C" int clik_qp_attach_rollout_summary_kernel(clik_qp* h, void* fn)
+{
+    return attach_on_demand(h, &clik_qp::rollsum_fn, fn, qp_attach_checks, kQpFamily);
+}
+extern "C" int clik_pinv_attach_converge_kernel(clik_pinv* h, void* fn)
+{
+    return attach_on_demand(h, &clik_pinv::converge_fn, fn, pinv_attach_checks,
+                            "converging rollouts exist for skills a shape-specialised kernel serves");
+}
+extern "C" int clik_qp_attach_converge_kernel(clik_qp* h, void* fn)
+{
+    return attach_on_demand(h, &clik_qp::converge_fn, fn, qp_attach_checks, kQpFamily);
 }
 
 // ---- constraint values over a trajectory (clik_*_constraint_values; the kernel: clik_monitor.hpp) ---------------------
@@ -1373,52 +1470,43 @@ static int trajectory_inputs_check(const DevSkill& S, const double* tterms, int6
     return CLIK_OK;
 }
 
-// what clik_*_constraint_values check before they launch (`host_only`: the handle has nothing on the device)
-static int constraint_values_common(clik_monitor_fn fn, const DevSkill& S, const void* d_img, bool host_only, int64_t n_rec,
-                                    int64_t B, const double* tterms, int64_t tt_rec_stride, int64_t tt_inst_stride,
-                                    const double* q, const double* x, const double* y, int64_t y_stride, double* e,
-                                    double* J, double* et, void* stream)
+static int constraint_values(const clik_handle* h, int64_t n_rec, int64_t B, const double* tterms, int64_t tt_rec_stride,
+                             int64_t tt_inst_stride, const double* q, const double* x, const double* y, int64_t y_stride,
+                             double* e, double* J, double* et, void* stream)
 {
+    if (!h) return fail(CLIK_EINVAL, "null handle");
     if (n_rec < 0 || B < 0) return fail(CLIK_EINVAL, "negative size");
     if (n_rec == 0 || B == 0) return CLIK_OK;
     if (!q) return fail(CLIK_EINVAL, "q must be a device pointer");
     if (!e && !J && !et) return fail(CLIK_EINVAL, "nothing to compute: e, J and et are all null");
-    if (!fn)
+    if (!h->monitor_fn)
         return fail(CLIK_EUNSUPPORTED, "no constraint-value kernel instantiated for this skill (clik_*_attach_monitor_kernel: "
                                        "skills of the shape-specialised family have one)");
-    if (host_only)
-        return fail(CLIK_EINVAL, "this handle was created host-only (clik_*_create_host / CLIK_HOST_ONLY=1): host-side queries only");
-    if (!d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device");
+    CLIK_NEEDS_DEVICE_HANDLE(h);
+    if (!h->d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device");
+    const DevSkill& S = h->host;
     const int rc = trajectory_inputs_check(S, tterms, tt_rec_stride, tt_inst_stride, x, y, y_stride);
     if (rc) return rc;
-    const hipError_t er = fn(d_img, (long long)n_rec, (long long)B, S.d.n_tslots > 0 ? tterms : nullptr,
-                             (long long)tt_rec_stride, (long long)tt_inst_stride, q, x, y, (long long)y_stride, e, J, et,
-                             (hipStream_t)stream);
+    const hipError_t er = h->monitor_fn(h->d_img, (long long)n_rec, (long long)B, S.d.n_tslots > 0 ? tterms : nullptr,
+                                        (long long)tt_rec_stride, (long long)tt_inst_stride, q, x, y, (long long)y_stride, e,
+                                        J, et, (hipStream_t)stream);
     if (er != hipSuccess) return hipfail(er, "constraint-value kernel launch");
     return CLIK_OK;
 }
 
-extern "C" int clik_pinv_attach_monitor_kernel(clik_pinv* h, void* constraint_values_fn)
-{
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    if (constraint_values_fn) {
-        CLIK_NEEDS_DEVICE_HANDLE(h);
-        int rc = pinv_attach_checks(h, "constraint values exist for skills a shape-specialised kernel serves");
-        if (rc) return rc;
-    }
-    h->monitor_fn = (clik_monitor_fn)constraint_values_fn;
-    return CLIK_OK;
-}
-
 extern "C" int clik_pinv_n_constraint_rows(const clik_pinv* h) { return h ? n_constraint_rows(h->host) : 0; }
-
+extern "C" int clik_qp_n_constraint_rows(const clik_qp* h) { return h ? n_constraint_rows(h->host) : 0; }
 extern "C" int clik_pinv_constraint_values(const clik_pinv* h, int64_t n_rec, int64_t B, const double* tterms,
                                            int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
                                            const double* y, int64_t y_stride, double* e, double* J, double* et, void* stream)
 {
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    return constraint_values_common(h->monitor_fn, h->host, h->d_img, h->dev == nullptr, n_rec, B, tterms, tt_rec_stride,
-                                    tt_inst_stride, q, x, y, y_stride, e, J, et, stream);
+    return constraint_values(h, n_rec, B, tterms, tt_rec_stride, tt_inst_stride, q, x, y, y_stride, e, J, et, stream);
+}
+extern "C" int clik_qp_constraint_values(const clik_qp* h, int64_t n_rec, int64_t B, const double* tterms,
+                                         int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
+                                         const double* y, int64_t y_stride, double* e, double* J, double* et, void* stream)
+{
+    return constraint_values(h, n_rec, B, tterms, tt_rec_stride, tt_inst_stride, q, x, y, y_stride, e, J, et, stream);
 }
 
 // ---- constraint summaries over a trajectory (clik_*_constraint_summary; the kernels: clik_summary.hpp) -----------------
@@ -1438,41 +1526,40 @@ static int summary_io_check(const SummaryIo& o)
     return CLIK_OK;
 }
 
-// what clik_*_constraint_summary check before they launch
-static int constraint_summary_common(clik_summary_fn fn, clik_summary_work_fn work_fn, const DevSkill& S, const void* d_img,
-                                     bool host_only, int64_t n_rec, int64_t B, const double* tterms, int64_t tt_rec_stride,
-                                     int64_t tt_inst_stride, const double* q, const double* x, const double* y,
-                                     int64_t y_stride, void* work, int64_t work_bytes, const SummaryIo& o, void* stream)
+static int constraint_summary(const clik_handle* h, int64_t n_rec, int64_t B, const double* tterms, int64_t tt_rec_stride,
+                              int64_t tt_inst_stride, const double* q, const double* x, const double* y, int64_t y_stride,
+                              void* work, int64_t work_bytes, const SummaryIo& o, void* stream)
 {
+    if (!h) return fail(CLIK_EINVAL, "null handle");
     if (n_rec < 0 || B < 0) return fail(CLIK_EINVAL, "negative size");
     if (n_rec == 0 || B == 0) return CLIK_OK;
     if (!q) return fail(CLIK_EINVAL, "q must be a device pointer");
     int rc = summary_io_check(o);
     if (rc) return rc;
-    if (!fn || !work_fn)
+    if (!h->summary_fn || !h->summary_work_fn)
         return fail(CLIK_EUNSUPPORTED, "no constraint-summary kernel instantiated for this skill (clik_*_attach_summary_kernel: "
                                        "skills of the shape-specialised family have one)");
-    if (host_only)
-        return fail(CLIK_EINVAL, "this handle was created host-only (clik_*_create_host / CLIK_HOST_ONLY=1): host-side queries only");
-    if (!d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device");
+    CLIK_NEEDS_DEVICE_HANDLE(h);
+    if (!h->d_img) return fail(CLIK_EUNSUPPORTED, "no skill image on the device");
     if (n_rec > 0x7fffffffLL) return fail(CLIK_EINVAL, "more than 2^31 - 1 records");
+    const DevSkill& S = h->host;
     rc = trajectory_inputs_check(S, tterms, tt_rec_stride, tt_inst_stride, x, y, y_stride);
     if (rc) return rc;
-    const unsigned long long need = work_fn((long long)n_rec, (long long)B);
+    const unsigned long long need = h->summary_work_fn((long long)n_rec, (long long)B);
     if (!work || work_bytes < 0 || (unsigned long long)work_bytes < need)
         return fail(CLIK_EINVAL, "work must hold %llu bytes (clik_*_summary_work_bytes), got %lld", need, (long long)work_bytes);
-    const hipError_t er = fn(d_img, (long long)n_rec, (long long)B, S.d.n_tslots > 0 ? tterms : nullptr,
-                             (long long)tt_rec_stride, (long long)tt_inst_stride, q, x, y, (long long)y_stride, o.tol, work,
-                             (unsigned long long)work_bytes, o.abs_max, o.abs_max_at, o.last, o.rms, o.viol_max, o.viol_count,
-                             o.settled_at, (hipStream_t)stream);
+    const hipError_t er = h->summary_fn(h->d_img, (long long)n_rec, (long long)B, S.d.n_tslots > 0 ? tterms : nullptr,
+                                        (long long)tt_rec_stride, (long long)tt_inst_stride, q, x, y, (long long)y_stride,
+                                        o.tol, work, (unsigned long long)work_bytes, o.abs_max, o.abs_max_at, o.last, o.rms,
+                                        o.viol_max, o.viol_count, o.settled_at, (hipStream_t)stream);
     if (er != hipSuccess) return hipfail(er, "constraint-summary kernel launch");
     return CLIK_OK;
 }
 
-static int64_t summary_work_bytes_common(clik_summary_work_fn work_fn, int64_t n_rec, int64_t B)
+static int64_t summary_work_bytes(const clik_handle* h, int64_t n_rec, int64_t B)
 {
-    if (!work_fn || n_rec <= 0 || B <= 0) return 0;
-    return (int64_t)work_fn((long long)n_rec, (long long)B);
+    if (!h || !h->summary_work_fn || n_rec <= 0 || B <= 0) return 0;
+    return (int64_t)h->summary_work_fn((long long)n_rec, (long long)B);
 }
 
 extern "C" int64_t clik_summary_chunk_length(int64_t n_rec, int64_t B)
@@ -1485,25 +1572,14 @@ extern "C" int64_t clik_summary_chunk_length(int64_t n_rec, int64_t B)
     return c > 8 ? c : 8;
 }
 
-extern "C" int clik_pinv_attach_summary_kernel(clik_pinv* h, void* constraint_summary_fn, void* work_bytes_fn)
-{
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    if (constraint_summary_fn) {
-        CLIK_NEEDS_DEVICE_HANDLE(h);
-        if (!work_bytes_fn) return fail(CLIK_EINVAL, "the summary kernel comes with its work-size function");
-        int rc = pinv_attach_checks(h, "constraint summaries exist for skills a shape-specialised kernel serves");
-        if (rc) return rc;
-    }
-    h->summary_fn = (clik_summary_fn)constraint_summary_fn;
-    h->summary_work_fn = constraint_summary_fn ? (clik_summary_work_fn)work_bytes_fn : nullptr;
-    return CLIK_OK;
-}
-
 extern "C" int64_t clik_pinv_summary_work_bytes(const clik_pinv* h, int64_t n_rec, int64_t B)
 {
-    return h ? summary_work_bytes_common(h->summary_work_fn, n_rec, B) : 0;
+    return summary_work_bytes(h, n_rec, B);
 }
-
+extern "C" int64_t clik_qp_summary_work_bytes(const clik_qp* h, int64_t n_rec, int64_t B)
+{
+    return summary_work_bytes(h, n_rec, B);
+}
 extern "C" int clik_pinv_constraint_summary(const clik_pinv* h, int64_t n_rec, int64_t B, const double* tterms,
                                             int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
                                             const double* y, int64_t y_stride, const double* tol, void* work,
@@ -1511,10 +1587,17 @@ extern "C" int clik_pinv_constraint_summary(const clik_pinv* h, int64_t n_rec, i
                                             double* rms, double* viol_max, int32_t* viol_count, int32_t* settled_at,
                                             void* stream)
 {
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    const SummaryIo o = {tol, abs_max, abs_max_at, last, rms, viol_max, viol_count, settled_at};
-    return constraint_summary_common(h->summary_fn, h->summary_work_fn, h->host, h->d_img, h->dev == nullptr, n_rec, B,
-                                     tterms, tt_rec_stride, tt_inst_stride, q, x, y, y_stride, work, work_bytes, o, stream);
+    return constraint_summary(h, n_rec, B, tterms, tt_rec_stride, tt_inst_stride, q, x, y, y_stride, work, work_bytes,
+                              {tol, abs_max, abs_max_at, last, rms, viol_max, viol_count, settled_at}, stream);
+}
+extern "C" int clik_qp_constraint_summary(const clik_qp* h, int64_t n_rec, int64_t B, const double* tterms,
+                                          int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
+                                          const double* y, int64_t y_stride, const double* tol, void* work,
+                                          int64_t work_bytes, double* abs_max, int32_t* abs_max_at, double* last, double* rms,
+                                          double* viol_max, int32_t* viol_count, int32_t* settled_at, void* stream)
+{
+    return constraint_summary(h, n_rec, B, tterms, tt_rec_stride, tt_inst_stride, q, x, y, y_stride, work, work_bytes,
+                              {tol, abs_max, abs_max_at, last, rms, viol_max, viol_count, settled_at}, stream);
 }
 
 static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
@@ -1524,32 +1607,32 @@ static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, i
     if (!h) return fail(CLIK_EINVAL, "null handle");
     CLIK_NEEDS_DEVICE_HANDLE(h);
     if (B < 0 || n_ticks < 0) return fail(CLIK_EINVAL, "negative size");
-    if (method != CLIK_INTEGRATE_EULER && method != CLIK_INTEGRATE_RK4) return fail(CLIK_EINVAL, "unknown integration method %d", method);
+    int stages = 1;
+    int rc = stages_of(method, &stages);
+    if (rc) return rc;
     if (B == 0 || n_ticks == 0) return CLIK_OK;
     const DevSkill& S = h->host;
     const bool has_static = pinv_shape_served(h);
-    if (S.d.n_x > 0) {
-        if (!x || !dx) return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required (clik_pinv_rollout_batch_x)");
-        if (!has_static)
-            return fail(CLIK_EUNSUPPORTED, "the rollout of a skill with virtual_var needs a shape-specialised kernel "
-                                           "(none attached for this skill)");
-    }
+    rc = virtual_var_check(S, x, dx, " (clik_pinv_rollout_batch_x)");
+    if (rc) return rc;
+    if (S.d.n_x > 0 && !has_static)
+        return fail(CLIK_EUNSUPPORTED, "the rollout of a skill with virtual_var needs a shape-specialised kernel "
+                                       "(none attached for this skill)");
     if (method == CLIK_INTEGRATE_RK4 && !has_static)
         return fail(CLIK_EUNSUPPORTED, "the Runge-Kutta rollout needs a shape-specialised kernel (none attached for this skill)");
     if (!has_static && skill_needs_static(S))
         return extern_needs_kernel("clik_pinv_rollout_batch");
     if (h->kernel < 0 && !h->jit_rollout) return no_kernel_for_wide_state(S, "clik_pinv_rollout_batch");
-    if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
-    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    rc = joint_args_check(S, q, y, dq);
+    if (rc) return rc;
     if (rec && !h->rec_rollout)
         return fail(CLIK_EUNSUPPORTED, "records and per-tick targets need a shape-specialised recording rollout (none "
                                        "attached for this skill: clik_pinv_attach_rec_kernel)");
-    const int stages = method == CLIK_INTEGRATE_RK4 ? 4 : 1;
-    double* d_tt = nullptr;
-    int rc = rollout_tterms(tts, S.d.n_tslots, n_ticks, stages, dt, (hipStream_t)stream, &d_tt);
+    TtBuffer tt;
+    rc = rollout_tterms(tts, S.d.n_tslots, n_ticks, stages, dt, (hipStream_t)stream, &tt);
     if (rc) return rc;
-    const clik::LaunchArgs la = {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->policy, x, dx, stages, nullptr,
-                                 rec};
+    double* const d_tt = tt.ptr;
+    const clik::LaunchArgs la = launch_args(h, x, dx, stages, nullptr, rec);
     hipError_t e = hipErrorNotSupported;
     if (rec) {
         if (h->val_rec_rollout && h->val_rollout && S.d.n_x == 0 &&
@@ -1557,7 +1640,6 @@ static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, i
             e = h->val_rec_rollout(&la, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, mode, (hipStream_t)stream);
         if (e == hipErrorNotSupported)
             e = h->rec_rollout(&la, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, mode, (hipStream_t)stream);
-        if (d_tt) (void)hipFreeAsync(d_tt, (hipStream_t)stream);
         if (e != hipSuccess) return hipfail(e, "pinv recording rollout launch");
         return CLIK_OK;
     }
@@ -1570,7 +1652,6 @@ static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, i
                                  (hipStream_t)stream)
                 : clik::pinv_launch_rollout(h->kernel, la, d_tt, n_ticks, dt, max_speed, (long long)B,
                                             q, y, dq, mode, (hipStream_t)stream);
-    if (d_tt) (void)hipFreeAsync(d_tt, (hipStream_t)stream);
     if (e != hipSuccess) return hipfail(e, "pinv_rollout_kernel launch");
     return CLIK_OK;
 }
@@ -1579,28 +1660,17 @@ static int pinv_rollout_common(const clik_pinv* h, int64_t B, int32_t n_ticks, i
 // clik_rollout_summary.hpp) --------------------------------------------------------------------------------------------
 // what both controllers check before anything else: sizes, the outputs, and where the tick times come from
 static int rollout_sum_checks(int64_t B, int32_t n_ticks, int32_t method, int n_tslots, const double* tterms,
-                              const double* times, const SummaryIo& o)
+                              const double* times, const SummaryIo& o, int* stages)
 {
     if (B < 0) return fail(CLIK_EINVAL, "negative size");
     if (n_ticks < 1) return fail(CLIK_EINVAL, "a summarising rollout needs at least one tick, got %d", n_ticks);
-    if (method != CLIK_INTEGRATE_EULER && method != CLIK_INTEGRATE_RK4) return fail(CLIK_EINVAL, "unknown integration method %d", method);
-    const int rc = summary_io_check(o);
+    int rc = stages_of(method, stages);
+    if (rc) return rc;
+    rc = summary_io_check(o);
     if (rc) return rc;
     if (tterms && times) return fail(CLIK_EINVAL, "tterms (host) and times (device) are alternatives: pass one");
     if (n_tslots > 0 && !tterms && !times)
         return fail(CLIK_EINVAL, "the skill has time slots: tterms (host) or times (device) required");
-    return CLIK_OK;
-}
-
-extern "C" int clik_pinv_attach_rollout_summary_kernel(clik_pinv* h, void* rollout_sum_fn)
-{
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    if (rollout_sum_fn) {
-        CLIK_NEEDS_DEVICE_HANDLE(h);
-        int rc = pinv_attach_checks(h, "summarising rollouts exist for skills a shape-specialised kernel serves");
-        if (rc) return rc;
-    }
-    h->rollsum_fn = (clik_rollsum_fn)rollout_sum_fn;
     return CLIK_OK;
 }
 
@@ -1616,7 +1686,8 @@ extern "C" int clik_pinv_rollout_batch_sum(const clik_pinv* h, int64_t B, int32_
     CLIK_NEEDS_DEVICE_HANDLE(h);
     const DevSkill& S = h->host;
     const SummaryIo o = {tol, abs_max, abs_max_at, last, rms, viol_max, viol_count, settled_at};
-    int rc = rollout_sum_checks(B, n_ticks, method, S.d.n_tslots, tterms, times, o);
+    int stages = 1;
+    int rc = rollout_sum_checks(B, n_ticks, method, S.d.n_tslots, tterms, times, o, &stages);
     if (rc) return rc;
     clik::RollRec rr;
     rc = roll_rec_of(B, S.d.n_y, y_per_tick, record_every, rec_q, rec_dq, rec_x, rec_dx, nullptr, rec_mode, &rr);
@@ -1625,23 +1696,21 @@ extern "C" int clik_pinv_rollout_batch_sum(const clik_pinv* h, int64_t B, int32_
     if (!h->rollsum_fn)
         return fail(CLIK_EUNSUPPORTED, "no summarising rollout instantiated for this skill "
                                        "(clik_pinv_attach_rollout_summary_kernel: skills of the shape-specialised family have one)");
-    if (S.d.n_x > 0 && (!x || !dx)) return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required");
+    rc = virtual_var_check(S, x, dx);
+    if (rc) return rc;
     // (as clik_pinv_rollout_batch_m: a skill whose rollouts are the built-in kernel's has no Runge-Kutta rollout, with or
     // without a summary)
     if (method == CLIK_INTEGRATE_RK4 && !pinv_shape_served(h))
         return fail(CLIK_EUNSUPPORTED, "the Runge-Kutta rollout needs a shape-specialised kernel (none attached for this skill)");
-    if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
-    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
-    const int stages = method == CLIK_INTEGRATE_RK4 ? 4 : 1;
-    double* d_tt = nullptr;
-    rc = rollout_tterms(times ? tt_device(times, h->time_fn) : tt_host(tterms), S.d.n_tslots, n_ticks, stages, dt,
-                        (hipStream_t)stream, &d_tt);
+    rc = joint_args_check(S, q, y, dq);
     if (rc) return rc;
-    const clik::LaunchArgs la = {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->policy, x, dx, stages, nullptr,
-                                 &rr};
-    const hipError_t e = h->rollsum_fn(&la, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, mode, (hipStream_t)stream,
+    TtBuffer tt;
+    rc = rollout_tterms(times ? tt_device(times, h->time_fn) : tt_host(tterms), S.d.n_tslots, n_ticks, stages, dt,
+                        (hipStream_t)stream, &tt);
+    if (rc) return rc;
+    const clik::LaunchArgs la = launch_args(h, x, dx, stages, nullptr, &rr);
+    const hipError_t e = h->rollsum_fn(&la, tt.ptr, n_ticks, dt, max_speed, (long long)B, q, y, dq, mode, (hipStream_t)stream,
                                        o.tol, o.abs_max, o.abs_max_at, o.last, o.rms, o.viol_max, o.viol_count, o.settled_at);
-    if (d_tt) (void)hipFreeAsync(d_tt, (hipStream_t)stream);
     if (e != hipSuccess) return hipfail(e, "pinv summarising rollout launch");
     return CLIK_OK;
 }
@@ -1659,18 +1728,6 @@ static int converge_checks(int64_t B, int32_t max_ticks, const double* tol, cons
     return CLIK_OK;
 }
 
-extern "C" int clik_pinv_attach_converge_kernel(clik_pinv* h, void* converge_fn)
-{
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    if (converge_fn) {
-        CLIK_NEEDS_DEVICE_HANDLE(h);
-        int rc = pinv_attach_checks(h, "converging rollouts exist for skills a shape-specialised kernel serves");
-        if (rc) return rc;
-    }
-    h->converge_fn = (clik_converge_fn)converge_fn;
-    return CLIK_OK;
-}
-
 extern "C" int clik_pinv_converge_batch(const clik_pinv* h, int64_t B, int32_t max_ticks, double dt, double max_speed,
                                         double min_step, const double* tterms, double* q, double* x, const double* y,
                                         double* dq, double* dx, int32_t* mode, const double* tol, int32_t* ticks,
@@ -1684,14 +1741,12 @@ extern "C" int clik_pinv_converge_batch(const clik_pinv* h, int64_t B, int32_t m
     if (!h->converge_fn)
         return fail(CLIK_EUNSUPPORTED, "no converging rollout instantiated for this skill "
                                        "(clik_pinv_attach_converge_kernel: skills of the shape-specialised family have one)");
-    if (S.d.n_x > 0 && (!x || !dx)) return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required");
-    if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
-    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    rc = state_args_check(S, q, x, y, dq, dx);
+    if (rc) return rc;
     TickArgs tk;
     rc = fill_tick(S, tterms, &tk);
     if (rc) return rc;
-    const clik::LaunchArgs la = {h->dev, h->d_img, &h->warm, S.d.n_q, S.d.n_x, S.d.n_y, h->policy, x, dx, 1, nullptr,
-                                 nullptr};
+    const clik::LaunchArgs la = launch_args(h, x, dx, 1, nullptr, nullptr);
     const hipError_t e = h->converge_fn(&la, &tk, (long long)B, max_ticks, dt, max_speed, min_step, q, y, dq, mode,
                                         (hipStream_t)stream, tol, ticks, stop_status, residual);
     if (e != hipSuccess) return hipfail(e, "pinv converging rollout launch");
@@ -1705,14 +1760,15 @@ static int qp_upload_image(clik_qp* h)
     std::vector<char> img;
     if (!build_qp_image(h->host, img))
         return fail(CLIK_EUNSUPPORTED, "skill rows are not contiguous: no static kernel possible");
-    hipError_t e = hipMalloc(&h->d_img, img.size());
-    if (e == hipSuccess) e = hipMemcpy(h->d_img, img.data(), img.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (h->d_img) (void)hipFree(h->d_img);
-        h->d_img = nullptr;
-        return hipfail(e, "QP skill image upload");
-    }
+    const hipError_t e = upload_image(h, img);
+    if (e != hipSuccess) return hipfail(e, "QP skill image upload");
     return CLIK_OK;
+}
+
+static int qp_attach_checks(clik_qp* h, const char* refusal)
+{
+    if (!qp_static_eligible(h->host)) return fail(CLIK_EUNSUPPORTED, "%s", refusal);
+    return qp_upload_image(h);
 }
 
 extern "C" int clik_qp_create(const clik_skill_desc* desc, const clik_qp_opts* opts, clik_qp** out)
@@ -1720,30 +1776,25 @@ extern "C" int clik_qp_create(const clik_skill_desc* desc, const clik_qp_opts* o
     if (!out) return fail(CLIK_EINVAL, "null out pointer");
     *out = nullptr;
     if (!opts) return fail(CLIK_EINVAL, "null options");
-    clik_qp* h = new (std::nothrow) clik_qp();
+    std::unique_ptr<clik_qp> h(new (std::nothrow) clik_qp());
     if (!h) return fail(CLIK_ENOMEM, "out of host memory");
-    h->gws = new (std::nothrow) clik::GwsOwner();
-    if (!h->gws) { delete h; return fail(CLIK_ENOMEM, "out of host memory"); }
-    int rc = validate_and_derive(desc, &h->host);
-    if (rc) { delete h; return rc; }
+    h->gws.reset(new (std::nothrow) clik::GwsOwner());
+    if (!h->gws) return fail(CLIK_ENOMEM, "out of host memory");
+    int used_rows = 0;
+    int rc = validate_and_derive(desc, &h->host, &used_rows);
+    if (rc) return rc;
     DevSkill& S = h->host;
     S.qo = *opts;
     if (S.qo.max_iter <= 0) S.qo.max_iter = 4 * (S.n_qp_rows + S.n_qp_vars) + 16;
     for (int k = 0; k < S.n_slack; ++k)
-        if (!(opts->weight_shifter + opts->slack_weights[k] > 0.0)) {
-            delete h;
+        if (!(opts->weight_shifter + opts->slack_weights[k] > 0.0))
             return fail(CLIK_EINVAL, "QP slack weight %d makes the cost non-convex", k);
-        }
-    if (S.n_qp_vars > CLIK_MAX_QPVARS || S.n_qp_rows > CLIK_MAX_QPROWS) {
-        delete h;
+    if (S.n_qp_vars > CLIK_MAX_QPVARS || S.n_qp_rows > CLIK_MAX_QPROWS)
         return fail(CLIK_EUNSUPPORTED, "QP with %d variables x %d rows exceeds the device limits (%d x %d)",
                     S.n_qp_vars, S.n_qp_rows, CLIK_MAX_QPVARS, CLIK_MAX_QPROWS);
-    }
     for (int j = 0; j < S.n; ++j)
-        if (!(opts->weight_shifter * opts->state_weights[j] > 0.0)) {
-            delete h;
+        if (!(opts->weight_shifter * opts->state_weights[j] > 0.0))
             return fail(CLIK_EINVAL, "QP cost weight %d is not positive", j);
-        }
     {
         int need = S.n;
         for (int ti = 0; ti < S.d.n_tasks; ++ti)
@@ -1761,7 +1812,6 @@ extern "C" int clik_qp_create(const clik_skill_desc* desc, const clik_qp_opts* o
         const bool dyn_lds = dyn_rows && clik::qp_variant_lds(h->variant, S.d.n_y) <= clik::kLdsBytesPerCu;
         if (!dyn_lds) {
             if (!eligible) {
-                delete h;
                 if (!dyn_rows)
                     return fail(CLIK_EUNSUPPORTED,
                                 "no QP kernel variant for %d variables x %d rows (device limit: %d rows)",
@@ -1771,41 +1821,28 @@ extern "C" int clik_qp_create(const clik_skill_desc* desc, const clik_qp_opts* o
             h->variant = -1;
         }
     }
-    compute_warm(S, S.lds_slots, h->warm);
-    S.zero_token = 0;
-    S.lds_slots = 0;
-    h->d_img = nullptr;
-    h->jit_solve = nullptr;
-    h->jit_rollout = nullptr;
-    h->val_resident = nullptr;
-    h->jit_name[0] = 0;
-    h->dev = nullptr;
+    compute_warm(S, used_rows, h->warm);
+    S.lds_slots = 0;        // (the QP kernels size their LDS themselves)
     {
         // the switches of the kernel choice (qp_select, clik_qp_select.hpp): CLIK_FORCE_DYNAMIC=1 / CLIK_NO_AOT=1 skip
         // the AOT table (the Python layer may still attach a run-time instantiated kernel)
         const char* force = getenv("CLIK_FORCE_DYNAMIC");
         const char* noaot = getenv("CLIK_NO_AOT");
         h->policy.aot = !((force && force[0] == '1') || (noaot && noaot[0] == '1'));
-        h->policy.values_attached = false;
         h->policy.folio = clik::qp_env().folio;
-        h->policy.cus = 0;
     }
     // shape-specialised kernel from the AOT table (a host-only handle picks it too, and uploads nothing)
     h->static_k = (h->policy.aot && eligible) ? clik::qp_pick_static(S.shape) : -1;
-    if (host_only_mode()) {
-        *out = h;
-        return CLIK_OK;
+    rc = upload_skill(h.get());
+    if (rc) return rc;
+    if (h->dev) {
+        if (h->static_k >= 0) {
+            rc = qp_upload_image(h.get());
+            if (rc) return rc;
+        }
+        h->policy.cus = clik::current_device_cus();
     }
-    hipError_t e = hipMalloc((void**)&h->dev, sizeof(DevSkill));
-    if (e != hipSuccess) { delete h; return hipfail(e, "hipMalloc(skill)"); }
-    e = hipMemcpy(h->dev, &S, sizeof(DevSkill), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(h->dev); delete h; return hipfail(e, "hipMemcpy(skill)"); }
-    if (h->static_k >= 0) {
-        int rc2 = qp_upload_image(h);
-        if (rc2) { (void)hipFree(h->dev); delete h; return rc2; }
-    }
-    h->policy.cus = clik::current_device_cus();
-    *out = h;
+    *out = h.release();
     return CLIK_OK;
 }
 
@@ -1836,14 +1873,13 @@ static bool qp_shape_served(const clik_qp* h)
 extern "C" int clik_qp_shape_describe(const clik_skill_desc* desc, char* buf, int cap)
 {
     if (!buf || cap <= 0) return fail(CLIK_EINVAL, "bad arguments");
-    DevSkill* S = new (std::nothrow) DevSkill();
+    std::unique_ptr<DevSkill> S(new (std::nothrow) DevSkill());
     if (!S) return fail(CLIK_ENOMEM, "out of host memory");
-    int rc = validate_and_derive(desc, S);
-    if (rc) { delete S; return rc; }
+    int rc = validate_and_derive(desc, S.get());
+    if (rc) return rc;
     finish_qp_shape(*S);
     const std::string o = shape_to_string(S->shape);
     const bool eligible = qp_static_eligible(*S);
-    delete S;
     if ((int)o.size() + 1 > cap) return fail(CLIK_EINVAL, "buffer too small");
     memcpy(buf, o.c_str(), o.size() + 1);
     return eligible ? 1 : 0;
@@ -1912,21 +1948,6 @@ extern "C" int clik_qp_rollout_batch_rec(const clik_qp* hc, int64_t B, int32_t n
                              &rr);
 }
 
-extern "C" int clik_qp_attach_time_kernel(clik_qp* h, void* time_terms_fn)
-{
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    h->time_fn = (clik_time_fn)time_terms_fn;
-    return CLIK_OK;
-}
-
-extern "C" int clik_qp_time_terms(const clik_qp* h, int64_t n_times, const double* times, int32_t stages, double dt,
-                                  double* out, void* stream)
-{
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    CLIK_NEEDS_DEVICE_HANDLE(h);
-    return time_terms_common(h->time_fn, h->host.d.n_tslots, n_times, times, stages, dt, out, stream);
-}
-
 extern "C" int clik_qp_rollout_batch_dev(const clik_qp* hc, int64_t B, int32_t n_ticks, int32_t method, double dt,
                                          double max_speed, const double* times, double* q, double* x, const double* y,
                                          double* dq, double* dx, double* slack, int32_t* status, void* stream,
@@ -1944,116 +1965,39 @@ extern "C" int clik_qp_rollout_batch_dev(const clik_qp* hc, int64_t B, int32_t n
     return qp_rollout_common(hc, B, n_ticks, method, dt, max_speed, tts, q, x, y, dq, dx, slack, status, stream, &rr);
 }
 
-// what the four clik_qp_attach_*_kernel of the on-demand kernels check before they store a pointer: the skill is in the
-// shape-specialised family, and its image is on the device (uploaded here when no kernel of that family runs yet)
-static int qp_attach_checks(clik_qp* h)
-{
-    if (!qp_static_eligible(h->host)) return fail(CLIK_EUNSUPPORTED, "skill is outside the shape-specialised QP family");
-    return qp_upload_image(h);
-}
-
-extern "C" int clik_qp_attach_rec_kernel(clik_qp* h, void* rollout_rec_fn, void* value_rollout_rec_fn)
-{
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    CLIK_NEEDS_DEVICE_HANDLE(h);        // (also when detaching, unlike the other three)
-    if (rollout_rec_fn) {
-        int rc = qp_attach_checks(h);
-        if (rc) return rc;
-    }
-    h->rec_rollout = (clik_qp_rec_fn)rollout_rec_fn;
-    // (the value-specialised rollout exists for the box family only)
-    h->val_rec_rollout = CLIK_QP_BOX_OK(h->host.shape) ? (clik_qp_value_rec_fn)value_rollout_rec_fn : nullptr;
-    return CLIK_OK;
-}
-
-extern "C" int clik_qp_attach_monitor_kernel(clik_qp* h, void* constraint_values_fn)
-{
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    if (constraint_values_fn) {
-        CLIK_NEEDS_DEVICE_HANDLE(h);
-        int rc = qp_attach_checks(h);
-        if (rc) return rc;
-    }
-    h->monitor_fn = (clik_monitor_fn)constraint_values_fn;
-    return CLIK_OK;
-}
-
-extern "C" int clik_qp_n_constraint_rows(const clik_qp* h) { return h ? n_constraint_rows(h->host) : 0; }
-
-extern "C" int clik_qp_constraint_values(const clik_qp* h, int64_t n_rec, int64_t B, const double* tterms,
-                                         int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
-                                         const double* y, int64_t y_stride, double* e, double* J, double* et, void* stream)
-{
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    return constraint_values_common(h->monitor_fn, h->host, h->d_img, h->dev == nullptr, n_rec, B, tterms, tt_rec_stride,
-                                    tt_inst_stride, q, x, y, y_stride, e, J, et, stream);
-}
-
-extern "C" int clik_qp_attach_summary_kernel(clik_qp* h, void* constraint_summary_fn, void* work_bytes_fn)
-{
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    if (constraint_summary_fn) {
-        CLIK_NEEDS_DEVICE_HANDLE(h);
-        if (!work_bytes_fn) return fail(CLIK_EINVAL, "the summary kernel comes with its work-size function");
-        int rc = qp_attach_checks(h);
-        if (rc) return rc;
-    }
-    h->summary_fn = (clik_summary_fn)constraint_summary_fn;
-    h->summary_work_fn = constraint_summary_fn ? (clik_summary_work_fn)work_bytes_fn : nullptr;
-    return CLIK_OK;
-}
-
-extern "C" int64_t clik_qp_summary_work_bytes(const clik_qp* h, int64_t n_rec, int64_t B)
-{
-    return h ? summary_work_bytes_common(h->summary_work_fn, n_rec, B) : 0;
-}
-
-extern "C" int clik_qp_constraint_summary(const clik_qp* h, int64_t n_rec, int64_t B, const double* tterms,
-                                          int64_t tt_rec_stride, int64_t tt_inst_stride, const double* q, const double* x,
-                                          const double* y, int64_t y_stride, const double* tol, void* work,
-                                          int64_t work_bytes, double* abs_max, int32_t* abs_max_at, double* last, double* rms,
-                                          double* viol_max, int32_t* viol_count, int32_t* settled_at, void* stream)
-{
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    const SummaryIo o = {tol, abs_max, abs_max_at, last, rms, viol_max, viol_count, settled_at};
-    return constraint_summary_common(h->summary_fn, h->summary_work_fn, h->host, h->d_img, h->dev == nullptr, n_rec, B,
-                                     tterms, tt_rec_stride, tt_inst_stride, q, x, y, y_stride, work, work_bytes, o, stream);
-}
-
-static int qp_rollout_common(const clik_qp* hc, int64_t B, int32_t n_ticks, int32_t method, double dt,
+static int qp_rollout_common(const clik_qp* h, int64_t B, int32_t n_ticks, int32_t method, double dt,
                              double max_speed, const TtSource& tts, double* q, double* x, const double* y,
                              double* dq, double* dx, double* slack, int32_t* status, void* stream,
                              const clik::RollRec* rec)
 {
-    const clik_qp* h = hc;
-    if (method != CLIK_INTEGRATE_EULER && method != CLIK_INTEGRATE_RK4)
-        return fail(CLIK_EINVAL, "clik_qp_rollout_batch_m: unknown integration method %d", method);
-    const int stages = method == CLIK_INTEGRATE_RK4 ? 4 : 1;
+    int stages = 1;
+    int rc = stages_of(method, &stages, "clik_qp_rollout_batch_m: ");
+    if (rc) return rc;
     if (!h) return fail(CLIK_EINVAL, "null handle");
     CLIK_NEEDS_DEVICE_HANDLE(h);
     if (B < 0 || n_ticks < 0) return fail(CLIK_EINVAL, "negative size");
     if (B == 0 || n_ticks == 0) return CLIK_OK;
     const DevSkill& S = h->host;
-    if (S.d.n_x > 0 && (!x || !dx))
-        return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required (clik_qp_rollout_batch_x)");
+    rc = virtual_var_check(S, x, dx, " (clik_qp_rollout_batch_x)");
+    if (rc) return rc;
     const clik::QpKernel k = clik::qp_select(S.shape, h->policy, qp_kernels(h), (long long)B, false, clik::QpOp::rollout);
     if (k == clik::QpKernel::none)
         return fail(CLIK_EUNSUPPORTED, "the QP rollout needs a shape-specialised kernel (none attached for this skill)");
-    if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
-    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    rc = joint_args_check(S, q, y, dq);
+    if (rc) return rc;
     if (rec && !h->rec_rollout)
         return fail(CLIK_EUNSUPPORTED, "records and per-tick targets need a shape-specialised recording rollout (none "
                                        "attached for this skill: clik_qp_attach_rec_kernel)");
-    double* d_tt = nullptr;
-    int rc = rollout_tterms(tts, S.d.n_tslots, n_ticks, stages, dt, (hipStream_t)stream, &d_tt);
+    TtBuffer tt;
+    rc = rollout_tterms(tts, S.d.n_tslots, n_ticks, stages, dt, (hipStream_t)stream, &tt);
     if (rc) return rc;
+    double* const d_tt = tt.ptr;
     if (rec) {
         hipError_t er = (k == clik::QpKernel::value && h->val_rec_rollout)
                             ? h->val_rec_rollout(d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, slack, status, x, dx,
                                                  (hipStream_t)stream, stages, rec)
                             : h->rec_rollout(h->d_img, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, slack, status,
                                              x, dx, (hipStream_t)stream, stages, rec);
-        if (d_tt) (void)hipFreeAsync(d_tt, (hipStream_t)stream);
         if (er != hipSuccess) return hipfail(er, "qp recording rollout launch");
         return CLIK_OK;
     }
@@ -2066,20 +2010,7 @@ static int qp_rollout_common(const clik_qp* hc, int64_t B, int32_t n_ticks, int3
                        : clik::qp_launch_rollout_static(h->static_k, h->d_img, d_tt, n_ticks, dt, max_speed,
                                                         (long long)B, q, y, dq, slack, status, x, dx,
                                                         (hipStream_t)stream, stages);
-    if (d_tt) (void)hipFreeAsync(d_tt, (hipStream_t)stream);
     if (e != hipSuccess) return hipfail(e, "qp_rollout_kernel launch");
-    return CLIK_OK;
-}
-
-extern "C" int clik_qp_attach_rollout_summary_kernel(clik_qp* h, void* rollout_sum_fn)
-{
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    if (rollout_sum_fn) {
-        CLIK_NEEDS_DEVICE_HANDLE(h);
-        int rc = qp_attach_checks(h);
-        if (rc) return rc;
-    }
-    h->rollsum_fn = (clik_qp_rollsum_fn)rollout_sum_fn;
     return CLIK_OK;
 }
 
@@ -2096,7 +2027,8 @@ extern "C" int clik_qp_rollout_batch_sum(const clik_qp* h, int64_t B, int32_t n_
     CLIK_NEEDS_DEVICE_HANDLE(h);
     const DevSkill& S = h->host;
     const SummaryIo o = {tol, abs_max, abs_max_at, last, rms, viol_max, viol_count, settled_at};
-    int rc = rollout_sum_checks(B, n_ticks, method, S.d.n_tslots, tterms, times, o);
+    int stages = 1;
+    int rc = rollout_sum_checks(B, n_ticks, method, S.d.n_tslots, tterms, times, o, &stages);
     if (rc) return rc;
     clik::RollRec rr;
     rc = roll_rec_of(B, S.d.n_y, y_per_tick, record_every, rec_q, rec_dq, rec_x, rec_dx, rec_slack, rec_status, &rr);
@@ -2105,31 +2037,16 @@ extern "C" int clik_qp_rollout_batch_sum(const clik_qp* h, int64_t B, int32_t n_
     if (!h->rollsum_fn || !h->d_img)
         return fail(CLIK_EUNSUPPORTED, "no summarising rollout instantiated for this skill "
                                        "(clik_qp_attach_rollout_summary_kernel: skills of the shape-specialised family have one)");
-    if (S.d.n_x > 0 && (!x || !dx)) return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required");
-    if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
-    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
-    const int stages = method == CLIK_INTEGRATE_RK4 ? 4 : 1;
-    double* d_tt = nullptr;
-    rc = rollout_tterms(times ? tt_device(times, h->time_fn) : tt_host(tterms), S.d.n_tslots, n_ticks, stages, dt,
-                        (hipStream_t)stream, &d_tt);
+    rc = state_args_check(S, q, x, y, dq, dx);
     if (rc) return rc;
-    const hipError_t e = h->rollsum_fn(h->d_img, d_tt, n_ticks, dt, max_speed, (long long)B, q, y, dq, slack, status, x, dx,
+    TtBuffer tt;
+    rc = rollout_tterms(times ? tt_device(times, h->time_fn) : tt_host(tterms), S.d.n_tslots, n_ticks, stages, dt,
+                        (hipStream_t)stream, &tt);
+    if (rc) return rc;
+    const hipError_t e = h->rollsum_fn(h->d_img, tt.ptr, n_ticks, dt, max_speed, (long long)B, q, y, dq, slack, status, x, dx,
                                        (hipStream_t)stream, stages, &rr, o.tol, o.abs_max, o.abs_max_at, o.last, o.rms,
                                        o.viol_max, o.viol_count, o.settled_at);
-    if (d_tt) (void)hipFreeAsync(d_tt, (hipStream_t)stream);
     if (e != hipSuccess) return hipfail(e, "qp summarising rollout launch");
-    return CLIK_OK;
-}
-
-extern "C" int clik_qp_attach_converge_kernel(clik_qp* h, void* converge_fn)
-{
-    if (!h) return fail(CLIK_EINVAL, "null handle");
-    if (converge_fn) {
-        CLIK_NEEDS_DEVICE_HANDLE(h);
-        int rc = qp_attach_checks(h);
-        if (rc) return rc;
-    }
-    h->converge_fn = (clik_qp_converge_fn)converge_fn;
     return CLIK_OK;
 }
 
@@ -2146,9 +2063,8 @@ extern "C" int clik_qp_converge_batch(const clik_qp* h, int64_t B, int32_t max_t
     if (!h->converge_fn || !h->d_img)
         return fail(CLIK_EUNSUPPORTED, "no converging rollout instantiated for this skill "
                                        "(clik_qp_attach_converge_kernel: skills of the shape-specialised family have one)");
-    if (S.d.n_x > 0 && (!x || !dx)) return fail(CLIK_EINVAL, "skill has virtual_var: x and dx required");
-    if (!q || !dq) return fail(CLIK_EINVAL, "q and dq must be device pointers");
-    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
+    rc = state_args_check(S, q, x, y, dq, dx);
+    if (rc) return rc;
     TickArgs tk;
     rc = fill_tick(S, tterms, &tk);
     if (rc) return rc;
@@ -2220,16 +2136,11 @@ extern "C" int clik_qp_resident_run(const clik_qp* h, int64_t B, int32_t n_ticks
 {
     if (!h) return fail(CLIK_EINVAL, "null handle");
     CLIK_NEEDS_DEVICE_HANDLE(h);
-    if (!h->val_resident)
-        return fail(CLIK_EUNSUPPORTED, "resident QP ticks need the value-specialised kernel of a bound-constrained skill "
-                                       "attached to this handle (none is)");
-    if (B <= 0 || n_ticks <= 0) return fail(CLIK_EINVAL, "B and n_ticks must be positive");
-    if (!q || !dq || !ticket || !done) return fail(CLIK_EINVAL, "q, dq, ticket and done must be device pointers");
-    const DevSkill& S = h->host;
-    if (S.d.n_y > 0 && !y) return fail(CLIK_EINVAL, "skill has input_var: y required");
-    if (!(timeout_s > 0.0) || timeout_s > 60.0) return fail(CLIK_EINVAL, "timeout_s must lie in (0, 60]");
     TickArgs tk;
-    int rc = fill_tick(S, tterms, &tk);
+    const int rc = resident_checks(h, h->val_resident != nullptr,
+                                   "resident QP ticks need the value-specialised kernel of a bound-constrained skill "
+                                   "attached to this handle (none is)",
+                                   B, n_ticks, tterms, q, y, dq, ticket, done, timeout_s, &tk);
     if (rc) return rc;
     const unsigned long long budget = (unsigned long long)(timeout_s * 5e6);       // (polls, at a nominal 0.2 us each)
     hipError_t e = h->val_resident(&tk, (long long)B, q, y, dq, slack, status, (void*)ticket, (unsigned*)done, n_ticks,
@@ -2258,10 +2169,7 @@ extern "C" const char* clik_qp_kernel_variant(const clik_qp* h, int64_t B, int32
 
 extern "C" int clik_qp_destroy(clik_qp* h)
 {
-    if (!h) return CLIK_OK;
-    if (h->d_img) (void)hipFree(h->d_img);
-    if (h->dev) (void)hipFree(h->dev);
-    delete h;           // (~clik_qp releases the work area of the global-workspace kernels)
+    delete h;       // (... and the work area of the global-workspace kernels)
     return CLIK_OK;
 }
 
@@ -2331,7 +2239,7 @@ static int qp_solve_common(const clik_qp* h, int64_t B, const double* tterms, co
                                            "owned by the handle and ordered per stream - hipStreamPerThread is not supported "
                                            "for it (pass an explicit stream)");
         e = clik::qp_launch_solve(h->variant, h->dev, h->warm, tk, (long long)B, h->host.d.n_y, q, x, y, dq, dx,
-                                  slack, status, (hipStream_t)stream, h->gws);
+                                  slack, status, (hipStream_t)stream, h->gws.get());
         if (e == hipErrorStreamCaptureUnsupported)
             return fail(CLIK_EHIP, "qp_solve_kernel launch: the work area of this skill's kernel must grow for this batch "
                                    "size, which cannot be captured - run one tick of this batch size before capturing");
@@ -2383,7 +2291,7 @@ extern "C" int clik_qp_data_batch(const clik_qp* h, int64_t B, const double* tte
         return fail(CLIK_EUNSUPPORTED, "clik_qp_data_batch: hipStreamPerThread is not supported for skills whose kernel keeps its "
                                        "work area in global memory (pass an explicit stream)");
     hipError_t e = clik::qp_launch_data(h->variant, h->dev, h->warm, tk, (long long)B, h->host.d.n_y, q, x, y, Hdiag, A,
-                                        lbA, ubA, (hipStream_t)stream, h->gws);
+                                        lbA, ubA, (hipStream_t)stream, h->gws.get());
     if (e != hipSuccess) return hipfail(e, "qp_data_kernel launch");
     return CLIK_OK;
 }

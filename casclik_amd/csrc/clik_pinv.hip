@@ -3,6 +3,7 @@
 // kernels (clik_pinv_dyn.hip).
 #define CLIK_LARGE_BATCH_VARIANT 1      // the ahead-of-time shapes also get the large-batch (occupancy 2) kernel
 #include "clik_pinv_kernels.hpp"
+#include "clik_launch.hpp"      // (what clik_api.hip calls here: declarations held against the definitions below)
 
 namespace clik {
 

@@ -1,6 +1,7 @@
 // Batched ReactiveQPController tick on gfx950, dynamic-shape kernels: the variant table and its look-up.  The kernels
 // and their launch templates are clik_qp_dyn.hpp; their instantiations compile in clik_qp_dyn_[a-d].hip.
 #include "clik_qp_dyn.hpp"
+#include "clik_launch.hpp"      // (what clik_api.hip calls here: declarations held against the definitions below)
 
 namespace clik {
 

@@ -3,6 +3,7 @@
 // Its own translation unit: it compiles beside clik_qp.hip (the dynamic-shape kernels) instead of behind it - together
 // they were one 13-minute compile.
 #include "clik_qp_static.hpp"
+#include "clik_launch.hpp"      // (what clik_api.hip calls here: declarations held against the definitions below)
 
 namespace clik {
 
