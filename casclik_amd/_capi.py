@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -173,32 +174,80 @@ def qp_opts_to_c(mu, state_weights, slack_weights, max_iter=0):
     return o
 
 
-_SYMBOLS = [
-    "clik_last_error", "clik_abi_version",
-    "clik_pinv_create", "clik_pinv_create_host", "clik_pinv_destroy", "clik_pinv_n_modes", "clik_pinv_kernel_name", "clik_pinv_kernel_variant", "clik_pinv_image_words", "clik_pinv_attach_value_kernel", "clik_pinv_attach_resident_kernel", "clik_pinv_resident_waves", "clik_pinv_resident_run", "clik_pinv_resident_run_state", "clik_ticket_feed", "clik_shape_describe", "clik_pinv_attach_kernel",
-    "clik_pinv_solve_batch", "clik_pinv_solve_batch_t", "clik_pinv_rollout_batch", "clik_pinv_rollout_batch_x", "clik_pinv_rollout_batch_m",
-    "clik_pinv_attach_rec_kernel", "clik_pinv_rollout_batch_rec", "clik_qp_attach_rec_kernel", "clik_qp_rollout_batch_rec",
-    "clik_pinv_attach_time_kernel", "clik_pinv_time_terms", "clik_pinv_rollout_batch_dev",
-    "clik_qp_attach_time_kernel", "clik_qp_time_terms", "clik_qp_rollout_batch_dev",
-    "clik_pinv_attach_monitor_kernel", "clik_pinv_constraint_values", "clik_pinv_n_constraint_rows",
-    "clik_qp_attach_monitor_kernel", "clik_qp_constraint_values", "clik_qp_n_constraint_rows",
-    "clik_summary_chunk_length",
-    "clik_pinv_attach_summary_kernel", "clik_pinv_summary_work_bytes", "clik_pinv_constraint_summary",
-    "clik_qp_attach_summary_kernel", "clik_qp_summary_work_bytes", "clik_qp_constraint_summary",
-    "clik_pinv_attach_rollout_summary_kernel", "clik_pinv_rollout_batch_sum",
-    "clik_qp_attach_rollout_summary_kernel", "clik_qp_rollout_batch_sum",
-    "clik_pinv_attach_converge_kernel", "clik_pinv_converge_batch", "clik_qp_attach_converge_kernel", "clik_qp_converge_batch",
-    "clik_qp_create", "clik_qp_create_host", "clik_qp_destroy", "clik_qp_n_vars", "clik_qp_n_rows", "clik_qp_workspace_bytes",
-    "clik_qp_kernel_name", "clik_qp_kernel_variant", "clik_qp_shape_describe", "clik_qp_attach_kernel", "clik_qp_image_words", "clik_qp_attach_value_kernel", "clik_qp_is_box_family",
-    "clik_qp_attach_resident_kernel", "clik_qp_resident_waves", "clik_qp_resident_run",
-    "clik_qp_solve_batch", "clik_qp_solve_batch_hot", "clik_qp_solve_batch_t", "clik_qp_rollout_batch", "clik_qp_rollout_batch_x", "clik_qp_rollout_batch_m", "clik_qp_data_batch",
-]
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "clik.h")
+
+# Every type the header's prototypes spell.  The three structures ctypes can check are typed pointers; handles, handle
+# outputs, tickets and buffers travel as plain addresses.
+_CTYPES = {
+    "int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double,
+    "const char*": C.c_char_p, "char*": C.c_char_p,
+    "const clik_skill_desc*": C.POINTER(clik_skill_desc),
+    "const clik_pinv_opts*": C.POINTER(clik_pinv_opts),
+    "const clik_qp_opts*": C.POINTER(clik_qp_opts),
+}
+_CTYPES.update(dict.fromkeys((
+    "clik_pinv*", "const clik_pinv*", "clik_pinv**", "clik_qp*", "const clik_qp*", "clik_qp**", "clik_ticket*",
+    "double*", "const double*", "int32_t*", "uint32_t*", "const uint32_t*", "uint64_t*", "void*"), C.c_void_p))
+
+
+def _spelling(text):
+    """a type as ``_CTYPES`` spells it: single spaces, none around a ``*``"""
+    return re.sub(r"\s*\*\s*", "*", " ".join(text.split()))
+
+
+def parse_prototypes(text):
+    """``[(name, return type, [parameter types])]`` of every function ``clik_*`` that the C header ``text`` declares, in
+    its order, the types as ``_spelling`` writes them.  Comments and preprocessor lines are dropped, a prototype may run
+    over several lines, ``(void)`` is an empty list.  ClikLibraryError for a ``clik_*(`` that does not read as a
+    prototype: nothing is skipped."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", " ", text, flags=re.M)
+    out = []
+    for stmt in re.split(r"[;{}]", text):
+        if not re.search(r"\bclik_\w+\s*\(", stmt):
+            continue
+        m = re.fullmatch(r"\s*([\w\s*]+?)\s*\b(clik_\w+)\s*\(([^()]*)\)\s*", stmt)
+        if m is None:
+            raise ClikLibraryError("cannot read the declaration %r" % " ".join(stmt.split()))
+        params = []
+        if m.group(3).strip() not in ("", "void"):
+            for p in m.group(3).split(","):
+                named = re.fullmatch(r"(.*[\s*])\w+", p.strip(), flags=re.S)      # (the type, then the parameter's name)
+                params.append(_spelling(named.group(1) if named else p))
+        out.append((m.group(2), _spelling(m.group(1)), params))
+    return out
+
+
+def prototype_ctypes(name, ret, params):
+    """``(restype, argtypes)`` of one parsed prototype; ClikLibraryError for a type outside ``_CTYPES``"""
+    def one(spelling):
+        if spelling not in _CTYPES:
+            raise ClikLibraryError("%s: the type %r has no ctypes mapping in _capi._CTYPES" % (name, spelling))
+        return _CTYPES[spelling]
+    return one(ret), [one(p) for p in params]
+
+
+_prototypes = None
+
+
+def header_prototypes():
+    """``parse_prototypes`` of include/clik.h, read once"""
+    global _prototypes
+    if _prototypes is None:
+        try:
+            with open(HEADER_PATH, "r") as f:
+                _prototypes = parse_prototypes(f.read())
+        except OSError as exc:
+            raise ClikLibraryError("cannot read %s: %s" % (HEADER_PATH, exc))
+    return _prototypes
+
 
 _lib = None
 
 
 def exported_symbols():
-    return list(_SYMBOLS)
+    """the names of the entry points include/clik.h declares"""
+    return [name for name, _, _ in header_prototypes()]
 
 
 def _preload_hip_runtime():
@@ -224,7 +273,7 @@ def _preload_hip_runtime():
 
 
 def load_library(path=None):
-    """Load libclik_hip.so (once) and declare the prototypes."""
+    """Load libclik_hip.so (once) and declare every prototype of include/clik.h on it."""
     global _lib
     if _lib is not None and path is None:
         return _lib
@@ -239,173 +288,11 @@ def load_library(path=None):
         lib = C.CDLL(p)
     except OSError as exc:
         raise ClikLibraryError("cannot load %s: %s" % (p, exc))
-    vp, dp, ip = C.c_void_p, C.c_void_p, C.c_void_p
-    lib.clik_last_error.restype = C.c_char_p
-    lib.clik_last_error.argtypes = []
-    lib.clik_abi_version.restype = C.c_int32
-    lib.clik_abi_version.argtypes = []
-    lib.clik_pinv_create.restype = C.c_int
-    lib.clik_pinv_create.argtypes = [C.POINTER(clik_skill_desc),
-                                     C.POINTER(clik_pinv_opts),
-                                     C.POINTER(C.c_void_p)]
-    lib.clik_pinv_create_host.restype = C.c_int
-    lib.clik_pinv_create_host.argtypes = lib.clik_pinv_create.argtypes
-    lib.clik_pinv_destroy.restype = C.c_int
-    lib.clik_pinv_destroy.argtypes = [vp]
-    lib.clik_pinv_n_modes.restype = C.c_int
-    lib.clik_pinv_n_modes.argtypes = [vp]
-    lib.clik_pinv_kernel_name.restype = C.c_char_p
-    lib.clik_pinv_kernel_name.argtypes = [vp]
-    lib.clik_pinv_image_words.restype = C.c_int
-    lib.clik_pinv_image_words.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
-    lib.clik_pinv_attach_value_kernel.restype = C.c_int
-    lib.clik_pinv_attach_value_kernel.argtypes = [vp, C.c_void_p, C.c_void_p]
-    lib.clik_pinv_attach_resident_kernel.restype = C.c_int
-    lib.clik_pinv_attach_resident_kernel.argtypes = [vp, C.c_void_p]
-    lib.clik_pinv_resident_waves.restype = C.c_int
-    lib.clik_pinv_resident_waves.argtypes = [vp, C.c_int64]
-    lib.clik_qp_attach_resident_kernel.restype = C.c_int
-    lib.clik_qp_attach_resident_kernel.argtypes = [vp, C.c_void_p]
-    lib.clik_qp_resident_waves.restype = C.c_int
-    lib.clik_qp_resident_waves.argtypes = [vp, C.c_int64]
-    lib.clik_qp_resident_run.restype = C.c_int
-    lib.clik_qp_resident_run.argtypes = [vp, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, ip, C.c_void_p, C.c_void_p,
-                                         C.c_double, C.c_void_p]
-    lib.clik_pinv_resident_run_state.restype = C.c_int
-    lib.clik_pinv_resident_run_state.argtypes = [vp, C.c_int64, C.c_int32, dp, dp, dp, dp, ip, C.c_void_p, C.c_void_p,
-                                                 C.c_double, C.c_double, C.c_double, C.c_void_p]
-    lib.clik_pinv_resident_run.restype = C.c_int
-    lib.clik_pinv_resident_run.argtypes = [vp, C.c_int64, C.c_int32, dp, dp, dp, dp, ip, C.c_void_p, C.c_void_p,
-                                           C.c_double, C.c_void_p]
-    lib.clik_ticket_feed.restype = C.c_int
-    lib.clik_ticket_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p]
-    lib.clik_pinv_kernel_variant.restype = C.c_char_p
-    lib.clik_pinv_kernel_variant.argtypes = [vp, C.c_int64]
-    lib.clik_pinv_attach_kernel.restype = C.c_int
-    lib.clik_pinv_attach_kernel.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_char_p]
-    lib.clik_shape_describe.restype = C.c_int
-    lib.clik_shape_describe.argtypes = [C.POINTER(clik_skill_desc), C.POINTER(clik_pinv_opts),
-                                        C.c_char_p, C.c_int]
-    lib.clik_pinv_solve_batch.restype = C.c_int
-    lib.clik_pinv_solve_batch.argtypes = [vp, C.c_int64, C.POINTER(C.c_double),
-                                          dp, dp, dp, dp, dp, ip, vp]
-    lib.clik_pinv_solve_batch_t.restype = C.c_int
-    lib.clik_pinv_solve_batch_t.argtypes = [vp, C.c_int64, dp, dp, dp, dp, dp, dp, ip, vp]
-    lib.clik_pinv_rollout_batch.restype = C.c_int
-    lib.clik_pinv_rollout_batch.argtypes = [vp, C.c_int64, C.c_int32,
-                                            C.c_double, C.c_double,
-                                            C.POINTER(C.c_double),
-                                            dp, dp, dp, ip, vp]
-    lib.clik_pinv_rollout_batch_m.restype = C.c_int
-    lib.clik_pinv_rollout_batch_m.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double,
-                                              C.POINTER(C.c_double), dp, dp, dp, dp, dp, ip, vp]
-    lib.clik_pinv_rollout_batch_x.restype = C.c_int
-    lib.clik_pinv_rollout_batch_x.argtypes = [vp, C.c_int64, C.c_int32, C.c_double, C.c_double,
-                                              C.POINTER(C.c_double), dp, dp, dp, dp, dp, ip, vp]
-    lib.clik_pinv_attach_rec_kernel.restype = C.c_int
-    lib.clik_pinv_attach_rec_kernel.argtypes = [vp, C.c_void_p, C.c_void_p]
-    lib.clik_pinv_rollout_batch_rec.restype = C.c_int
-    lib.clik_pinv_rollout_batch_rec.argtypes = lib.clik_pinv_rollout_batch_m.argtypes + [C.c_int32, C.c_int32, dp, dp, dp,
-                                                                                         dp, ip]
-    lib.clik_qp_create.restype = C.c_int
-    lib.clik_qp_create.argtypes = [C.POINTER(clik_skill_desc),
-                                   C.POINTER(clik_qp_opts),
-                                   C.POINTER(C.c_void_p)]
-    lib.clik_qp_create_host.restype = C.c_int
-    lib.clik_qp_create_host.argtypes = lib.clik_qp_create.argtypes
-    lib.clik_qp_destroy.restype = C.c_int
-    lib.clik_qp_destroy.argtypes = [vp]
-    lib.clik_qp_kernel_name.restype = C.c_char_p
-    lib.clik_qp_kernel_name.argtypes = [vp]
-    lib.clik_qp_kernel_variant.restype = C.c_char_p
-    lib.clik_qp_kernel_variant.argtypes = [vp, C.c_int64, C.c_int32]
-    lib.clik_qp_shape_describe.restype = C.c_int
-    lib.clik_qp_shape_describe.argtypes = [C.POINTER(clik_skill_desc), C.c_char_p, C.c_int]
-    lib.clik_qp_attach_kernel.restype = C.c_int
-    lib.clik_qp_attach_kernel.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_char_p]
-    lib.clik_qp_rollout_batch.restype = C.c_int
-    lib.clik_qp_rollout_batch.argtypes = [vp, C.c_int64, C.c_int32, C.c_double, C.c_double,
-                                          C.POINTER(C.c_double), dp, dp, dp, dp, ip, vp]
-    lib.clik_qp_rollout_batch_x.restype = C.c_int
-    lib.clik_qp_rollout_batch_x.argtypes = [vp, C.c_int64, C.c_int32, C.c_double, C.c_double,
-                                            C.POINTER(C.c_double), dp, dp, dp, dp, dp, dp, ip, vp]
-    lib.clik_qp_image_words.restype = C.c_int
-    lib.clik_qp_image_words.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
-    lib.clik_qp_is_box_family.restype = C.c_int
-    lib.clik_qp_is_box_family.argtypes = [vp]
-    lib.clik_qp_attach_value_kernel.restype = C.c_int
-    lib.clik_qp_attach_value_kernel.argtypes = [vp, vp, vp]
-    lib.clik_qp_rollout_batch_m.restype = C.c_int
-    lib.clik_qp_rollout_batch_m.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double,
-                                            C.POINTER(C.c_double), dp, dp, dp, dp, dp, dp, ip, vp]
-    lib.clik_qp_attach_rec_kernel.restype = C.c_int
-    lib.clik_qp_attach_rec_kernel.argtypes = [vp, C.c_void_p, C.c_void_p]
-    lib.clik_qp_rollout_batch_rec.restype = C.c_int
-    lib.clik_qp_rollout_batch_rec.argtypes = lib.clik_qp_rollout_batch_m.argtypes + [C.c_int32, C.c_int32, dp, dp, dp, dp,
-                                                                                     dp, ip]
-    # time slots on the device: `times` is a DEVICE pointer where the calls above take the host table `tterms`
-    for name in ("clik_pinv_attach_time_kernel", "clik_qp_attach_time_kernel"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [vp, C.c_void_p]
-    for name in ("clik_pinv_time_terms", "clik_qp_time_terms"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [vp, C.c_int64, dp, C.c_int32, C.c_double, dp, vp]
-    for name, rec in (("clik_pinv_rollout_batch_dev", lib.clik_pinv_rollout_batch_rec),
-                      ("clik_qp_rollout_batch_dev", lib.clik_qp_rollout_batch_rec)):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [dp if k == 6 else a for k, a in enumerate(rec.argtypes)]
-    # constraint values over a trajectory: `tterms` is a DEVICE table here, read through its two strides
-    for kind in ("pinv", "qp"):
-        fn = getattr(lib, "clik_%s_attach_monitor_kernel" % kind)
-        fn.restype, fn.argtypes = C.c_int, [vp, C.c_void_p]
-        fn = getattr(lib, "clik_%s_constraint_values" % kind)
-        fn.restype = C.c_int
-        fn.argtypes = [vp, C.c_int64, C.c_int64, dp, C.c_int64, C.c_int64, dp, dp, dp, C.c_int64, dp, dp, dp, vp]
-        fn = getattr(lib, "clik_%s_n_constraint_rows" % kind)
-        fn.restype, fn.argtypes = C.c_int, [vp]
-        # ... and their summaries: the same inputs, then tol, the work area and its size, the seven outputs
-        fn = getattr(lib, "clik_%s_attach_summary_kernel" % kind)
-        fn.restype, fn.argtypes = C.c_int, [vp, C.c_void_p, C.c_void_p]
-        fn = getattr(lib, "clik_%s_summary_work_bytes" % kind)
-        fn.restype, fn.argtypes = C.c_int64, [vp, C.c_int64, C.c_int64]
-        fn = getattr(lib, "clik_%s_constraint_summary" % kind)
-        fn.restype = C.c_int
-        fn.argtypes = [vp, C.c_int64, C.c_int64, dp, C.c_int64, C.c_int64, dp, dp, dp, C.c_int64, dp, vp, C.c_int64,
-                       dp, ip, dp, dp, dp, ip, ip, vp]
-        # the summarising rollout: the arguments of the recording one, then times (device), tol and the seven outputs
-        fn = getattr(lib, "clik_%s_attach_rollout_summary_kernel" % kind)
-        fn.restype, fn.argtypes = C.c_int, [vp, C.c_void_p]
-        fn = getattr(lib, "clik_%s_rollout_batch_sum" % kind)
-        fn.restype = C.c_int
-        fn.argtypes = getattr(lib, "clik_%s_rollout_batch_rec" % kind).argtypes + [dp, dp, dp, ip, dp, dp, dp, ip, ip]
-    # the converging rollout: B, max_ticks, dt, max_speed, min_step, tterms (host, one record), q, x, y, dq, dx, mode |
-    # status (QP: then slack), tol, ticks, stop_status, residual, stream
-    for kind, extra in (("pinv", []), ("qp", [dp])):
-        fn = getattr(lib, "clik_%s_attach_converge_kernel" % kind)
-        fn.restype, fn.argtypes = C.c_int, [vp, C.c_void_p]
-        fn = getattr(lib, "clik_%s_converge_batch" % kind)
-        fn.restype = C.c_int
-        fn.argtypes = [vp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double),
-                       dp, dp, dp, dp, dp, ip] + extra + [dp, ip, ip, dp, vp]
-    lib.clik_summary_chunk_length.restype = C.c_int64
-    lib.clik_summary_chunk_length.argtypes = [C.c_int64, C.c_int64]
-    lib.clik_qp_n_vars.restype = C.c_int
-    lib.clik_qp_n_vars.argtypes = [vp]
-    lib.clik_qp_n_rows.restype = C.c_int
-    lib.clik_qp_n_rows.argtypes = [vp]
-    lib.clik_qp_workspace_bytes.restype = C.c_int64
-    lib.clik_qp_workspace_bytes.argtypes = [vp]
-    lib.clik_qp_solve_batch.restype = C.c_int
-    lib.clik_qp_solve_batch.argtypes = [vp, C.c_int64, C.POINTER(C.c_double),
-                                        dp, dp, dp, dp, dp, dp, ip, vp]
-    lib.clik_qp_solve_batch_hot.restype = C.c_int
-    lib.clik_qp_solve_batch_hot.argtypes = [vp, C.c_int64, C.POINTER(C.c_double),
-                                        dp, dp, dp, dp, dp, dp, ip, ip, C.c_int32, vp]
-    lib.clik_qp_solve_batch_t.restype = C.c_int
-    lib.clik_qp_solve_batch_t.argtypes = [vp, C.c_int64, dp, dp, dp, dp, dp, dp, dp, ip, ip, C.c_int32, vp]
-    lib.clik_qp_data_batch.restype = C.c_int
-    lib.clik_qp_data_batch.argtypes = [vp, C.c_int64, C.POINTER(C.c_double),
-                                       dp, dp, dp, dp, dp, dp, dp, vp]
+    for name, ret, params in header_prototypes():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise ClikLibraryError("%s does not export %s, which include/clik.h declares" % (p, name))
+        fn.restype, fn.argtypes = prototype_ctypes(name, ret, params)
     if lib.clik_abi_version() != ABI_VERSION:
         raise ClikLibraryError("ABI version mismatch: library %d, python %d"
                                % (lib.clik_abi_version(), ABI_VERSION))

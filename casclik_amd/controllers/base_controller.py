@@ -402,6 +402,9 @@ class BaseController(object):
     controller_type = "BaseController"
     _create_fn = _destroy_fn = None
     _kind = None                # "pinv" | "qp": whose clik_<kind>_* entry points and jit.UNITS entries the handle takes
+    # what a rollout returns after dX and records after dx: (name, descriptor attribute of its width | None: one number per
+    # instance, dtype name); a width of 0 leaves the output out (None in the result, no record)
+    _rollout_tail = ()
     _kernels = {}               # on-demand kernels asked for so far, what -> cache tag | False (``_create_handle`` resets it)
 
     def __repr__(self):
@@ -708,6 +711,90 @@ class BaseController(object):
         """tol and the seven outputs as ``clik_*_constraint_summary`` and ``clik_*_rollout_batch_sum`` take them"""
         return (ptr(tol_dev), ptr(out["abs_max"]), ptr(out["abs_max_at"]), ptr(out["last"]), ptr(out["rms"]),
                 ptr(out["viol_max"]), ptr(out["viol_count"]), ptr(out.get("settled_at")))
+
+    def rollout_batch(self, time_vars, robot_var, input_var=None, dt=0.008, max_speed=0.0, virtual_var=None,
+                      method="euler", record_every=None, record_out=None, summary=False, summary_tol=None):
+        """``len(time_vars)`` ticks of solve -> clamp(+-max_speed) -> integrate in one launch, the host loop of
+        ur5_moe2016_example2.ipynb:537-545 (ReactiveQPController: the working set hot-started from tick to tick).
+        ``method="euler"``: ``q += dq*dt``; ``method="rk4"``: classical Runge-Kutta with the controller as the right-hand
+        side (casclik/integration_methods.py:17-23: k1..k4 at t, t+dt/2, t+dt/2, t+dt, each clamped).
+
+        Returns ``(q_final, dq_last, mode_last)`` (PseudoInverseController) or ``(q_final, dq_last, slack_last | None,
+        status [B])`` (ReactiveQPController: ``status`` is the worst status met so far, and an infeasible tick leaves the
+        state where it was).  For a skill with virtual variables (path following, cart_on_track_1D...ipynb cell 60: pass
+        ``virtual_var``) the path parameters are integrated alongside, unclamped, and the result is ``(q_final, x_final,
+        dq_last, dx_last, mode_last)`` or ``(q_final, x_final, dq_last, dx_last, slack_last | None, status)``.
+
+        Trajectory in: ``input_var`` may be ``[n_ticks, B, n_y]``, tick i then reads record i (``"rk4"``: all four
+        stages of the tick).  Trajectory out: ``record_every=k`` appends one last element to the result, a dict of
+        ``[n_ticks // k, B, .]`` arrays ``q``, ``dq`` (``x``, ``dx`` with virtual variables) and ``mode [R, B]``
+        (ReactiveQPController: ``slack`` when the skill has slack, and ``status [R, B]``, the worst status up to and
+        including that tick): entry r is what a launch ending at tick ``(r + 1) * k`` returns.  ``record_out``:
+        preallocated device tensors for some of them.  Both need a kernel instantiated for the skill
+        (NotImplementedError otherwise).
+
+        Summary: ``summary=True`` appends one more, last element (behind the records when ``record_every`` is given as
+        well): the dict ``constraint_summary_batch`` returns - ``abs_max``, ``abs_max_at``, ``last``, ``rms``,
+        ``viol_max``, ``viol_count`` and, with ``summary_tol`` (a scalar or ``[M_tot]`` values, finite and >= 0),
+        ``settled_at``; ``[B, M_tot]`` each, rows as ``constraint_rows()`` - computed inside the rollout, with no record
+        of the trajectory.  Record r = 0 .. n_ticks - 1 is what tick r acts on: ``time_vars[r]``, the state the tick
+        starts from (record 0: ``robot_var``) and the target it reads; with ``"rk4"`` the tick's first stage.  The state
+        after the last tick is not a record (``constraint_values_batch`` on ``q_final`` gives its e); a tick of the
+        ReactiveQPController that is infeasible leaves the state where it was, and the next record is that same state.
+        It is what ``constraint_summary_batch(time_vars, concat(q_0, rec["q"][:-1]), ...)`` gives on the records of the
+        same launch with ``record_every=1``, the same bits on every call and in every batch.  Such a launch uses the
+        lane-per-instance kernel at every batch size.  ValueError for ``summary_tol`` without ``summary``, a bad
+        ``summary_tol`` and an empty ``time_vars``; NotImplementedError when no kernel could be instantiated for the
+        skill, when its block does not fit the LDS of a compute unit or when its kernel would spill.
+
+        With ``options["time_on_device"]`` the launch goes through ``clik_*_rollout_batch_dev``: the time terms of all
+        ticks and stages are computed on the device from ``time_vars``, which may be a tensor on the controller's
+        device (used in place, no host synchronisation)."""
+        self._require_handle()
+        torch = _torch()
+        d, dev = self.descriptor, self._device
+        dev_times = self._time_kernel is not None
+        if dev_times:
+            n_ticks, stages, tt = self._rollout_times_dev(time_vars, method)
+            ttp = ptr(tt)
+        else:
+            n_ticks, stages, (tt, ttp) = self._rollout_times(time_vars, dt, method)
+        want_sum, tol = rollout_summary_request(summary, summary_tol, n_ticks, sum(int(t["m"]) for t in d.tasks))
+        tail = [(name, None if width is None else getattr(d, width), dtype) for name, width, dtype in self._rollout_tail]
+        Q, X, Y, B, was_np, y_per_tick, rec = self._rollout_io(
+            robot_var, virtual_var, input_var, n_ticks, record_every, record_out,
+            [("q", d.n_q, "float64"), ("dq", d.n_q, "float64"), ("x", d.n_x, "float64"), ("dx", d.n_x, "float64")] + tail)
+        dQ = torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
+        dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
+        last = [None if width == 0 else torch.empty((B,) if width is None else (B, width), dtype=getattr(torch, dtype),
+                                                    device=dev) for _, width, dtype in tail]
+        args = (self._handle, B, n_ticks, stages, float(dt), float(max_speed), ttp,
+                ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX), *map(ptr, last), current_stream(dev))
+        # (without records or per-tick targets: 0, 0 and NULL for every record)
+        r = rec or {}
+        rec_args = (y_per_tick, int(record_every or 0)) + tuple(
+            ptr(r.get(name)) for name in ["q", "dq", "x", "dx"] + [name for name, _, _ in tail])
+        entry = lambda suffix: getattr(self._lib, "clik_%s_rollout_batch_%s" % (self._kind, suffix))     # noqa: E731
+        summ = None
+        plain = rec is None and not y_per_tick
+        if want_sum:
+            # (records, per-tick targets and the summary in ONE launch of the summarising lane kernel)
+            tol_dev, summ = self._summary_out(tol, B)
+            self._require_kernel("rollsum")
+        elif not plain:
+            self._require_kernel("rec")
+        with torch.cuda.device(dev):
+            if want_sum:
+                # (here the host table and the device times are two arguments, and exactly one of them is given)
+                rc = entry("sum")(*args[:6], None if dev_times else ttp, *args[7:], *rec_args,
+                                  ttp if dev_times else None, *self._summary_ptrs(tol_dev, summ))
+            elif plain and not dev_times:
+                rc = entry("m")(*args)
+            else:
+                rc = entry("dev" if dev_times else "rec")(*args, *rec_args)
+        _capi.check(self._lib, rc)
+        outs = (Q, dQ, *last) if X is None else (Q, X, dQ, dX, *last)
+        return self._rollout_result(outs, rec, was_np, summ)
 
     # -- constraint values over a trajectory --------------------------------------------------------------------
     def constraint_rows(self):

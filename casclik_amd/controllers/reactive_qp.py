@@ -22,8 +22,7 @@ from .. import _capi
 from .. import sym as cs
 from ..constraints import (EqualityConstraint, SetConstraint, VelocityEqualityConstraint,
                            VelocitySetConstraint)
-from .base_controller import (BaseController, current_stream, ptr, check_out_tensor, scalar_of, _torch,
-                              rollout_summary_request)
+from .base_controller import (BaseController, current_stream, ptr, check_out_tensor, scalar_of, _torch)
 
 
 def _weights(weights, n, what):
@@ -68,6 +67,7 @@ class ReactiveQPController(BaseController):
     weight_shifter = 0.001   # mu of the eTaSL paper (reactive_qp.py:44)
     _create_fn, _destroy_fn = "clik_qp_create", "clik_qp_destroy"
     _kind = "qp"
+    _rollout_tail = (("slack", "n_slack", "float64"), ("status", None, "int32"))
 
     def __init__(self, skill_spec, robot_var_weights=None,
                  virtual_var_weights=None, slack_var_weights=None, options=None):
@@ -591,88 +591,6 @@ class ReactiveQPController(BaseController):
             rc = 0
         _capi.check(self._lib, rc)
         return self._to_caller((dQ, dX, SL, status), was_np)
-
-    def rollout_batch(self, time_vars, robot_var, input_var=None, dt=0.008, max_speed=0.0, virtual_var=None,
-                      method="euler", record_every=None, record_out=None, summary=False, summary_tol=None):
-        """``len(time_vars)`` ticks of QP solve -> clamp(+-max_speed) -> integrate in
-        one launch, the working set hot-started from tick to tick (the host loop of
-        ur5_moe2016_example2.ipynb:537-545 for this controller).  ``method="euler"``: ``q += dq*dt``;
-        ``method="rk4"``: classical Runge-Kutta with the controller as the right-hand side
-        (casclik/integration_methods.py:17-23: k1..k4 at t, t+dt/2, t+dt/2, t+dt, each clamped).  Returns
-        (q_final, dq_last, slack_last | None, status [B] = worst status met); for a skill with
-        virtual variables (pass ``virtual_var``; cart_on_track_1D...ipynb cell 60) they are integrated
-        alongside, unclamped: (q_final, x_final, dq_last, dx_last, slack_last | None, status).
-
-        Trajectory in: ``input_var`` may be ``[n_ticks, B, n_y]``, tick i then reads record i (``"rk4"``: all four
-        stages of the tick).  Trajectory out: ``record_every=k`` appends one last element to the result, a dict of
-        ``[n_ticks // k, B, .]`` arrays ``q``, ``dq`` (``x``, ``dx`` with virtual variables; ``slack`` when the skill has
-        slack) and ``status [R, B]``, the worst status up to and including that tick: entry r is what a launch ending
-        at tick ``(r + 1) * k`` returns.  ``record_out``: preallocated device tensors for some of them.  Both need a
-        kernel instantiated for the skill (NotImplementedError otherwise).
-
-        Summary: ``summary=True`` appends one more, last element (behind the records when ``record_every`` is given as
-        well): the dict ``constraint_summary_batch`` returns - ``abs_max``, ``abs_max_at``, ``last``, ``rms``,
-        ``viol_max``, ``viol_count`` and, with ``summary_tol`` (a scalar or ``[M_tot]`` values, finite and >= 0),
-        ``settled_at``; ``[B, M_tot]`` each, rows as ``constraint_rows()`` - computed inside the rollout, with no record
-        of the trajectory.  Record r = 0 .. n_ticks - 1 is what tick r acts on: ``time_vars[r]``, the state the tick
-        starts from (record 0: ``robot_var``) and the target it reads; with ``"rk4"`` the tick's first stage.  The state
-        after the last tick is not a record (``constraint_values_batch`` on ``q_final`` gives its e); a tick that is
-        infeasible leaves the state where it was, and the next record is that same state.  It is what
-        ``constraint_summary_batch(time_vars, concat(q_0, rec["q"][:-1]), ...)`` gives on the records of the same launch
-        with ``record_every=1``, the same bits on every call and in every batch.  Such a launch uses the
-        lane-per-instance kernel at every batch size.  ValueError for ``summary_tol`` without ``summary``, a bad
-        ``summary_tol`` and an empty ``time_vars``; NotImplementedError when no kernel could be instantiated for the
-        skill, when its block does not fit the LDS of a compute unit or when its kernel would spill.
-
-        With ``options["time_on_device"]`` the launch goes through ``clik_qp_rollout_batch_dev``: the time terms of all
-        ticks and stages are computed on the device from ``time_vars``, which may be a tensor on the controller's
-        device (used in place, no host synchronisation)."""
-        self._require_handle()
-        torch = _torch()
-        d = self.descriptor
-        dev = self._device
-        dev_times = self._time_kernel is not None
-        if dev_times:
-            n_ticks, stages, tt = self._rollout_times_dev(time_vars, method)
-            ttp = ptr(tt)
-        else:
-            n_ticks, stages, (tt, ttp) = self._rollout_times(time_vars, dt, method)
-        want_sum, tol = rollout_summary_request(summary, summary_tol, n_ticks, sum(int(t["m"]) for t in d.tasks))
-        Q, X, Y, B, was_np, y_per_tick, rec = self._rollout_io(
-            robot_var, virtual_var, input_var, n_ticks, record_every, record_out,
-            [("q", d.n_q, "float64"), ("dq", d.n_q, "float64"), ("x", d.n_x, "float64"), ("dx", d.n_x, "float64"),
-             ("slack", d.n_slack, "float64"), ("status", None, "int32")])
-        dQ = torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
-        dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
-        SL = torch.empty((B, d.n_slack), dtype=torch.float64, device=dev) if d.n_slack else None
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-        args = (self._handle, B, n_ticks, stages, float(dt), float(max_speed), ttp,
-                ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX), ptr(SL), ptr(status), current_stream(dev))
-        summ = None
-        if want_sum:
-            # (records, per-tick targets and the summary in ONE launch of the summarising kernel)
-            tol_dev, summ = self._summary_out(tol, B)
-            self._require_kernel("rollsum")
-            r = rec or {}
-            with torch.cuda.device(dev):
-                rc = self._lib.clik_qp_rollout_batch_sum(
-                    *(args[:6] + (None if dev_times else ttp,) + args[7:]), y_per_tick, int(record_every or 0),
-                    ptr(r.get("q")), ptr(r.get("dq")), ptr(r.get("x")), ptr(r.get("dx")), ptr(r.get("slack")),
-                    ptr(r.get("status")), ttp if dev_times else None, *self._summary_ptrs(tol_dev, summ))
-        elif rec is None and not y_per_tick:
-            with torch.cuda.device(dev):
-                rc = self._lib.clik_qp_rollout_batch_dev(*args, 0, 0, None, None, None, None, None, None) if dev_times \
-                    else self._lib.clik_qp_rollout_batch_m(*args)
-        else:
-            self._require_kernel("rec")
-            r = rec or {}
-            with torch.cuda.device(dev):
-                rc = (self._lib.clik_qp_rollout_batch_dev if dev_times else self._lib.clik_qp_rollout_batch_rec)(
-                    *args, y_per_tick, int(record_every or 0), ptr(r.get("q")), ptr(r.get("dq")), ptr(r.get("x")),
-                    ptr(r.get("dx")), ptr(r.get("slack")), ptr(r.get("status")))
-        _capi.check(self._lib, rc)
-        outs = (Q, dQ, SL, status) if X is None else (Q, X, dQ, dX, SL, status)
-        return self._rollout_result(outs, rec, was_np, summ)
 
     def bind_batch(self, robot_var, input_var=None, virtual_var=None, out=None, hot_start=False, hot_set=None):
         """Pre-bind device tensors and return ``tick(time_var=0.0)``: one kernel

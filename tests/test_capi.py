@@ -35,6 +35,104 @@ def test_exports_every_declared_symbol(lib):
     assert lib.clik_abi_version() == _capi.ABI_VERSION
 
 
+_SNIPPET = """
+/* a header in small: clik_in_a_comment(int x); is no declaration */
+#define CLIK_MACRO(x) \\
+    clik_in_a_macro(x)
+typedef struct clik_thing { int32_t n; double v[3]; } clik_thing;
+typedef struct clik_pinv clik_pinv;
+extern "C" {
+const char* clik_name(void);
+int64_t clik_count ( const clik_pinv *h,int64_t  B );   // clik_in_a_line_comment(int x);
+int clik_four_lines(const clik_pinv* h, int64_t B,
+                    const double* q, /* the state */ double* dq,
+                    int32_t *mode,
+                    void* stream);
+int clik_make(const clik_skill_desc* desc, const clik_qp_opts* opts, clik_qp** out);
+int32_t clik_nothing();
+}
+"""
+
+
+def test_parser_reads_synthetic_prototypes():
+    """comments of both kinds, a macro, struct bodies, a prototype over four lines with a comment between two
+    parameters, (void), an empty list, a ``const char*`` return, spaces in odd places"""
+    assert _capi.parse_prototypes(_SNIPPET) == [
+        ("clik_name", "const char*", []),
+        ("clik_count", "int64_t", ["const clik_pinv*", "int64_t"]),
+        ("clik_four_lines", "int", ["const clik_pinv*", "int64_t", "const double*", "double*", "int32_t*", "void*"]),
+        ("clik_make", "int", ["const clik_skill_desc*", "const clik_qp_opts*", "clik_qp**"]),
+        ("clik_nothing", "int32_t", []),
+    ]
+    vp = C.c_void_p
+    assert _capi.prototype_ctypes(*_capi.parse_prototypes(_SNIPPET)[2]) == (C.c_int, [vp, C.c_int64, vp, vp, vp, vp])
+    assert _capi.prototype_ctypes("clik_name", "const char*", []) == (C.c_char_p, [])
+    assert _capi.prototype_ctypes(*_capi.parse_prototypes(_SNIPPET)[3]) == (
+        C.c_int, [C.POINTER(_capi.clik_skill_desc), C.POINTER(_capi.clik_qp_opts), vp])
+    assert _capi.parse_prototypes("int clik_unnamed(int64_t, const double*);") == [
+        ("clik_unnamed", "int", ["int64_t", "const double*"])]
+
+
+@pytest.mark.parametrize("decl, spelling", [("int clik_bad(const clik_pinv* h, float gain);", "float"),
+                                            ("float clik_bad(void);", "float"),
+                                            ("int clik_bad(const float* gains);", "const float*"),
+                                            ("int clik_bad(double q[7]);", "double q[7]")])
+def test_parser_refuses_an_unknown_type(decl, spelling):
+    """no silent default: a type outside the mapping names the function and the spelling"""
+    (proto,) = _capi.parse_prototypes(decl)
+    with pytest.raises(_capi.ClikLibraryError) as err:
+        _capi.prototype_ctypes(*proto)
+    assert "clik_bad" in str(err.value) and repr(spelling) in str(err.value)
+
+
+def test_parser_refuses_what_it_cannot_read():
+    with pytest.raises(_capi.ClikLibraryError, match="clik_cb"):
+        _capi.parse_prototypes("int clik_cb(void (*fn)(int), void* arg);")
+
+
+def test_parser_finds_every_declared_name_of_the_header():
+    """on include/clik.h the parser returns exactly the names the regular expression of
+    test_exports_every_declared_symbol finds, each once: nothing is skipped"""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    declared = sorted(set(re.findall(r"\b(clik_[a-z_0-9]+)\s*\(", text)))
+    protos = _capi.parse_prototypes(open(HEADER).read())
+    assert sorted(name for name, _, _ in protos) == declared
+    assert _capi.exported_symbols() == [name for name, _, _ in protos]
+
+
+def test_loaded_functions_carry_the_header_prototypes(lib):
+    """after load_library() every function has the header's parameter count and kinds; the three struct parameters are
+    typed pointers, which refuse a wrong struct"""
+    protos = _capi.header_prototypes()
+    assert len(protos) >= 76
+    scalars = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
+    structs = {"const clik_skill_desc*": _capi.clik_skill_desc, "const clik_pinv_opts*": _capi.clik_pinv_opts,
+               "const clik_qp_opts*": _capi.clik_qp_opts}
+    seen = set()
+    for name, ret, params in protos:
+        fn = getattr(lib, name)
+        assert len(fn.argtypes) == len(params), name
+        for spelling, ctype in zip([ret] + params, [fn.restype] + list(fn.argtypes)):
+            if spelling in scalars:
+                assert ctype is scalars[spelling], (name, spelling)
+            elif spelling in structs:
+                assert ctype is not C.c_void_p and ctype._type_ is structs[spelling], (name, spelling)
+                seen.add(spelling)
+            elif spelling in ("const char*", "char*"):
+                assert ctype is C.c_char_p, (name, spelling)
+            else:
+                assert spelling.endswith("*") and ctype is C.c_void_p, (name, spelling)
+    assert seen == set(structs)
+    with pytest.raises(C.ArgumentError):
+        lib.clik_pinv_create(C.byref(_capi.clik_qp_opts()), None, None)
+
+
+def test_a_declared_function_the_library_lacks_fails_at_load(lib, monkeypatch):
+    monkeypatch.setattr(_capi, "_prototypes", _capi.header_prototypes() + [("clik_not_there", "int", [])])
+    with pytest.raises(_capi.ClikLibraryError, match="clik_not_there"):
+        _capi.load_library(_capi.LIB_PATH)
+
+
 def test_struct_layouts_match_the_header(tmp_path):
     src = tmp_path / "sz.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "clik.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n",'
