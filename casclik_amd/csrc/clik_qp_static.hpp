@@ -104,10 +104,14 @@ __device__ __forceinline__ int gi_solve(const double* Qs, const double* lbs, con
     // Violations are measured relative to max(1, |bound|) of the bound in question, not of the row (a
     // one-sided SetConstraint carries the reference's default 1e10 on its other side, constraints.py:199-206:
     // a common scale per row would hide the violation of the real bound).  The scale is recomputed from the
-    // bound the scan reads anyway (v_rcp_f64: ranking and a 1e-11 threshold do not need more); keeping the two
+    // bound the scan reads anyway (v_rcp_f64: ranking and a 1e-12 threshold do not need more); keeping the two
     // scales per row in registers instead (CLIK_QP_SCALE_REGS_MAX = rows up to which to do so) measured
     // 0.3-0.5 us slower per tick on config 4 (cold, hot and rollout) and spills beyond 8 rows.
-    constexpr double kVtol = 1e-11;
+    // 1e-12: a violation the scan ignores stays in the answer.  On a row that bounds one velocity that is an error of
+    // 1e-12 max(1, |b|) in a velocity of size |b| - below the floor of the parity rule, 1e-12 (1 + |v|); at 1e-11 a
+    // bound that is active by a multiplier of 1e-11 was missed by 1.4 bounds (tests/test_gpu_qp_exact_parity.py).
+    // The rows' own rounding (c = c0 + Q nu) is 1e-13 on the built-in skills.
+    constexpr double kVtol = 1e-12;
 #ifndef CLIK_QP_SCALE_REGS_MAX
 #define CLIK_QP_SCALE_REGS_MAX 0
 #endif
@@ -683,7 +687,7 @@ __device__ __forceinline__ int qp_box_pas(const double (&Pm)[N * (N + 1) / 2], c
     }
     // held[a]: the state sits on a bound and is not moved (mask word); free_ok[a]: it may be released (lb < ub)
     int held[N], free_ok[N];
-    double tol[N];
+    double tol[N], tolc[N];
     // Cold start: projected Gauss-Seidel sweeps from the clipped coordinate-wise minimisers x_a = clip(g_a / P_aa)
     // - each state in turn to the minimiser of its own coordinate, clipped, the residual g - P x updated by one
     // column (77 instructions per sweep against ~460 + seven dependent reciprocals of an active-set pass) - and the
@@ -754,7 +758,14 @@ __device__ __forceinline__ int qp_box_pas(const double (&Pm)[N * (N + 1) / 2], c
         const bool pin = !(ub[a] > lb[a]);
         held[a] = (on_l | on_u | pin) ? kOne : 0;
         free_ok[a] = pin ? 0 : kOne;
-        tol[a] = 1e-9 * fmax(1.0, fabs(g[a]));
+        // Release threshold of the state.  Zero until the state has been released once, 1e-9 max(1, |g_a|) after that:
+        // a held state whose multiplier has the wrong sign by ANY amount is let go - held at a bound that lies delta
+        // outside the minimiser its multiplier is wrong by delta / (P_FF^-1)_aa only, and a threshold of 1e-9 |g_a| kept
+        // it there up to 2e-6 out (velocity errors of 1e-9 ... 1e-7 on config 4; tests/test_gpu_qp_exact_parity.py) -
+        // but once only, so that a multiplier that is zero to rounding cannot make the state leave and land for ever:
+        // the second time it has to be wrong by more than rounding (tolc), as before.
+        tol[a] = 0.0;
+        tolc[a] = 1e-9 * fmax(1.0, fabs(g[a]));
     }
     double gr[N];
     auto gradient = [&]() __attribute__((always_inline)) {
@@ -832,15 +843,22 @@ __device__ __forceinline__ int qp_box_pas(const double (&Pm)[N * (N + 1) / 2], c
             r[a] = fabs(x[a] - tgt[a]) * __builtin_amdgcn_rcp(fabs(d[a]));
             amin = fmin(amin, r[a]);
         }
-        const bool blocked = amin < 1.0;
+        bool blocked = amin < 1.0;
         const double alpha = done ? 0.0 : amin;
         const double thr = amin * (1.0 + 1e-7);
 #pragma unroll
         for (int a = 0; a < N; ++a) {
             const double xn = fma(-alpha, d[a], x[a]);
-            const bool lands = blocked & !done & (r[a] <= thr);            // the blocking state (and ties): held there
+            // the blocking state (and ties): held there - ALSO after a full step (amin = 1): the hardware reciprocal is
+            // good to 2^-24, so a full step that ends within that share of |d_a| BEYOND a bound looks unblocked (a bound
+            // active by a multiplier of 1e-11 was missed that way, and overshot by 2e-11).  A state within 1e-7 |d_a|
+            // inside its bound lands too; its multiplier then has the wrong sign and the next pass lets it go again.
+            // (Free states only: a held state's ratio is the NaN of 0 * inf, and the device code is compiled without
+            // NaN semantics - the comparison alone may come out true.)
+            const bool lands = !done & (held[a] == 0) & (r[a] <= thr);
             x[a] = lands ? tgt[a] : xn;
             held[a] = lands ? kOne : held[a];
+            blocked = blocked | lands;
         }
         gradient();
         // at a face minimum: release the held state whose multiplier is wrong by the largest amount, or stop
@@ -853,8 +871,14 @@ __device__ __forceinline__ int qp_box_pas(const double (&Pm)[N * (N + 1) / 2], c
             worst = fmax(worst, c[a]);
         }
         const bool release = !blocked & !done & (worst > 0.0);
+        if (__ballot(release) != 0ull) {        // (wave-uniform: the last pass of a tick, and every pass of a hot one, skips it)
 #pragma unroll
-        for (int a = 0; a < N; ++a) held[a] = (release & (c[a] == worst)) ? 0 : held[a];
+            for (int a = 0; a < N; ++a) {
+                const bool go = release & (c[a] == worst);
+                held[a] = go ? 0 : held[a];
+                tol[a] = go ? tolc[a] : tol[a];         // (its next release needs more than rounding)
+            }
+        }
         done = done | (!blocked & !(worst > 0.0));
         if constexpr (FOLIO) {
             if (done & !done_before) {
@@ -883,7 +907,7 @@ __device__ __forceinline__ int qp_box_pas(const double (&Pm)[N * (N + 1) / 2], c
         bool kkt = true;
 #pragma unroll
         for (int a = 0; a < N; ++a) {
-            const bool fine = ((x[a] <= lb[a]) & (gr[a] >= -tol[a])) | ((x[a] >= ub[a]) & (gr[a] <= tol[a])) | (fabs(gr[a]) <= tol[a]);
+            const bool fine = ((x[a] <= lb[a]) & (gr[a] >= -tolc[a])) | ((x[a] >= ub[a]) & (gr[a] <= tolc[a])) | (fabs(gr[a]) <= tolc[a]);
             kkt = kkt & fine;
         }
         status = (done & kkt) ? 0 : 1;

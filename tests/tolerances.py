@@ -51,6 +51,27 @@ TWO YARDSTICKS for the pseudo-inverse path, and when each applies:
       the first yardstick had it at 0.02 of the bound; a Newton step less in `recip` moves the team kernels from
       0.2 - 0.65 to 0.8 - 0.9 u kappa_r and stays inside FACTOR (profiles/structural_parity.md).
 
+TWO YARDSTICKS for the QP path, and when each applies:
+
+  the literal oracle with kappa (above)        pins the STATUSES, infeasibility and the reference's problem data: what
+      `clik_oracle.qp_solve_batch` hands out, held to kappa = cond(H) * cond+(Aa H^-1 Aa').  With unit weights and
+      mu = 1e-3, cond(H) = 1001 - diagonal scaling, which limits no correct solver: on config 4 the bound has a median
+      of 4.8e-9 where the oracle itself is within 1.3e-12 of a 50-digit minimiser.  `qp_close`; what bench.py, smoke()
+      and every test written before the second one check.
+  the exact minimiser with kappa_S             pins the ARITHMETIC and the STOPPING RULES.  The unique minimiser at 50
+      digits with its optimality certificate (tests/qp_exact.py::qp_exact, an active-set polish of the oracle's answer)
+      and kappa_S = cond+(Aa H^-1 Aa') of its working set alone (`kappa_qp_active`): the condition of the system every
+      variant's algebra reduces to.  Median bound on config 4 below 1e-11, three orders under the first yardstick;
+      the literal oracle fits inside at <= 3.1 u kappa_S on random batches (tests/test_qp_exact_yardstick.py).
+      `qp_close_exact`, same FACTOR / FLOOR / ILL_POSED / MAX_LEFT_OUT; tests/test_gpu_qp_exact_parity.py holds the
+      tick kernels of the QP family to it, also at WEAKLY ACTIVE bounds (`qp_exact.weak_bound_cases`: a state within
+      1e-11 ... 1e-5 of its bound on either side), where only the exact evaluation can be the reference - the literal
+      oracle stops on a threshold of its own (`qp_solve_dense`: worst = -1e-11).  It found the box solver keeping a
+      held state held while its multiplier was wrong by less than 1e-9 |g_a| (430 ... 1.1e5 bounds out, velocity errors
+      of 2e-9 ... 1e-7, where the first yardstick saw nothing), a full step past a bound that the ratio test's hardware
+      reciprocal let through (4.6 bounds), and the dual iteration's 1e-11 violation threshold (1.4 bounds); all three
+      fixed in clik_qp_static.hpp, figures before and after in profiles/qp_exact_parity.md.
+
 Measured against the reference's own Python over the stand-in casadi (tests/golden/ref_pins.npz): err / (u kappa) <= 0.8
 for the oracle (tests/test_refpins.py); for the HIP kernels - different algebra: LDL' without pivoting, push-through and
 Woodbury forms, DESIGN.md section 3 - <= FACTOR with the margins recorded in profiles/r4_tolerance_sweep.txt."""
@@ -120,7 +141,7 @@ LAST = {}               # what the most recent *_close / worst_over_tol call did
 
 
 def _compare(a, ref, rows, kappa, ceiling, what, rule="kappa"):
-    """the shared body of pinv_close / qp_close / pinv_close_structural.  `ref` rows that are NaN (the oracle's "infeasible") are no instances;
+    """the shared body of pinv_close / qp_close / pinv_close_structural / qp_close_exact.  `ref` rows that are NaN (the oracle's "infeasible") are no instances;
     a NaN in `a` where `ref` is finite is a FAILURE.  `rows`: boolean mask of the instances to compare (so that `ref` can
     stay the array the oracle returned and every instance keeps ITS kappa); `kappa`: condition numbers [B] given
     explicitly (`cond_out` of the oracle), else looked up from the oracle's last solve when `ref` is its result."""
@@ -190,6 +211,14 @@ def qp_close(a, ref, ceiling=QP_RTOL, rows=None, kappa=None):
     """the same for the QP path (kappa = clik_oracle.qp_condition of each instance; rows the oracle reports infeasible -
     NaN in `ref` - are no instances)"""
     return _compare(a, ref, rows, kappa, ceiling, "qp_close")
+
+
+def qp_close_exact(a, ref, kappa_s, rows=None):
+    """`a` against `ref` = the 50-digit minimiser (tests/qp_exact.py::qp_exact), every instance held to
+    max(FLOOR, FACTOR u kappa_S), kappa_S [B] = `qp_exact.kappa_qp_active` of its working set.  The same body,
+    constants, NaN rule and `LAST` bookkeeping (rule "kappa_s") as `qp_close`; there is no ceiling to fall back to."""
+    assert kappa_s is not None, "qp_close_exact needs kappa_qp_active of the exact minimiser's working set"
+    return _compare(a, ref, rows, kappa_s, None, "qp_close_exact", rule="kappa_s")
 
 
 def worst_over_tol(a, ref, rows=None, kappa=None):
