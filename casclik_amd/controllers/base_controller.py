@@ -395,7 +395,7 @@ def trajectory_rows(val, width, what, lead=None):
 
 class BaseController(object):
     """What a device controller is apart from its mathematics.  A controller class names the C entry points that make
-    and free its handle (``_create_fn`` / ``_destroy_fn``), returns their options structure from ``_c_options()``, says
+    and free its handle (``_create_fn`` / ``_destroy_fn``), returns their options structure from ``_c_options(descriptor)``, says
     in ``_slot_results()`` how many doubles and int32 its ``solve()`` brings back, and has ``skill_spec`` and
     ``options``; ``_create_handle()`` then gives it ``_lib``, ``_handle``, ``_device`` and ``descriptor``, which every
     other helper here works from."""
@@ -435,7 +435,7 @@ class BaseController(object):
         self._lib = _capi.load_library()
         self.descriptor = lower_skill(self.skill_spec)
         cdesc = _capi.desc_to_c(self.descriptor)
-        copts = self._c_options()
+        copts = self._c_options(self.descriptor)
         self._device = device_of(self.options.get("device"))
         handle = C.c_void_p()
         with _torch().cuda.device(self._device):

@@ -220,7 +220,7 @@ class PseudoInverseController(BaseController):
         self._require_generated_code_kernel()
         self._setup_time_kernel()
 
-    def _c_options(self):
+    def _c_options(self, d):
         return _capi.pinv_opts_to_c(self.options)
 
     def kernel_variant(self, batch):

@@ -189,8 +189,7 @@ class ReactiveQPController(BaseController):
                 "value-specialised QP kernel could not be built, using the image-reading one", 300)
         self._setup_time_kernel()
 
-    def _c_options(self):
-        d = self.descriptor
+    def _c_options(self, d):
         state_w = np.concatenate([self._robot_var_weights,
                                   self._virtual_var_weights[:d.n_x]])
         if self._slack_var_weights.size != d.n_slack:

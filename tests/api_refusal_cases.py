@@ -41,8 +41,7 @@ def descriptors(iiwa_fk, ur5_fk):
         out[name] = (_capi.desc_to_c(d), opts, d.n_x, d.n_y, d.n_tslots)
     spec = skills.qp_skill(iiwa_fk)
     d = lower_skill(spec)
-    qc = cc.ReactiveQPController(skill_spec=spec)
-    opts = _capi.qp_opts_to_c(qc.weight_shifter, list(qc._robot_var_weights), list(qc._slack_var_weights))
+    opts = cc.ReactiveQPController(skill_spec=spec)._c_options(d)
     out["qp"] = (_capi.desc_to_c(d), opts, d.n_x, d.n_y, d.n_tslots)
     return out
 

@@ -72,47 +72,32 @@ def test_shape_of_the_config3_stack():
         assert rc4 == inside
 
 
-def test_instantiated_notebook_qp_kernel_has_no_scratch(tmp_path):
+def test_instantiated_notebook_qp_kernel_has_no_scratch():
     """The kernel instantiated for the dual-quaternion notebook QP (generated 8-row error, joint limits and
     speed limits merged into six box rows) must stay in registers: 12 separate rows spilled 784 B per lane."""
-    import subprocess
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from extern_skills import dual_quaternion_skill
     from casclik_amd import jit
-    from casclik_amd.build import parse_resource_remarks, FLAGS
-    hipcc = jit._hipcc()
-    if hipcc is None:
+    if jit._hipcc() is None:
         pytest.skip("hipcc not available")
-    lib = _capi.load_library()
-    d = lower_skill(dual_quaternion_skill(skills.ur5(), "Q_dist2"))
-    cdesc = _capi.desc_to_c(d)
-    buf = C.create_string_buffer(16384)
-    assert lib.clik_qp_shape_describe(C.byref(cdesc), buf, len(buf)) == 1
-    src = tmp_path / "dq_qp.hip"
-    src.write_text(jit._QP_TEMPLATE % {"init": buf.value.decode(), "extern": d.extern_source()})
-    out = subprocess.run([hipcc] + FLAGS + ["-c", str(src), "-o", str(tmp_path / "dq_qp.o")],
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert out.returncode == 0, out.stdout.decode()[-2000:]
-    res = parse_resource_remarks(out.stdout.decode())
+    req = jit.unit_request(cc.ReactiveQPController(skill_spec=dual_quaternion_skill(skills.ur5(), "Q_dist2")))
+    assert req.eligible
+    res = jit.unit_resources(jit.unit_text(jit._QP_TEMPLATE, req.init, req.extern), req.init)
     kernels = {k: v for k, v in res.items() if "qp_solve_static" in k or "qp_rollout_static_kernel" in k}
     assert len(kernels) == 4          # per tick (one time / one time per instance), rollout (Euler / Runge-Kutta)
     for name, r in kernels.items():
+        print(name[-60:], r)
         assert r["ScratchSize"] == 0, (name, r)
 
 
-def test_instantiated_kernels_with_expression_attributes_have_no_scratch(tmp_path):
+def test_instantiated_kernels_with_expression_attributes_have_no_scratch():
     """gains / bounds given as expressions (ExternAttr code + the per-lane attribute slice of the task cache)
     must dissolve into registers: one run-time evaluated offset pins the whole task cache in scratch"""
-    import subprocess
     import numpy as np
-    import casclik_amd as cc
     from casclik_amd import jit, sym as cs
-    from casclik_amd.build import parse_resource_remarks, FLAGS
-    hipcc = jit._hipcc()
-    if hipcc is None:
+    if jit._hipcc() is None:
         pytest.skip("hipcc not available")
-    lib = _capi.load_library()
     fk = skills.ur5()
     t, q = cs.MX.sym("t"), cs.MX.sym("q", 6)
     gain = 0.5 + 0.3 * cs.sin(0.2 * t) + 0.1 * q[0] * q[0]
@@ -121,51 +106,35 @@ def test_instantiated_kernels_with_expression_attributes_have_no_scratch(tmp_pat
         cc.SetConstraint("lims", q, gain=gain, set_min=-lim, set_max=lim, priority=0),
         cc.EqualityConstraint("move", fk["T_fk"](q)[:3, 3] - np.array([0.3, 0.2, 0.4]), gain=gain,
                               constraint_type="soft", priority=1)])
-    d = lower_skill(spec)
-    cdesc = _capi.desc_to_c(d)
-    buf = C.create_string_buffer(16384)
-    assert lib.clik_qp_shape_describe(C.byref(cdesc), buf, len(buf)) == 1
-    src = tmp_path / "attr_qp.hip"
-    src.write_text(jit._QP_TEMPLATE % {"init": buf.value.decode(), "extern": d.extern_source()})
-    out = subprocess.run([hipcc] + FLAGS + ["-c", str(src), "-o", str(tmp_path / "attr_qp.o")],
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert out.returncode == 0, out.stdout.decode()[-2000:]
-    res = parse_resource_remarks(out.stdout.decode())
+    req = jit.unit_request(cc.ReactiveQPController(skill_spec=spec))
+    assert req.eligible
+    res = jit.unit_resources(jit.unit_text(jit._QP_TEMPLATE, req.init, req.extern), req.init)
     kernels = {k: v for k, v in res.items() if "_static_" in k}
     assert len(kernels) == 4
     for name, r in kernels.items():
+        print(name[-60:], r)
         assert r["ScratchSize"] == 0, (name, r)
 
 
-def test_value_specialised_kernels_of_the_config3_skill_have_no_scratch(tmp_path):
+def test_value_specialised_kernels_of_the_config3_skill_have_no_scratch():
     """The kernels casclik_amd/jit.py::attach_values instantiates for BASELINE config 3 with the skill's numbers compiled
     in (four lanes per instance, one lane per instance, their rollouts) must stay in registers, and the one-lane kernel
     must fit two waves per SIMD (that is what makes it the large-batch kernel).  The skill-image words come from a
     host-only handle (CLIK_HOST_ONLY, include/clik.h): no GPU, no recorded fixture."""
     import re
-    import subprocess
-    from casclik_amd import jit, _capi
-    from casclik_amd.build import parse_resource_remarks, FLAGS, CSRC
-    from casclik_amd.lowering import lower_skill
-    hipcc = jit._hipcc()
-    if hipcc is None:
+    from casclik_amd import jit
+    from casclik_amd.build import CSRC
+    if jit._hipcc() is None:
         pytest.skip("hipcc not available")
     spec = skills.stack_skill(skills.iiwa())
-    full = cc.PseudoInverseController(skill_spec=spec, options=dict(skills.STACK_OPTIONS)).options
-    words = jit.host_image_words(_capi.load_library(), "pinv", _capi.desc_to_c(lower_skill(spec)), _capi.pinv_opts_to_c(full))
+    req = jit.unit_request(cc.PseudoInverseController(skill_spec=spec, options=dict(skills.STACK_OPTIONS)), words=True)
     gen = open(os.path.join(CSRC, "clik_shapes_gen.hpp")).read()
     init = re.search(r"kStackIiwa\s*=\s*(\{.*?\});", gen, re.S).group(1)
-    text = jit._VALUE_TEMPLATE.replace("%(nwords)d", str(len(words))).replace(
-        "%(words)s", ", ".join(w + "ull" for w in words)) % {"init": init, "extern": ""}
-    src = tmp_path / "stack_values.hip"
-    src.write_text(text)
+    text = jit.unit_text(jit._VALUE_TEMPLATE, init, "", req.words)
     # (compiled as shipped: with the scheduling strategy jit.py picks for this translation unit)
     sched = jit.sched_strategy(text, init)
     assert sched == "max-memory-clause"
-    out = subprocess.run([hipcc] + FLAGS + ["-DCLIK_VALUE_KERNEL"] + jit.sched_flags(sched) + ["-c", str(src),
-                          "-o", str(tmp_path / "stack_values.o")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert out.returncode == 0, out.stdout.decode()[-2000:]
-    res = parse_resource_remarks(out.stdout.decode())
+    res = jit.unit_resources(text, init, jit.VALUE_DEFINES)
     kernels = {k: v for k, v in res.items() if "_static_" in k}
     # team solve, team rollout (Euler, Runge-Kutta: its own instantiation each since round 6), lane solve, lane rollout
     # (Euler, Runge-Kutta)
@@ -217,8 +186,8 @@ def test_value_kernels_of_the_team_family_compile_for_long_input_rows():
         ok, init = jit.shape_of(lib, cdesc, copts)
         assert ok and desc.n_y == 7 + n
         words = jit.host_image_words(lib, "pinv", cdesc, copts)
-        text = jit._VALUE_TEMPLATE.replace("%(nwords)d", str(len(words))).replace("%(words)s", ", ".join(w + "ull" for w in words))
-        so, tag = jit.build_shape_library(init, False, template=text, defines=("-DCLIK_VALUE_KERNEL",), extern="")
+        so, tag = jit.build_shape_library(init, False, template=jit._with_words(jit._VALUE_TEMPLATE, words),
+                                          defines=jit.VALUE_DEFINES, extern="")
         assert so is not None and os.path.exists(so)
 
 

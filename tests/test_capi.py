@@ -272,9 +272,7 @@ def test_qp_kernel_selection_table(lib, monkeypatch, skill, env):
     fk = skills.ur5() if skill == "config4_ur5" else skills.iiwa()
     spec = skills.pose_skill(fk) if skill == "hard_pose_iiwa" else skills.qp_skill(fk)
     d = lower_skill(spec)
-    qc = cc.ReactiveQPController(skill_spec=spec)
-    state_w = list(qc._robot_var_weights) + list(qc._virtual_var_weights[:d.n_x])
-    copts = _capi.qp_opts_to_c(qc.weight_shifter, state_w, list(qc._slack_var_weights))
+    copts = cc.ReactiveQPController(skill_spec=spec)._c_options(d)
     desc = _capi.desc_to_c(d)
     h = C.c_void_p()
     assert lib.clik_qp_create_host(C.byref(desc), C.byref(copts), C.byref(h)) == 0

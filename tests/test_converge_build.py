@@ -6,15 +6,12 @@ import ctypes as C
 import hashlib
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import casclik_amd as cc
 from casclik_amd import _capi, jit, skills
 from casclik_amd.controllers.base_controller import converge_request, converge_tolerances, select_seeds
-from casclik_amd.lowering import lower_skill
 
 import converge_cases as K
 
@@ -26,33 +23,18 @@ LDS_CAP = jit.SUMMARY_LDS_BYTES
 
 def _unit(name):
     """(kind, descriptor, C descriptor, C options, shape initialiser, generated code, template) of a fixture's unit"""
-    lib = _capi.load_library()
-    fk = skills.iiwa()
-    spec, ctrl, qp = K.make(name, fk, skills.ur5())
-    d = lower_skill(spec)
-    cdesc = _capi.desc_to_c(d)
-    copts = None if qp else _capi.pinv_opts_to_c(ctrl.options)          # (the QP's shape does not depend on its options)
-    kind = "qp" if qp else "pinv"
-    ok, init = jit.shape_init(lib, kind, cdesc, copts)
-    assert ok
-    return kind, d, cdesc, copts, init, d.extern_source(), jit.CONVERGE_UNITS["converge", kind]["template"]
+    req = jit.unit_request(K.make(name, skills.iiwa(), skills.ur5())[1])
+    assert req.eligible
+    return (req.kind, req.descriptor, req.cdesc, req.copts, req.init, req.extern,
+            jit.CONVERGE_UNITS["converge", req.kind]["template"])
 
 
 @pytest.mark.parametrize("name", ["pose", "stack", "qp"])
-def test_converging_rollout_compiles_for_gfx950_without_scratch(name, tmp_path):
-    from casclik_amd.build import parse_resource_remarks
-    hipcc = jit._hipcc()
-    if hipcc is None:
+def test_converging_rollout_compiles_for_gfx950_without_scratch(name):
+    if jit._hipcc() is None:
         pytest.skip("hipcc not available")
     kind, d, cdesc, copts, init, extern, tmpl = _unit(name)
-    src = tmp_path / "converge.hip"
-    src.write_text(tmpl % {"init": init, "extern": extern})
-    # (compiled as shipped: with the scheduling strategy jit.py picks for this translation unit)
-    flags = [f for f in jit.compile_flags() if f != "-shared"] + jit.sched_flags(jit.sched_strategy(tmpl, init))
-    out = subprocess.run([hipcc] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", str(src), "-o",
-                                            str(tmp_path / "converge.o")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert out.returncode == 0, out.stdout.decode()[-3000:]
-    res = parse_resource_remarks(out.stdout.decode())
+    res = jit.unit_resources(jit.unit_text(tmpl, init, extern), init)         # (compiled as shipped)
     kernel = "qp_converge_static_kernel" if kind == "qp" else "pinv_converge_static_kernel"
     assert len(res) == 1 and all(kernel in k for k in res), sorted(res)        # (Euler only, nothing else)
     for k, r in res.items():

@@ -271,18 +271,10 @@ def test_the_host_evaluator_answers_as_ieee_does_where_python_raises():
 
 # ---- device compilation ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", fc.NAMES)
-def test_function_kernel_compiles_for_gfx950_alone_and_without_scratch(name, tmp_path):
-    from casclik_amd.build import parse_resource_remarks
-    hipcc = jit._hipcc()
-    if hipcc is None:
+def test_function_kernel_compiles_for_gfx950_alone_and_without_scratch(name):
+    if jit._hipcc() is None:
         pytest.skip("hipcc not available")
-    src = tmp_path / "function.hip"
-    src.write_text(jit._FUNCTION_TEMPLATE % {"init": "", "extern": codegen.emit_function(fc.get(name))})
-    flags = [f for f in jit.compile_flags() if f not in ("-shared",)]
-    out = subprocess.run([hipcc] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", str(src), "-o",
-                                            str(tmp_path / "function.o")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert out.returncode == 0, out.stdout.decode()[-3000:]
-    res = parse_resource_remarks(out.stdout.decode())
+    res = jit.unit_resources(jit.unit_text(jit._FUNCTION_TEMPLATE, "", codegen.emit_function(fc.get(name))), "")
     assert len(res) == 1, sorted(res)
     (kernel, r), = res.items()
     assert "function_batch_kernel" in kernel

@@ -6,7 +6,6 @@ import hashlib
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -37,37 +36,18 @@ def _fixture(name):
     return spec, cc.PseudoInverseController(skill_spec=spec), "pinv"
 
 
-def _shape_init(lib, ctrl, kind, d):
-    cdesc = _capi.desc_to_c(d)
-    if kind == "pinv":
-        ok, init = jit.shape_of(lib, cdesc, _capi.pinv_opts_to_c(ctrl.options))
-        assert ok
-        return init
-    buf = C.create_string_buffer(8192)
-    assert lib.clik_qp_shape_describe(C.byref(cdesc), buf, len(buf)) == 1
-    return buf.value.decode()
-
-
 @pytest.mark.parametrize("name", FIXTURES)
-def test_monitor_unit_compiles_for_gfx950_without_scratch(name, tmp_path):
-    from casclik_amd.build import parse_resource_remarks
-    hipcc = jit._hipcc()
-    if hipcc is None:
+def test_monitor_unit_compiles_for_gfx950_without_scratch(name):
+    if jit._hipcc() is None:
         pytest.skip("hipcc not available")
-    lib = _capi.load_library()
-    spec, ctrl, kind = _fixture(name)
-    d = lower_skill(spec)
+    req = jit.unit_request(_fixture(name)[1])
+    assert req.eligible
+    d = req.descriptor
     if name == "dual_quaternion":
         assert d.extern_code                         # (the 8-row deviation runs as generated code)
     if name == "tracking":
         assert d.n_tslots > 0
-    src = tmp_path / "monitor.hip"
-    src.write_text(jit._MONITOR_TEMPLATE % {"init": _shape_init(lib, ctrl, kind, d), "extern": d.extern_source()})
-    flags = [f for f in jit.compile_flags() if f not in ("-shared",)]
-    out = subprocess.run([hipcc] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", str(src), "-o",
-                                            str(tmp_path / "monitor.o")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert out.returncode == 0, out.stdout.decode()[-3000:]
-    res = parse_resource_remarks(out.stdout.decode())
+    res = jit.unit_resources(jit.unit_text(jit._MONITOR_TEMPLATE, req.init, req.extern), req.init)
     assert len(res) == 1, sorted(res)        # (the one kernel of the unit: none of the tick / rollout kernels)
     for kernel, r in res.items():
         assert "constraint_values_kernel" in kernel
@@ -197,9 +177,7 @@ def test_c_abi_edges_on_host_only_handles(monkeypatch):
         assert lib.clik_pinv_destroy(h) == 0
     spec, qc, _ = _fixture("qp")
     d = lower_skill(spec)
-    desc = _capi.desc_to_c(d)
-    state_w = list(qc._robot_var_weights) + list(qc._virtual_var_weights[:d.n_x])
-    qopts = _capi.qp_opts_to_c(qc.weight_shifter, state_w, qc._slack_var_weights, int(qc.options.get("max_iter", 0)))
+    desc, qopts = _capi.desc_to_c(d), qc._c_options(d)
     assert lib.clik_qp_create(C.byref(desc), C.byref(qopts), C.byref(h)) == 0
     try:
         assert lib.clik_qp_n_constraint_rows(h) == 13

@@ -2,20 +2,17 @@
 translation units cross-compiled for gfx950 without scratch, two kernels each (Euler and Runge-Kutta) and nothing else; a
 recorded request replayed by ``prebuild_recorded`` under the name the attach asks for; the tags of every other template
 untouched by the new header; and what ``rollout_batch(..., summary=, summary_tol=)`` refuses on the host."""
-import ctypes as C
 import hashlib
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import casclik_amd as cc
-from casclik_amd import _capi, jit, skills
+from casclik_amd import jit, skills
 from casclik_amd.controllers.base_controller import rollout_summary_request
-from casclik_amd.lowering import lower_skill
 
 from extern_skills import mixed_frame_skill
 
@@ -26,41 +23,24 @@ _OLD_TEMPLATES = ("_TEMPLATE", "_VALUE_TEMPLATE", "_QP_TEMPLATE", "_QP_VALUE_TEM
 
 def _unit(name):
     """(shape initialiser, generated constraint code, template) of the summarising rollout of a fixture"""
-    lib = _capi.load_library()
     fk = skills.iiwa()
     if name == "qp":
-        spec, tmpl = skills.qp_skill(fk), jit._QP_ROLLSUM_TEMPLATE
+        ctrl = cc.ReactiveQPController(skill_spec=skills.qp_skill(fk))
     elif name == "stack":
-        spec, opts, tmpl = skills.stack_skill(fk), dict(skills.STACK_OPTIONS), jit._ROLLSUM_TEMPLATE
+        ctrl = cc.PseudoInverseController(skill_spec=skills.stack_skill(fk), options=dict(skills.STACK_OPTIONS))
     else:
-        spec, opts, tmpl = mixed_frame_skill(fk), {"multidim_sets": False}, jit._ROLLSUM_TEMPLATE      # (a virtual variable)
-    d = lower_skill(spec)
-    cdesc = _capi.desc_to_c(d)
-    if name == "qp":
-        buf = C.create_string_buffer(8192)
-        assert lib.clik_qp_shape_describe(C.byref(cdesc), buf, len(buf)) == 1
-        return buf.value.decode(), d.extern_source(), tmpl
-    ctrl = cc.PseudoInverseController(skill_spec=spec, options=opts)
-    ok, init = jit.shape_of(lib, cdesc, _capi.pinv_opts_to_c(ctrl.options))
-    assert ok
-    return init, d.extern_source(), tmpl
+        ctrl = cc.PseudoInverseController(skill_spec=mixed_frame_skill(fk), options={"multidim_sets": False})  # (a virtual variable)
+    req = jit.unit_request(ctrl)
+    assert req.eligible
+    return req.init, req.extern, jit.UNITS["rollsum", req.kind]["template"]
 
 
 @pytest.mark.parametrize("name", ["stack", "mixed", "qp"])
-def test_summarising_rollout_compiles_for_gfx950_without_scratch(name, tmp_path):
-    from casclik_amd.build import parse_resource_remarks
-    hipcc = jit._hipcc()
-    if hipcc is None:
+def test_summarising_rollout_compiles_for_gfx950_without_scratch(name):
+    if jit._hipcc() is None:
         pytest.skip("hipcc not available")
     init, extern, tmpl = _unit(name)
-    src = tmp_path / "rollsum.hip"
-    src.write_text(tmpl % {"init": init, "extern": extern})
-    # (compiled as shipped: with the scheduling strategy jit.py picks for this translation unit)
-    flags = [f for f in jit.compile_flags() if f != "-shared"] + jit.sched_flags(jit.sched_strategy(tmpl, init))
-    out = subprocess.run([hipcc] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", str(src), "-o",
-                                            str(tmp_path / "rollsum.o")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert out.returncode == 0, out.stdout.decode()[-3000:]
-    res = parse_resource_remarks(out.stdout.decode())
+    res = jit.unit_resources(jit.unit_text(tmpl, init, extern), init)         # (compiled as shipped)
     kernel = "qp_rollout_static_sum_kernel" if name == "qp" else "pinv_rollout_static_sum_kernel"
     assert len(res) == 2 and all(kernel in k for k in res), sorted(res)        # (Euler and Runge-Kutta, nothing else)
     for k, r in res.items():

@@ -7,7 +7,6 @@ import hashlib
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -29,35 +28,15 @@ def _fixture(name):
     return spec, cc.ReactiveQPController(skill_spec=spec, robot_var_weights=[1.0, 1.0]), "qp"
 
 
-def _shape_init(lib, ctrl, kind, d):
-    cdesc = _capi.desc_to_c(d)
-    if kind == "pinv":
-        ok, init = jit.shape_of(lib, cdesc, _capi.pinv_opts_to_c(ctrl.options))
-        assert ok
-        return init
-    buf = C.create_string_buffer(8192)
-    assert lib.clik_qp_shape_describe(C.byref(cdesc), buf, len(buf)) == 1
-    return buf.value.decode()
-
-
 @pytest.mark.parametrize("name", ["stack", "pendulum"])
-def test_summary_unit_compiles_for_gfx950_without_scratch(name, tmp_path):
-    from casclik_amd.build import parse_resource_remarks
-    hipcc = jit._hipcc()
-    if hipcc is None:
+def test_summary_unit_compiles_for_gfx950_without_scratch(name):
+    if jit._hipcc() is None:
         pytest.skip("hipcc not available")
-    lib = _capi.load_library()
-    spec, ctrl, kind = _fixture(name)
-    d = lower_skill(spec)
+    req = jit.unit_request(_fixture(name)[1])
+    assert req.eligible
     if name == "pendulum":
-        assert d.extern_code                         # (its constraints run as generated code)
-    src = tmp_path / "summary.hip"
-    src.write_text(jit._SUMMARY_TEMPLATE % {"init": _shape_init(lib, ctrl, kind, d), "extern": d.extern_source()})
-    flags = [f for f in jit.compile_flags() if f not in ("-shared",)]
-    out = subprocess.run([hipcc] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", str(src), "-o",
-                                            str(tmp_path / "summary.o")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert out.returncode == 0, out.stdout.decode()[-3000:]
-    res = parse_resource_remarks(out.stdout.decode())
+        assert req.descriptor.extern_code            # (its constraints run as generated code)
+    res = jit.unit_resources(jit.unit_text(jit._SUMMARY_TEMPLATE, req.init, req.extern), req.init)
     assert len(res) == 2, sorted(res)        # (the two phases: none of the tick / rollout / constraint-value kernels)
     assert sorted("combine" in k for k in res) == [False, True]
     for kernel, r in res.items():
@@ -106,9 +85,9 @@ def test_a_recorded_summary_request_replays(tmp_path, monkeypatch):
     controller will ask for; the committed records hold the units of the GPU tests' five skills"""
     if jit._hipcc() is None:
         pytest.skip("hipcc not available")
-    lib = _capi.load_library()
-    spec, ctrl, kind = _fixture("stack")
-    init = _shape_init(lib, ctrl, kind, lower_skill(spec))
+    req = jit.unit_request(_fixture("stack")[1])
+    assert req.eligible
+    init = req.init
     monkeypatch.setenv("CLIK_JIT_RECORD", str(tmp_path / "records"))
     monkeypatch.setattr(jit, "CACHE", str(tmp_path / "cache"))
     monkeypatch.setenv("CLIK_JIT_NO_COMPILER", "1")

@@ -119,18 +119,10 @@ def test_emitted_text_as_host_code_matches_the_host_evaluator(descs, name, tmp_p
 
 
 @pytest.mark.parametrize("name", SKILLS)
-def test_time_kernel_compiles_for_gfx950_alone_and_without_scratch(descs, name, tmp_path):
-    from casclik_amd.build import parse_resource_remarks
-    hipcc = jit._hipcc()
-    if hipcc is None:
+def test_time_kernel_compiles_for_gfx950_alone_and_without_scratch(descs, name):
+    if jit._hipcc() is None:
         pytest.skip("hipcc not available")
-    src = tmp_path / "time.hip"
-    src.write_text(jit._TIME_TEMPLATE % {"init": "", "extern": codegen.emit_time_slots(descs[name])})
-    flags = [f for f in jit.compile_flags() if f not in ("-shared",)]
-    out = subprocess.run([hipcc] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", str(src), "-o",
-                                            str(tmp_path / "time.o")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert out.returncode == 0, out.stdout.decode()[-2000:]
-    res = parse_resource_remarks(out.stdout.decode())
+    res = jit.unit_resources(jit.unit_text(jit._TIME_TEMPLATE, "", codegen.emit_time_slots(descs[name])), "")
     assert len(res) == 1, sorted(res)
     (kernel, r), = res.items()
     assert "time_terms_kernel" in kernel

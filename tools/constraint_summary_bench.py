@@ -9,16 +9,14 @@ after a warm-up round; median and minimum are reported.  `--resources` compiles 
 scratch of its two kernels (no GPU needed); `--write` puts the tables into profiles/constraint_summary.md.
 """
 import os
-import subprocess
 import sys
-import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np          # noqa: E402
 
 import casclik_amd as cc    # noqa: E402
-from casclik_amd import _capi, jit, skills      # noqa: E402
+from casclik_amd import jit, skills      # noqa: E402
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 B = int(args[0]) if args else 16384
@@ -30,31 +28,18 @@ MARK = "<!-- tools/constraint_summary_bench.py %s -->"
 
 def resources_part():
     """registers / LDS / scratch of the two kernels, from the compiler's resource remarks"""
-    from casclik_amd.build import parse_resource_remarks
-    from casclik_amd.lowering import lower_skill
-    lib = _capi.load_library()
-    spec = skills.stack_skill(skills.iiwa())
-    ctrl = cc.PseudoInverseController(skill_spec=spec, options=dict(skills.STACK_OPTIONS))
-    ok, init = jit.shape_of(lib, _capi.desc_to_c(lower_skill(spec)), _capi.pinv_opts_to_c(ctrl.options))
-    assert ok
+    import ctypes as C
+    ctrl = cc.PseudoInverseController(skill_spec=skills.stack_skill(skills.iiwa()), options=dict(skills.STACK_OPTIONS))
+    req = jit.unit_request(ctrl)
+    assert req.eligible
     out = ["", "### Kernel resources (headline skill, compiler remarks)", "",
            "| kernel | VGPR | AGPR | SGPR | LDS bytes | scratch | occupancy (waves / SIMD) |", "|---|---|---|---|---|---|---|"]
-    with tempfile.TemporaryDirectory() as tmp:
-        src = os.path.join(tmp, "summary.hip")
-        with open(src, "w") as f:
-            f.write(jit._SUMMARY_TEMPLATE % {"init": init, "extern": ""})
-        flags = [f for f in jit.compile_flags() if f != "-shared"]
-        proc = subprocess.run([jit._hipcc()] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o",
-                                                        os.path.join(tmp, "summary.o")],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-        assert proc.returncode == 0, proc.stdout.decode()[-3000:]
-        so = os.path.join(tmp, "summary.so")
-        subprocess.run([jit._hipcc()] + jit.compile_flags() + [src, "-o", so], check=True)
-        import ctypes as C
-        unit = C.CDLL(so)
-        unit.clik_jit_summary_info.restype = C.c_longlong
-        lds = int(unit.clik_jit_summary_info(2))
-    for name, r in sorted(parse_resource_remarks(proc.stdout.decode()).items()):
+    res = jit.unit_resources(jit.unit_text(jit._SUMMARY_TEMPLATE, req.init, req.extern), req.init)
+    so, _ = jit.build_shape_library(req.init, template=jit._SUMMARY_TEMPLATE, extern=req.extern)      # (the shipped object)
+    unit = C.CDLL(so)
+    unit.clik_jit_summary_info.restype = C.c_longlong
+    lds = int(unit.clik_jit_summary_info(2))
+    for name, r in sorted(res.items()):
         short = "constraint_summary_combine_kernel" if "combine" in name else "constraint_summary_kernel"
         out.append("| `%s` | %d | %d | %d | %d | %d | %d |" % (
             short, r.get("VGPRs", 0), r.get("AGPRs", 0), r.get("TotalSGPRs", r.get("SGPRs", 0)), 0 if "combine" in name else lds,

@@ -11,7 +11,6 @@ variant and a replay is timed between two HIP events, `ROUNDS` interleaved round
 and minimum are reported.  `--write` puts the tables into profiles/function_batch.md.
 """
 import os
-import subprocess
 import sys
 import time
 
@@ -66,25 +65,16 @@ def interleaved(variants):
 
 def resources():
     """registers / LDS / scratch of the four test kernels from the compiler's remarks (no GPU needed)"""
-    from casclik_amd.build import parse_resource_remarks
-    import tempfile
     out = ["", "### The four test kernels (compiler remarks, gfx950)", "",
            "| function | inputs -> outputs (entries) | VGPRs | SGPRs | scratch | occupancy | LDS per block |", "|---|---|---|---|---|---|---|"]
-    with tempfile.TemporaryDirectory() as d:
-        for name in fc.NAMES:
-            fn = fc.get(name)
-            src = os.path.join(d, name + ".hip")
-            with open(src, "w") as f:
-                f.write(jit._FUNCTION_TEMPLATE % {"init": "", "extern": codegen.emit_function(fn)})
-            flags = [f for f in jit.compile_flags() if f != "-shared"]
-            p = subprocess.run([jit._hipcc()] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o",
-                                                         os.path.join(d, name + ".o")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-            (_, r), = parse_resource_remarks(p.stdout.decode()).items()
-            ins, outs = codegen.function_layout(fn)
-            slots = max([sum(a * b for a, b, _ in ins)] + [a * b for a, b, _ in outs])
-            out.append("| `%s` | %s -> %s | %d | %d | %d | %d | %d B |" % (
-                name, " + ".join(str(a * b) for a, b, _ in ins), " + ".join(str(a * b) for a, b, _ in outs), r["VGPRs"],
-                r["TotalSGPRs"], r["ScratchSize"], r["Occupancy"], 4 * 64 * 8 * slots))
+    for name in fc.NAMES:
+        fn = fc.get(name)
+        (_, r), = jit.unit_resources(jit.unit_text(jit._FUNCTION_TEMPLATE, "", codegen.emit_function(fn)), "").items()
+        ins, outs = codegen.function_layout(fn)
+        slots = max([sum(a * b for a, b, _ in ins)] + [a * b for a, b, _ in outs])
+        out.append("| `%s` | %s -> %s | %d | %d | %d | %d | %d B |" % (
+            name, " + ".join(str(a * b) for a, b, _ in ins), " + ".join(str(a * b) for a, b, _ in outs), r["VGPRs"],
+            r["TotalSGPRs"], r["ScratchSize"], r["Occupancy"], 4 * 64 * 8 * slots))
     return out
 
 

@@ -31,10 +31,9 @@ def units(only):
         yield name, what, text, meta
 
 
-def assembly(csrc, path, meta):
-    flags = [f for f in jit.compile_flags(meta.get("stamps", False), meta.get("flags", [])) if f != "-shared"]
-    flags = ["-I" + csrc if f == "-I" + jit.CSRC else f for f in flags] + jit.sched_flags(meta.get("_sched"))
-    cmd = [jit._hipcc()] + flags + ["--offload-device-only", "-S", "-x", "hip", path, "-o", "-"]
+def assembly(csrc, path, text, meta):
+    cmd = jit.unit_command(text, meta["init"], path, "-", meta.get("flags", []), meta.get("stamps", False), kind="asm",
+                           csrc=csrc, sched=meta["_sched"])
     proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     if proc.returncode != 0:
         raise RuntimeError("hipcc failed on %s against %s:\n%s" % (path, csrc, proc.stderr.decode("utf-8", "replace")[-3000:]))
@@ -95,7 +94,7 @@ def main():
         path = os.path.join(work, name + ".hip")
         with open(path, "w") as f:
             f.write(text)
-        return [kernels(assembly(os.path.abspath(d), path, meta)) for d in (a.old_csrc, a.new_csrc)]
+        return [kernels(assembly(d, path, text, meta)) for d in (a.old_csrc, a.new_csrc)]
 
     differ = 0
     with ThreadPoolExecutor(max_workers=a.jobs) as ex:
