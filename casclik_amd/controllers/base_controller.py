@@ -349,6 +349,26 @@ def converge_request(tol, max_ticks, min_step, input_var, m_tot):
     return converge_tolerances(tol, m_tot), int(max_ticks)
 
 
+def converge_group_request(group, B):
+    """``group`` of ``converge_batch`` as an int, checked on the host.  ValueError for anything but an int among 1, 2, 4,
+    8, 16, 32, 64 (bools and floats are refused as for ``max_ticks``) and for a batch of ``B`` instances that is not
+    whole groups."""
+    if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or int(group) not in (1, 2, 4, 8, 16, 32, 64):
+        raise ValueError("group must be one of 1, 2, 4, 8, 16, 32, 64, got %r" % (group,))
+    if int(B) % int(group) != 0:
+        raise ValueError("group=%d: the batch must be whole groups, got %d instances" % (group, B))
+    return int(group)
+
+
+def padded_seeds(S):
+    """Seeds per target of an ``ik_batch(first_hit=True)`` launch: ``S`` padded to the next power of two, the size of a
+    group of lanes.  ValueError for ``S > 64``: a group does not span two waves."""
+    S = int(S)
+    if S > 64:
+        raise ValueError("first_hit serves at most 64 seeds per target (a target's seeds share a wave), got %d" % S)
+    return 1 << (S - 1).bit_length() if S > 1 else 1
+
+
 def select_seeds(ticks, status, residual, tol, S):
     """Which of its ``S`` seeds serves each target of an ``ik_batch`` launch: a pure function of torch tensors, on any
     device.  ``ticks``, ``status`` ``[T * S]`` and ``residual`` ``[T * S, M_tot]`` are ``converge_batch``'s info of
@@ -406,6 +426,10 @@ class BaseController(object):
     # instance, dtype name); a width of 0 leaves the output out (None in the result, no record)
     _rollout_tail = ()
     _kernels = {}               # on-demand kernels asked for so far, what -> cache tag | False (``_create_handle`` resets it)
+    # the converging rollouts loaded so far, group -> (cache tag, attach function, its arguments) | False, and the group of
+    # the one attached (``_require_converge_kernel``; ``_create_handle`` resets both)
+    _converge_units = {}
+    _converge_group = None
 
     def __repr__(self):
         return self.controller_type + "<" + self.skill_spec.label + ">"
@@ -444,6 +468,7 @@ class BaseController(object):
         self._handle = handle
         self._setup_c = (cdesc, copts)      # (the on-demand kernels are instantiated later, at their first use)
         self._kernels = {}
+        self._converge_units, self._converge_group = {}, None
         return cdesc, copts
 
     def _want_jit(self):
@@ -514,6 +539,8 @@ class BaseController(object):
         and the library refuses the call (NotImplementedError): there is no chunked or host fallback.  A skill whose
         summary or summarising rollout does not fit the LDS of a compute unit, or would spill, is refused here with the
         figure."""
+        if what == "converge":
+            return self._require_converge_kernel(1)     # (the one unit with variants: which of them is attached matters)
         if self._kernels.get(what) is None and self._want_jit():
             from .. import jit
             cdesc, copts = self._setup_c
@@ -521,6 +548,29 @@ class BaseController(object):
                 tag = jit.attach_unit(self._lib, self._handle, self._kind, what, cdesc, copts,
                                       extern=self.descriptor.extern_source(), values=bool(self.value_kernel))
             self._kernels[what] = tag or False
+
+    def _require_converge_kernel(self, group=1):
+        """The converging rollout with the group rule for groups of ``group`` lanes (1: the default unit, whose tag
+        ``_kernels["converge"]`` is) attached to the handle: loaded at its first use as ``_require_kernel`` does it,
+        kept, and attached again whenever the last call used another.  A variant that cannot be had detaches what is
+        attached, so the library refuses the call (NotImplementedError) and no other variant runs in its place."""
+        if self._converge_group == group or not self._want_jit():   # (what the last call used: nothing to do)
+            return
+        from .. import jit
+        unit = self._converge_units.get(group)
+        with _torch().cuda.device(self._device):
+            if unit is None:
+                cdesc, copts = self._setup_c
+                unit = jit.load_unit(self._lib, self._handle, self._kind, "converge", cdesc, copts,
+                                     extern=self.descriptor.extern_source(), values=bool(self.value_kernel),
+                                     defines=jit.converge_group_defines(group)) or False
+                self._converge_units[group] = unit
+                if group == 1:
+                    self._kernels["converge"] = unit[0] if unit else False
+            if self._converge_group != group:
+                attach = jit.CONVERGE_UNITS["converge", self._kind]["attach"]
+                _capi.check(self._lib, getattr(self._lib, attach)(self._handle, *(unit[2] if unit else [None])))
+                self._converge_group = group
 
     def _device_times(self, time_vars):
         """times as a flat contiguous float64 tensor on the controller's device (one that already is, is used in
@@ -973,7 +1023,7 @@ class BaseController(object):
 
     # -- rollouts that run until each instance has converged ------------------------------------------------------
     def converge_batch(self, robot_var, input_var=None, tol=1e-6, max_ticks=1000, dt=0.008, max_speed=0.0,
-                       virtual_var=None, time_var=0.0, min_step=0.0):
+                       virtual_var=None, time_var=0.0, min_step=0.0, group=1):
         """Closed-loop inverse kinematics for a batch in ONE launch: every instance ticks (solve -> clamp(+-max_speed)
         -> ``q += dq * dt``, explicit Euler) with the time ``time_var`` and its target ``input_var [B, n_y]`` frozen,
         until it has converged or cannot go on; a wave of 64 instances leaves the loop when all of them have stopped.
@@ -990,14 +1040,23 @@ class BaseController(object):
         * 3 (ReactiveQPController) when the QP of tick r is infeasible, 2 when ``min_step > 0`` and ``max_j |dq_j| * dt
           <= min_step`` over the robot variables - the state stays as it was in both cases.
 
+        ``group = G`` (2, 4, 8, 16, 32 or 64; ``B`` a multiple of it) adds the group rule: instances ``[g G, (g + 1) G)``
+        are one group - the seeds of one target, say - and an instance that is still running behind the test of tick r
+        stops there with ``status`` 5 and ``ticks = r`` once an instance of its group has stopped with status 0, at this
+        test or an earlier one.  It keeps its state and the ``dist_i`` of that test.  An instance the test itself stops
+        at r keeps the status above, and a group none of whose instances reaches status 0 runs as without the rule.
+        So a group costs its wave the ticks of its first arrival, not of its slowest member.  The rule is compiled into
+        a kernel of its own per ``G``, built at its first use like the default one.
+
         Returns ``(q, dq, mode, info)``, with virtual variables ``(q, x, dq, dx, mode, info)`` (ReactiveQPController: the
         worst QP status met in place of ``mode``): the state at the stop, the velocity and mode of the last tick that was
         integrated (zeros and -1 when there was none), and ``info = {"ticks": int32 [B], "status": int32 [B], "residual":
         float64 [B, M_tot]}`` - the number of ticks integrated, the status above and the ``dist_i`` of the returned
         state.  For status 4 every component of the instance's rows of ``q``, ``dq`` and ``residual`` is NaN; no other
         instance changes.  Numpy when ``robot_var`` is numpy, device tensors otherwise; the same bits on every call and
-        in every batch.  ValueError for a bad ``tol`` (negative, NaN, wrong length), ``max_ticks < 0``, and a 3-D
-        ``input_var`` (targets are fixed here); NotImplementedError when no kernel could be instantiated for the skill,
+        in every batch (with ``group``: in every batch of whole groups).  ValueError for a bad ``tol`` (negative, NaN,
+        wrong length), ``max_ticks < 0``, a 3-D ``input_var`` (targets are fixed here), a ``group`` outside 1, 2, 4, 8, 16,
+        32, 64 and a ``B`` that is no multiple of it; NotImplementedError when no kernel could be instantiated for the skill,
         when its block does not fit the LDS of a compute unit or when its kernel would spill."""
         self._require_handle()
         torch = _torch()
@@ -1007,7 +1066,8 @@ class BaseController(object):
         Q, X, Y, B, was_np = self._batch_inputs(robot_var, virtual_var, input_var, clone=True)
         if B < 1:
             raise ValueError("converge_batch needs at least one instance")
-        dQ = torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
+        group = converge_group_request(group, B)
+        dQ =torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
         dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
         mode = torch.empty((B,), dtype=torch.int32, device=dev)
         info = {"ticks": torch.empty((B,), dtype=torch.int32, device=dev),
@@ -1015,7 +1075,7 @@ class BaseController(object):
                 "residual": torch.empty((B, m_tot), dtype=torch.float64, device=dev)}
         tol_dev = torch.from_numpy(tol_np).to(dev)
         tt, ttp = _capi.tterms_arg(d.time_terms(float(scalar_of(time_var))))
-        self._require_kernel("converge")
+        self._require_converge_kernel(group)
         extra = (None,) if self._kind == "qp" else ()       # (QP: slack, not returned)
         with torch.cuda.device(dev):
             rc = getattr(self._lib, "clik_%s_converge_batch" % self._kind)(
@@ -1026,13 +1086,22 @@ class BaseController(object):
         outs = (Q, X, dQ, dX, mode) if d.n_x > 0 else (Q, dQ, mode)
         return self._rollout_result(outs, info, was_np)
 
-    def ik_batch(self, input_var, seeds, **converge_kwargs):
+    def ik_batch(self, input_var, seeds, first_hit=False, **converge_kwargs):
         """Multi-seed inverse kinematics: ``T`` targets ``input_var [T, n_y]``, each started from ``S`` seeds - ``seeds
         [S, n_q]`` shared by all targets or ``[T, S, n_q]`` - in ONE ``converge_batch`` launch of ``T * S`` instances
         (instance ``t * S + s``); ``converge_kwargs`` are its other arguments.  Returns ``(q [T, n_q], info)``: per
         target the state and ``converge_batch``'s info of the seed ``select_seeds`` picks, and ``info["seed"]`` (int32
         ``[T]``) which one that was.  Numpy when ``seeds`` is numpy, device tensors otherwise.  For skills without
-        virtual variables (ValueError otherwise)."""
+        virtual variables (ValueError otherwise).
+
+        ``first_hit=True``: a target's first converged seed stops its other seeds (``converge_batch``'s ``group``), so
+        a target costs its wave the ticks of its best seed instead of ``max_ticks`` whenever one seed stalls.  The seeds
+        are padded to the next power of two ``P`` with copies of seed 0 and the launch has ``T * P`` instances in groups
+        of ``P``; at most 64 seeds (ValueError otherwise).  The seed picked and everything returned for it are what
+        ``first_hit=False`` returns: the seeds ``select_seeds`` can pick stop before the rule touches them, a stopped
+        seed (status 5) never wins against a converged one, and a copy of seed 0 ties with seed 0 and loses to its
+        lower index.  (The grouped kernel is another compilation of the same tick: the same integers, floats that agree
+        to rounding.)"""
         self._require_handle()
         torch = _torch()
         d, dev = self.descriptor, self._device
@@ -1040,6 +1109,8 @@ class BaseController(object):
             raise ValueError("ik_batch serves skills without virtual variables")
         if "robot_var" in converge_kwargs:
             raise ValueError("ik_batch starts from seeds, not from robot_var")
+        if first_hit and "group" in converge_kwargs:
+            raise ValueError("first_hit chooses the group itself (the padded number of seeds): do not pass group")
         was_np = not isinstance(seeds, torch.Tensor)
         sd = (seeds if not was_np else torch.from_numpy(np.ascontiguousarray(np.asarray(seeds, dtype=np.float64)))).to(
             device=dev, dtype=torch.float64)
@@ -1049,13 +1120,20 @@ class BaseController(object):
             sd = sd.unsqueeze(0).expand(T, -1, -1)
         if sd.dim() != 3 or sd.shape[0] != T or sd.shape[2] != d.n_q or sd.shape[1] < 1:
             raise ValueError("seeds must be [S, %d] or [%d, S, %d], got shape %s" % (d.n_q, T, d.n_q, tuple(sd.shape)))
-        S = sd.shape[1]
+        S = n_seeds = sd.shape[1]
+        if first_hit:
+            S = padded_seeds(n_seeds)
+            if S > n_seeds:
+                sd = torch.cat([sd, sd[:, :1].expand(T, S - n_seeds, d.n_q)], dim=1)
+            converge_kwargs = dict(converge_kwargs, group=S)
         Q0 = sd.reshape(T * S, d.n_q).contiguous()
         Ys = Y.unsqueeze(1).expand(T, S, d.n_y).reshape(T * S, d.n_y).contiguous()
         tol = converge_kwargs.get("tol", 1e-6)
         q, _, _, info = self.converge_batch(Q0, Ys, **converge_kwargs)
         m_tot = info["residual"].shape[1]
         pick = select_seeds(info["ticks"], info["status"], info["residual"], converge_tolerances(tol, m_tot), S)
+        if S > n_seeds:
+            assert bool((pick < n_seeds).all()), "a copy of seed 0 was picked ahead of seed 0"
         at = torch.arange(T, device=dev) * S + pick
         out = {k: v.index_select(0, at) for k, v in info.items()}
         out["seed"] = pick.to(torch.int32)

@@ -26,7 +26,18 @@
 namespace clik {
 
 // status of an instance (include/clik.h: CLIK_CONVERGE_*)
-constexpr int kConvOk = 0, kConvMaxTicks = 1, kConvStalled = 2, kConvInfeasible = 3, kConvNonFinite = 4;
+constexpr int kConvOk = 0, kConvMaxTicks = 1, kConvStalled = 2, kConvInfeasible = 3, kConvNonFinite = 4, kConvCancelled = 5;
+
+// The group rule (include/clik.h), compiled in: the lanes [g G, (g + 1) G) of a wave are one group - the seeds of one
+// target of a multi-seed launch -, and a lane that is still active behind the stop test of tick r stops there with
+// kConvCancelled once a lane of its group has stopped with kConvOk.  G divides 64 and the host asks for B % G == 0, so a
+// group never spans two waves and is valid as a whole or not at all.  G == 1: the kernels as they are without the rule.
+#ifndef CLIK_CONVERGE_GROUP
+#define CLIK_CONVERGE_GROUP 1
+#endif
+constexpr int kConvGroup = CLIK_CONVERGE_GROUP;
+static_assert(kConvGroup == 1 || kConvGroup == 2 || kConvGroup == 4 || kConvGroup == 8 || kConvGroup == 16 ||
+              kConvGroup == 32 || kConvGroup == 64, "CLIK_CONVERGE_GROUP is one of 1, 2, 4, 8, 16, 32, 64");
 
 // what a launch reads and writes beside the state (device pointers)
 struct ConvergeArgs {
@@ -115,6 +126,25 @@ __device__ __forceinline__ void converge_test(const Img<SD>* __restrict__ S, con
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// the group rule of tick r, right behind its stop test: one ballot of the lanes that have stopped with kConvOk (a lane
+// past the end of the batch starts stopped with that status and is no winner: `valid`), the lane's own group cut out of
+// it.  A lane the test itself stopped at r is not active and keeps its status; a cancelled lane keeps its state and the
+// dist values of this test.  Called by all 64 lanes (the loops around it branch on ballots only).
+template <int G>
+__device__ __forceinline__ void converge_group(const bool valid, const int lane, const int r, bool& active, int& status,
+                                               int& ticks)
+{
+    if constexpr (G > 1) {
+        constexpr unsigned long long mask = G == 64 ? ~0ull : (1ull << (G & 63)) - 1ull;
+        const unsigned long long won = __ballot(valid && !active && status == kConvOk);
+        if (active && ((won >> (lane & ~(G - 1))) & mask) != 0ull) {
+            active = false;
+            status = kConvCancelled;
+            ticks = r;
+        }
+    }
+}
+
 // the lane's [MT] residuals, after the loop (NaN by bits for an instance that stopped on a non-finite value)
 template <const ShapeDesc& SD>
 __device__ __forceinline__ void converge_store(const ConvergeArgs& ca, const long long inst, const int ticks,
@@ -192,6 +222,7 @@ __global__ __launch_bounds__(WV * WAVE) CLIK_ROLL_ATTR void pinv_converge_static
     for (int r = 0; __ballot(active) != 0ull; ++r) {
         asm volatile("" ::: "memory");      // (keeps the image reads inside the loop, see pinv_rollout_static_body)
         converge_test<SD>(S, tk, z, ysl, tols, lane, r, ca.max_ticks, dist, active, status, ticks);
+        converge_group<kConvGroup>(valid, lane, r, active, status, ticks);
         if (__ballot(active) == 0ull) break;
         double vt[N];
         int mt = -1;
@@ -250,6 +281,9 @@ inline hipError_t launch_converge_static(const LaunchArgs& a, const TickArgs& tk
         if (B < 1 || ca.max_ticks < 0 || ca.tol == nullptr || ca.ticks == nullptr || ca.status == nullptr ||
             ca.residual == nullptr)
             return hipErrorInvalidValue;
+        if constexpr (kConvGroup > 1) {
+            if (B % kConvGroup != 0) return hipErrorInvalidValue;       // (a group is whole: the host checks it first)
+        }
         if (SD.n_x != 0 && (a.roll_x == nullptr || a.roll_dx == nullptr)) return hipErrorInvalidValue;
         constexpr int WV = pinv_converge_waves<SD>();
         const long long per_block = (long long)WV * WAVE;
@@ -331,6 +365,7 @@ __global__ __launch_bounds__(WAVE) void qp_converge_static_kernel(
     for (int r = 0; __ballot(active) != 0ull; ++r) {
         asm volatile("" ::: "memory");      // (keeps the image reads inside the loop, see pinv_rollout_static_body)
         converge_test<SD>(S, tk, z, ysl, tols, lane, r, ca.max_ticks, dist, active, status, ticks);
+        converge_group<kConvGroup>(valid, lane, r, active, status, ticks);
         if (__ballot(active) == 0ull) break;
         double vt[N], st_sl[LY::NSA];
         const int st = qp_tick_static<SD>(S, T, tk, z, ysl, lane, active, slots, vt, st_sl, &hot, r > 0);
@@ -400,6 +435,9 @@ inline hipError_t launch_qp_converge_static(const void* d_img, const TickArgs& t
         if (B < 1 || ca.max_ticks < 0 || ca.tol == nullptr || ca.ticks == nullptr || ca.status == nullptr ||
             ca.residual == nullptr)
             return hipErrorInvalidValue;
+        if constexpr (kConvGroup > 1) {
+            if (B % kConvGroup != 0) return hipErrorInvalidValue;       // (a group is whole: the host checks it first)
+        }
         if (SD.n_x != 0 && (x == nullptr || dx == nullptr)) return hipErrorInvalidValue;
         const long long blocks = (B + WAVE - 1) / WAVE;
         if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -411,7 +449,7 @@ inline hipError_t launch_qp_converge_static(const void* d_img, const TickArgs& t
 
 // what a caller may ask about the instantiation (clik_jit_converge_info): 0 rows, 1 SetConstraint rows, 2 LDS bytes of a
 // block, 3 fits the LDS of a CU, 4 waves of a block, 5 bytes of scratch per lane as the loaded code object states them
-// (-1: no device to ask)
+// (-1: no device to ask), 6 the group size the unit was compiled with (CLIK_CONVERGE_GROUP)
 template <const ShapeDesc& SD>
 inline long long converge_info(int what)
 {
@@ -424,7 +462,7 @@ inline long long converge_info(int what)
         }
     }
     return what == 0 ? LY::MT : what == 1 ? LY::MS : what == 2 ? (long long)converge_lds_bytes<SD>()
-         : what == 3 ? (converge_fits<SD>() ? 1 : 0) : what == 4 ? converge_waves<SD>() : -1;
+         : what == 3 ? (converge_fits<SD>() ? 1 : 0) : what == 4 ? converge_waves<SD>() : what == 6 ? kConvGroup : -1;
 }
 
 }  // namespace clik

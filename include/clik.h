@@ -498,12 +498,25 @@ int clik_pinv_rollout_batch_sum(const clik_pinv* h, int64_t B, int32_t n_ticks, 
  * q, x, dq, dx and residual rows is a quiet NaN; no other instance changes.  One lane owns one instance: the same bits
  * on every call and in every batch.  CLIK_EINVAL for B < 1, max_ticks < 0, a NULL tol or a NULL output;
  * CLIK_EUNSUPPORTED for a handle without an attached kernel (one served by the built-in dynamic-shape kernel has
- * none).                                                                                                              */
+ * none).
+ * The group rule is a property of the attached kernel (clik_converge.hpp compiled with -DCLIK_CONVERGE_GROUP=G, G one
+ * of 2, 4, 8, 16, 32, 64; jit.py builds one per G and converge_batch(..., group=G) attaches it - same entry, same
+ * signature).  Instances [g G, (g + 1) G) are one group, e.g. the seeds of one target; B must be a multiple of G (the
+ * launch refuses any other), so a group lies in one wave.  Between steps 4 and 5 of tick r:
+ *   4a. an instance that is still running, and whose group holds an instance that has stopped with CLIK_CONVERGE_OK at
+ *       this tick's test or an earlier one, stops with CLIK_CONVERGE_CANCELLED and ticks = r; it keeps its state and
+ *       the dist_i of this test.
+ * An instance steps 2 - 4 stop at r keeps that status, and a cancelled instance never reaches the solve of tick r.  A
+ * group none of whose instances reaches CLIK_CONVERGE_OK runs as without the rule, and so does every instance up to the
+ * test at which the first of its group arrives: the instance with the fewest ticks among a group's CLIK_CONVERGE_OK
+ * instances is the same with and without the rule, with the same outputs.  A kernel compiled without the define (G = 1)
+ * never reports CLIK_CONVERGE_CANCELLED.                                                                             */
 #define CLIK_CONVERGE_OK          0   /* every row within its tolerance                      */
 #define CLIK_CONVERGE_MAX_TICKS   1   /* max_ticks ticks integrated, some row still outside  */
 #define CLIK_CONVERGE_STALLED     2   /* a step of at most min_step                          */
 #define CLIK_CONVERGE_INFEASIBLE  3   /* (QP) the tick's QP is infeasible                    */
 #define CLIK_CONVERGE_NONFINITE   4   /* a constraint value is NaN or infinite               */
+#define CLIK_CONVERGE_CANCELLED   5   /* (group rule) an instance of its group has converged */
 int clik_pinv_attach_converge_kernel(clik_pinv* h, void* converge_fn);
 int clik_pinv_converge_batch(const clik_pinv* h, int64_t B, int32_t max_ticks, double dt, double max_speed,
                              double min_step, const double* tterms, double* q, double* x, const double* y,

@@ -8,6 +8,11 @@ Timing: HIP events around the call on device tensors, `WARMUP` calls first, the 
 `SETS` copies of the inputs and every call gets new state and output tensors.  What (a) should cost is derived from the
 run's own `ticks`: w = mean over waves of (largest ticks in the wave + 1) / (max_ticks + 1); (a) <= 1.15 w (b) is the
 expectation.  `--out` writes the tables (markdown) to a file as well.
+    python tools/converge_bench.py --ik [T ...  default 1024 8192] [--out FILE]
+Multi-seed IK instead: `ik_batch(first_hit=True)` - a target's first converged seed stops its other seeds - against
+`ik_batch()`, the single-pose skill, T targets x 16 seeds of which about a quarter run out of ticks (the achieved share is
+printed), `max_ticks` = 40, several times the median arrival.  The expectation beside the ratio: the ticks the launch lasts
+with the rule over those without it, from the two launches' own `ticks` (`launch_cost`).
 """
 import ctypes as C
 import os
@@ -104,6 +109,113 @@ def measure(name, ctrl, tol, B):
     return out
 
 
+IK_SEEDS, IK_FAR, IK_TICKS, IK_TOL, SIMDS = 16, 7, 40, 1e-5, 1024
+
+
+def ik_inputs(fk, T, seed):
+    """(targets [T, 7], seeds [T, 16, 7]): UNIQUE distinct targets - the tool pose at a state inside half the joint range -
+    drawn with replacement, each with its own seeds around that state: nine at 0.003 .. 0.1 rad (a standard deviation
+    per joint), which arrive, and IK_FAR = seven at 1 .. 3.2 rad (clipped to the joint range), about half of which cross a
+    singularity on their way and are not there after IK_TICKS ticks (the oracle's host loop on 24 targets: 21 % of all
+    seeds run out of ticks, every target's first arrival after 8 .. 10 ticks)"""
+    rng = np.random.default_rng(seed)
+    lo, hi = np.asarray(fk["lower"], float), np.asarray(fk["upper"], float)
+    star = rng.uniform(0.5 * lo, 0.5 * hi, size=(UNIQUE, lo.size))
+    Y = np.zeros((UNIQUE, 7))
+    for b in range(UNIQUE):
+        M = fk["chain"].fk_numeric(star[b])
+        Y[b, :3], Y[b, 3:] = M[:3, 3], skills.quat_from_matrix(M[:3, :3])
+    scale = np.concatenate([10.0 ** np.linspace(-2.5, -1.0, IK_SEEDS - IK_FAR), 10.0 ** np.linspace(0.0, 0.5, IK_FAR)])
+    seeds = star[:, None, :] + scale[None, :, None] * rng.normal(size=(UNIQUE, IK_SEEDS, lo.size))
+    seeds = np.clip(seeds, lo, hi)
+    pick = rng.integers(0, UNIQUE, T)
+    return Y[pick], seeds[pick]
+
+
+def launch_cost(ticks):
+    """what a launch with these tick counts costs in ticks, as w is derived above: a wave runs the tests 0 .. its largest
+    `ticks`; with no more waves than SIMDs the launch lasts as long as its slowest wave, with more a SIMD runs its waves
+    (taken round-robin) one after the other and the launch lasts as long as the slowest SIMD"""
+    waves = np.pad(ticks, (0, -len(ticks) % 64)).reshape(-1, 64).max(axis=1) + 1.0
+    per_simd = np.pad(waves, (0, -len(waves) % SIMDS)).reshape(-1, SIMDS).sum(axis=0)
+    return float(per_simd.max()), len(waves)
+
+
+def measure_ik(ctrl, T):
+    fk = skills.iiwa()
+    sets = []
+    for k in range(SETS):
+        Y, seeds = ik_inputs(fk, T, seed=40 + k)
+        sets.append((torch.from_numpy(Y).cuda(), torch.from_numpy(seeds).cuda()))
+    kw = dict(tol=IK_TOL, max_ticks=IK_TICKS, dt=DT)
+    # the tick counts of input set 0 with and without the rule, from the launches ik_batch makes
+    Y, seeds = sets[0]
+    Q0 = seeds.reshape(T * IK_SEEDS, -1).contiguous()
+    Ys = Y.unsqueeze(1).expand(T, IK_SEEDS, Y.shape[1]).reshape(T * IK_SEEDS, -1).contiguous()
+    plain = ctrl.converge_batch(Q0, Ys, **kw)[3]
+    grouped = ctrl.converge_batch(Q0, Ys, group=IK_SEEDS, **kw)[3]
+    pt, ps = plain["ticks"].cpu().numpy(), plain["status"].cpu().numpy()
+    gt, gs = grouped["ticks"].cpu().numpy(), grouped["status"].cpu().numpy()
+    ok = (ps == 0).reshape(T, IK_SEEDS)
+    arrival = np.where(ok, pt.reshape(T, IK_SEEDS), IK_TICKS + 1).min(axis=1)
+    cost_p, n_waves = launch_cost(pt)
+    cost_g, _ = launch_cost(gt)
+    one, two = ctrl.ik_batch(Y, seeds, **kw), ctrl.ik_batch(Y, seeds, first_hit=True, **kw)
+    same = all(bool((one[1][k] == two[1][k]).all()) for k in ("seed", "ticks", "status"))
+    dq = float((one[0] - two[0]).abs().max())
+
+    def a(k):
+        return ctrl.ik_batch(*sets[k % SETS], first_hit=True, **kw)
+
+    def b(k):
+        return ctrl.ik_batch(*sets[k % SETS], **kw)
+
+    # the launch alone - `converge_batch` on the T x 16 instances with and without the rule -, apart from what `ik_batch`
+    # does around it on the host and in torch kernels (expanding the targets, `select_seeds`, gathering the picks)
+    flat = [(s.reshape(T * IK_SEEDS, -1).contiguous(),
+             y.unsqueeze(1).expand(T, IK_SEEDS, y.shape[1]).reshape(T * IK_SEEDS, -1).contiguous()) for y, s in sets]
+
+    def c(k):
+        return ctrl.converge_batch(*flat[k % SETS], group=IK_SEEDS, **kw)
+
+    def d(k):
+        return ctrl.converge_batch(*flat[k % SETS], **kw)
+
+    ta, tb, tc, td = timed(a), timed(b), timed(c), timed(d)
+    out = ["", "### multi-seed IK, single pose (iiwa): %d targets x %d seeds = %d instances, max_ticks = %d" % (
+               T, IK_SEEDS, T * IK_SEEDS, IK_TICKS), "",
+           "| path | device time, median of %d (min .. max), us |" % REPS, "|---|---|",
+           "| (a) `ik_batch(first_hit=True)` | %.1f (%.1f .. %.1f) |" % ta,
+           "| (b) `ik_batch()` | %.1f (%.1f .. %.1f) |" % tb,
+           "| (c) the launch alone: `converge_batch(group=%d)` | %.1f (%.1f .. %.1f) |" % ((IK_SEEDS,) + tc),
+           "| (d) the launch alone: `converge_batch()` | %.1f (%.1f .. %.1f) |" % td, "",
+           "(a) / (b) = %.4f, (c) / (d) = %.4f; expected from the tick counts of input set 0: %.4f (a launch of %d waves "
+           "lasts %.0f ticks with the rule, %.0f without)" % (ta[0] / tb[0], tc[0] / td[0], cost_g / cost_p, n_waves,
+                                                              cost_g, cost_p),
+           "", "seeds out of ticks without the rule: %.1f %% (status 1: %d of %d); targets with an arrival: %d of %d, "
+           "median first arrival %.0f ticks, latest %d; seeds cancelled with the rule: %.1f %%" % (
+               100.0 * (ps == 1).mean(), (ps == 1).sum(), ps.size, ok.any(axis=1).sum(), T,
+               np.median(arrival[ok.any(axis=1)]), arrival[ok.any(axis=1)].max(), 100.0 * (gs == 5).mean()),
+           "largest ticks per wave, mean: %.1f with the rule, %.1f without; same seed, ticks and status from both paths: "
+           "%s, max |q(a) - q(b)| = %.2e" % (
+               np.pad(gt, (0, -len(gt) % 64)).reshape(-1, 64).max(axis=1).mean(),
+               np.pad(pt, (0, -len(pt) % 64)).reshape(-1, 64).max(axis=1).mean(), same, dq)]
+    print("\n".join(out), flush=True)
+    return out
+
+
+def main_ik():
+    """`--ik`: `ik_batch(first_hit=True)` against `ik_batch()`, the single-pose skill, T x 16 seeds (default T = 1024 8192)"""
+    ctrl = cc.PseudoInverseController(skill_spec=skills.pose_skill(skills.iiwa()))
+    ctrl.setup_problem_functions()
+    text = []
+    for T in [int(a) for a in sys.argv[1:] if a.isdigit()] or [1024, 8192]:
+        text += measure_ik(ctrl, T)
+    if OUT:
+        with open(OUT, "w") as f:
+            f.write("\n".join(text) + "\n")
+
+
 def main():
     fk = skills.iiwa()
     text = []
@@ -126,4 +238,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main_ik() if "--ik" in sys.argv else main()

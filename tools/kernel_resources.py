@@ -6,7 +6,8 @@ remarks (no GPU needed).      python tools/kernel_resources.py [stack|pose|qp] [
 --rollsum: the two summarising rollouts of that skill (jit._ROLLSUM_TEMPLATE / _QP_ROLLSUM_TEMPLATE: image-reading, Euler and
 Runge-Kutta; their LDS is dynamic - tools/rollout_summary_bench.py prints the launcher's figure).
 --converge: the converging rollout of that skill (jit._CONVERGE_TEMPLATE / _QP_CONVERGE_TEMPLATE: pinv_converge_static_kernel /
-qp_converge_static_kernel, image-reading, Euler; LDS dynamic - tools/converge_bench.py prints the launcher's figure)."""
+qp_converge_static_kernel, image-reading, Euler; LDS dynamic - tools/converge_bench.py prints the launcher's figure);
+--converge=G: the same unit with the group rule for groups of G lanes (-DCLIK_CONVERGE_GROUP=G, G in 2 .. 64)."""
 import os
 import subprocess
 import sys
@@ -42,8 +43,11 @@ if "--summary" in sys.argv:
     template, words, defines = jit._SUMMARY_TEMPLATE, None, ()
 if "--rollsum" in sys.argv:
     template, words, defines = jit.UNITS["rollsum", req.kind]["template"], None, ()
-if "--converge" in sys.argv:
-    template, words, defines = jit.CONVERGE_UNITS["converge", req.kind]["template"], None, ()
+group = [a for a in sys.argv[2:] if a == "--converge" or a.startswith("--converge=")]
+if group:
+    # (--converge=G: the unit with the group rule for groups of G lanes, as converge_batch(..., group=G) asks for it)
+    template, words = jit.CONVERGE_UNITS["converge", req.kind]["template"], None
+    defines = jit.converge_group_defines(int(group[-1].split("=", 1)[1]) if "=" in group[-1] else 1)
 text = jit.unit_text(template, req.init, req.extern, words)
 # (the scheduling strategy the shipped object is compiled with, casclik_amd/jit.py::sched_strategy - unless one is given)
 how = dict(extra=defines, csrc=csrc, more=flags, sched=None if any("sched-strategy" in f for f in flags) else "unit")
