@@ -360,6 +360,34 @@ def converge_group_request(group, B):
     return int(group)
 
 
+def velocity_feedback_request(fb, n_q, n_x, n_y):
+    """``options["velocity_feedback"]`` checked against a lowered skill (``n_q`` robot, ``n_x`` virtual variables, ``n_y``
+    entries of ``input_var``): the map as a tuple of ints, one per state - robot variables first -, entry j the index
+    into ``input_var`` that the next tick of an on-device loop reads the velocity of state j in, -1 for none.  None for no
+    option (None) and for a map that feeds nothing.  ValueError for a skill without ``input_var``, a wrong length, an
+    entry that is no int in ``[-1, n_y)`` and an ``input_var`` index named twice.  No device is needed."""
+    if fb is None:
+        return None
+    try:
+        entries = list(fb.tolist() if hasattr(fb, "tolist") else fb)
+    except TypeError:
+        raise ValueError("options['velocity_feedback'] must be a sequence of ints, got %r" % (fb,))
+    if n_y <= 0:
+        raise ValueError("options['velocity_feedback'] needs a skill with input_var: the velocities are fed into it")
+    if len(entries) != n_q + n_x:
+        raise ValueError("options['velocity_feedback'] must have %d entries (%d robot and %d virtual variables), got %d"
+                         % (n_q + n_x, n_q, n_x, len(entries)))
+    for j, k in enumerate(entries):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not -1 <= int(k) < n_y:
+            raise ValueError("options['velocity_feedback'][%d] must be an int in [-1, %d), got %r" % (j, n_y, k))
+    entries = tuple(int(k) for k in entries)
+    named = [k for k in entries if k >= 0]
+    if len(set(named)) != len(named):
+        raise ValueError("options['velocity_feedback'] names input_var[%d] twice"
+                         % next(k for k in named if named.count(k) > 1))
+    return entries if named else None
+
+
 def padded_seeds(S):
     """Seeds per target of an ``ik_batch(first_hit=True)`` launch: ``S`` padded to the next power of two, the size of a
     group of lanes.  ValueError for ``S > 64``: a group does not span two waves."""
@@ -430,6 +458,7 @@ class BaseController(object):
     # the one attached (``_require_converge_kernel``; ``_create_handle`` resets both)
     _converge_units = {}
     _converge_group = None
+    _feedback = None            # options["velocity_feedback"] as ``velocity_feedback_request`` returns it (set-up)
 
     def __repr__(self):
         return self.controller_type + "<" + self.skill_spec.label + ">"
@@ -458,6 +487,7 @@ class BaseController(object):
         self._release()
         self._lib = _capi.load_library()
         self.descriptor = lower_skill(self.skill_spec)
+        self._setup_velocity_feedback()     # (checked before anything is made on the device)
         cdesc = _capi.desc_to_c(self.descriptor)
         copts = self._c_options(self.descriptor)
         self._device = device_of(self.options.get("device"))
@@ -525,6 +555,29 @@ class BaseController(object):
                 "slot(s) (jit disabled, or hipcc missing and nothing cached)" % self.descriptor.n_tslots)
         self._kernels["time"] = tag
 
+    # -- velocity feedback --------------------------------------------------------------------------------------
+    def _setup_velocity_feedback(self):
+        """``options["velocity_feedback"] = fb`` (default None), read at set-up and checked there
+        (``velocity_feedback_request``): ``fb[j]`` is the index into ``input_var`` in which tick k + 1 of an on-device
+        loop - ``rollout_batch`` in all its forms, ``converge_batch``, ``ik_batch`` - reads the velocity of state j
+        (robot variables, then virtual ones) that tick k was integrated with; tick 0 reads what the caller gave.  The map
+        is compiled into variants of the lane-per-instance kernels, built at their first use; ``solve_batch``,
+        ``solve`` and the resident ticks fed by a producer do not change."""
+        d = self.descriptor
+        self._feedback = velocity_feedback_request(self.options.get("velocity_feedback"), d.n_q, d.n_x, d.n_y)
+
+    def _feedback_defines(self):
+        from .. import jit
+        return jit.velocity_feedback_defines(self._feedback)
+
+    def _require_feedback_served(self, tag, what):
+        """With the velocity feedback a launch has no other kernel to run on: refuse here, saying so."""
+        if self._feedback is not None and not tag:
+            raise NotImplementedError(
+                "options['velocity_feedback'] is set, but no %s with the feedback compiled in could be instantiated for "
+                "this skill: only the built-in kernels serve this handle (jit disabled, hipcc missing and nothing cached, "
+                "or a skill outside the shape-specialised family), and they feed nothing back" % what)
+
     @property
     def _time_kernel(self):
         """cache tag of the attached time kernel (``options["time_on_device"]``), or None"""
@@ -545,15 +598,21 @@ class BaseController(object):
             from .. import jit
             cdesc, copts = self._setup_c
             with _torch().cuda.device(self._device):
+                # (the rollouts of a controller with the velocity feedback are the variants with its map compiled in)
                 tag = jit.attach_unit(self._lib, self._handle, self._kind, what, cdesc, copts,
-                                      extern=self.descriptor.extern_source(), values=bool(self.value_kernel))
+                                      extern=self.descriptor.extern_source(), values=bool(self.value_kernel),
+                                      defines=self._feedback_defines() if what in ("rec", "rollsum") else ())
             self._kernels[what] = tag or False
+        if what in ("rec", "rollsum"):
+            self._require_feedback_served(self._kernels.get(what), "rollout")
 
     def _require_converge_kernel(self, group=1):
         """The converging rollout with the group rule for groups of ``group`` lanes (1: the default unit, whose tag
         ``_kernels["converge"]`` is) attached to the handle: loaded at its first use as ``_require_kernel`` does it,
         kept, and attached again whenever the last call used another.  A variant that cannot be had detaches what is
         attached, so the library refuses the call (NotImplementedError) and no other variant runs in its place."""
+        if not self._want_jit():
+            self._require_feedback_served(None, "converging rollout")
         if self._converge_group == group or not self._want_jit():   # (what the last call used: nothing to do)
             return
         from .. import jit
@@ -563,7 +622,7 @@ class BaseController(object):
                 cdesc, copts = self._setup_c
                 unit = jit.load_unit(self._lib, self._handle, self._kind, "converge", cdesc, copts,
                                      extern=self.descriptor.extern_source(), values=bool(self.value_kernel),
-                                     defines=jit.converge_group_defines(group)) or False
+                                     defines=jit.converge_group_defines(group) + self._feedback_defines()) or False
                 self._converge_units[group] = unit
                 if group == 1:
                     self._kernels["converge"] = unit[0] if unit else False
@@ -571,6 +630,7 @@ class BaseController(object):
                 attach = jit.CONVERGE_UNITS["converge", self._kind]["attach"]
                 _capi.check(self._lib, getattr(self._lib, attach)(self._handle, *(unit[2] if unit else [None])))
                 self._converge_group = group
+        self._require_feedback_served(unit, "converging rollout")
 
     def _device_times(self, time_vars):
         """times as a flat contiguous float64 tensor on the controller's device (one that already is, is used in
@@ -799,7 +859,15 @@ class BaseController(object):
 
         With ``options["time_on_device"]`` the launch goes through ``clik_*_rollout_batch_dev``: the time terms of all
         ticks and stages are computed on the device from ``time_vars``, which may be a tensor on the controller's
-        device (used in place, no host synchronisation)."""
+        device (used in place, no host synchronisation).
+
+        With ``options["velocity_feedback"] = fb`` tick k + 1 reads in ``input_var[:, fb[j]]`` the velocity of state j
+        that tick k was integrated with - what record k of ``record_every=1`` holds in ``dq`` / ``dx``: after the clamp,
+        with ``"rk4"`` the combined rate, read by all four stages - and tick 0 what the caller gave; a NaN is fed like
+        any other value.  With a 3-D ``input_var`` tick i takes its other entries from record i, and the fed entries of
+        the records ``i >= 1`` are ignored.  A launch of ``n1 + n2`` ticks is a launch of ``n1`` followed by one of
+        ``n2`` whose fed entries are the first one's ``dq`` / ``dx``.  Such a launch uses the lane-per-instance kernel
+        at every batch size; NotImplementedError for a handle that only the built-in kernels serve."""
         self._require_handle()
         torch = _torch()
         d, dev = self.descriptor, self._device
@@ -822,11 +890,17 @@ class BaseController(object):
                 ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX), *map(ptr, last), current_stream(dev))
         # (without records or per-tick targets: 0, 0 and NULL for every record)
         r = rec or {}
-        rec_args = (y_per_tick, int(record_every or 0)) + tuple(
+        every = int(record_every or 0)
+        if self._feedback is not None and dev_times and not every and not y_per_tick:
+            # (clik_*_rollout_batch_dev hands a launch without records and per-tick targets to the plain kernels, which
+            # feed nothing: ask for a record behind the last tick - none is written, and the recording lane kernel runs)
+            every = n_ticks + 1
+        rec_args = (y_per_tick, every) + tuple(
             ptr(r.get(name)) for name in ["q", "dq", "x", "dx"] + [name for name, _, _ in tail])
         entry = lambda suffix: getattr(self._lib, "clik_%s_rollout_batch_%s" % (self._kind, suffix))     # noqa: E731
         summ = None
-        plain = rec is None and not y_per_tick
+        # (with the velocity feedback every launch is the recording lane kernel's, with or without records)
+        plain = rec is None and not y_per_tick and self._feedback is None
         if want_sum:
             # (records, per-tick targets and the summary in ONE launch of the summarising lane kernel)
             tol_dev, summ = self._summary_out(tol, B)
@@ -1057,7 +1131,11 @@ class BaseController(object):
         in every batch (with ``group``: in every batch of whole groups).  ValueError for a bad ``tol`` (negative, NaN,
         wrong length), ``max_ticks < 0``, a 3-D ``input_var`` (targets are fixed here), a ``group`` outside 1, 2, 4, 8, 16,
         32, 64 and a ``B`` that is no multiple of it; NotImplementedError when no kernel could be instantiated for the skill,
-        when its block does not fit the LDS of a compute unit or when its kernel would spill."""
+        when its block does not fit the LDS of a compute unit or when its kernel would spill.
+
+        With ``options["velocity_feedback"]`` a tick that is integrated feeds its velocity to the instance's next tick
+        (``rollout_batch`` has the rule); a stopped instance keeps its entries, and a stalled or infeasible tick feeds
+        nothing.  ``group`` combines freely with it."""
         self._require_handle()
         torch = _torch()
         d, dev = self.descriptor, self._device

@@ -351,6 +351,11 @@ class PseudoInverseController(BaseController):
         D = int(ring_depth)
         if D < 1:
             raise ValueError("ring_depth must be at least 1")
+        if self._feedback is not None and integrate_dt > 0.0:
+            raise NotImplementedError(
+                "options['velocity_feedback'] has no resident form: resident_start(integrate_dt > 0) keeps the state in "
+                "the kernel and would feed nothing back (resident ticks fed by a producer are unchanged: the caller "
+                "owns input_var there)")
         if not isinstance(robot_var, torch.Tensor) or not robot_var.is_cuda:
             raise ValueError("resident ticks: robot_var must be a device tensor")
         if D > 1:

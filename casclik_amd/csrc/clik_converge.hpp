@@ -240,6 +240,8 @@ __global__ __launch_bounds__(WV * WAVE) CLIK_ROLL_ATTR void pinv_converge_static
                 vout[j] = vt[j];
                 z[j] = fma(vt[j], ca.dt, z[j]);
             }
+            // (velocity feedback: a tick that was integrated, and no other, feeds the next; a stopped lane keeps its row)
+            if constexpr (kVelFeedbackN > 0) velocity_feed<SD>(vt, 0u, ys + lane * NY);
         }
     }
     const unsigned nan_hi = (status == kConvNonFinite) ? 0x7ff80000u : 0u;
@@ -388,6 +390,8 @@ __global__ __launch_bounds__(WAVE) void qp_converge_static_kernel(
                 v[j] = vt[j];
                 z[j] = fma(vt[j], ca.dt, z[j]);
             }
+            // (velocity feedback: a tick that was integrated, and no other, feeds the next; a stopped lane keeps its row)
+            if constexpr (kVelFeedbackN > 0) velocity_feed<SD>(vt, 0u, ys + lane * NY);
 #pragma unroll
             for (int k = 0; k < LY::NSA; ++k) sl[k] = st_sl[k];
         }
@@ -449,11 +453,13 @@ inline hipError_t launch_qp_converge_static(const void* d_img, const TickArgs& t
 
 // what a caller may ask about the instantiation (clik_jit_converge_info): 0 rows, 1 SetConstraint rows, 2 LDS bytes of a
 // block, 3 fits the LDS of a CU, 4 waves of a block, 5 bytes of scratch per lane as the loaded code object states them
-// (-1: no device to ask), 6 the group size the unit was compiled with (CLIK_CONVERGE_GROUP)
+// (-1: no device to ask), 6 the group size the unit was compiled with (CLIK_CONVERGE_GROUP), 7 + k the compiled-in
+// velocity feedback map (velocity_feedback_info(k), clik_rollout_lane.hpp)
 template <const ShapeDesc& SD>
 inline long long converge_info(int what)
 {
     using LY = SummaryLayout<SD>;
+    if (what >= 7) return velocity_feedback_info(what - 7);
     if (what == 5) {
         if constexpr (!converge_fits<SD>()) {
             return -1;

@@ -360,6 +360,8 @@ __device__ __forceinline__ void pinv_rollout_static_body(
                 __syncthreads();
             }
         }
+        // (velocity feedback: behind the record and the reload, or the next record's rows would overwrite the fed entries)
+        if constexpr (HOOK::FEEDS) hook.fed(vout, 0u, ys + lane * NY);
     };
     if constexpr (!RK) {
         const Img<SD>* __restrict__ Se = REGIMG ? &Sreg : S;       // (what the Euler tick reads)
@@ -441,7 +443,7 @@ __global__ __launch_bounds__(WAVE) CLIK_ROLL_ATTR void pinv_rollout_static_rec_k
     const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed,
     double* __restrict__ x, double* __restrict__ dx, const RollRec rec)
 {
-    NoTickHook none;
+    FedHook<SD, NoTickHook> none;
     pinv_rollout_static_body<SD, RK, 1, true>(img_g, q, y, dq, mode_out, B, tterms, n_ticks, dt, max_speed, x, dx, rec, none);
 }
 
@@ -565,6 +567,7 @@ inline hipError_t launch_rollout_values_rec(const LaunchArgs& a, const double* d
                                             double max_speed, long long B, double* q, const double* y, double* dq,
                                             int32_t* mode, hipStream_t stream)
 {
+    if constexpr (kVelFeedbackN > 0) return hipErrorNotSupported;       // (the lane kernels alone carry the feedback)
     if (a.roll_rec == nullptr) return hipErrorInvalidValue;
     const RollRec rr = *a.roll_rec;
     const bool rk = a.roll_stages == 4;
@@ -601,7 +604,8 @@ inline hipError_t launch_rollout_static_rec(const LaunchArgs& a, const double* d
     const RollRec rr = *a.roll_rec;
     const bool rk = a.roll_stages == 4;
     const unsigned grid = (unsigned)((B + WAVE - 1) / WAVE);
-    if constexpr (shape_team_ok(SD)) {
+    // (a unit with the velocity feedback compiled in runs the lane kernel at every batch size: the team kernel has none)
+    if constexpr (shape_team_ok(SD) && kVelFeedbackN == 0) {
         PinvPolicy p = a.policy;
         p.values_attached = false;  // (see launch_solve_static)
         if (pinv_select(SD, p, B, PinvOp::rollout) == PinvVariant::team4)
@@ -614,6 +618,20 @@ inline hipError_t launch_rollout_static_rec(const LaunchArgs& a, const double* d
     return launch_with_lds(rk ? pinv_rollout_static_rec_kernel<SD, true> : pinv_rollout_static_rec_kernel<SD, false>, grid,
                            WAVE, shmem, stream, a.dImg, q, y, dq, mode, B, d_tterms, n_ticks, dt, max_speed, a.roll_x,
                            a.roll_dx, rr);
+}
+
+// what a caller may ask about the lane kernels of a recording unit (clik_jit_rec_info, in the units built with the
+// velocity feedback): 0 / 1 bytes of scratch per lane of the Euler / Runge-Kutta kernel as the loaded code object states
+// them (-1: no device to ask), 2 / 3 LDS bytes of an Euler / Runge-Kutta block, 4 both fit the LDS of a CU, 5 + k the
+// compiled-in feedback map (velocity_feedback_info(k))
+template <const ShapeDesc& SD>
+inline long long rollout_rec_info(int what)
+{
+    const size_t euler = static_lds_bytes<SD>(SD.n_y > 0 ? SD.n_y : 0), rk = euler + (size_t)2 * SD.n * WAVE * sizeof(double);
+    if (what == 0) return kernel_scratch_bytes((const void*)pinv_rollout_static_rec_kernel<SD, false>);
+    if (what == 1) return kernel_scratch_bytes((const void*)pinv_rollout_static_rec_kernel<SD, true>);
+    return what == 2 ? (long long)euler : what == 3 ? (long long)rk : what == 4 ? (rk <= kLaneLdsCap ? 1 : 0)
+         : what >= 5 ? velocity_feedback_info(what - 5) : -1;
 }
 
 }  // namespace clik

@@ -278,6 +278,8 @@ __device__ __forceinline__ void qp_rollout_static_body(
                 __syncthreads();
             }
         }
+        // (velocity feedback: behind the record and the reload, and what the record holds - NaN once infeasible)
+        if constexpr (HOOK::FEEDS) hook.fed(v, (worst == 2) ? 0x7ff80000u : 0u, ys + lane * NY);
     };
     if constexpr (!RK) {
 #pragma unroll 1
@@ -371,7 +373,7 @@ __global__ __launch_bounds__(WAVE) void qp_rollout_static_rec_kernel(
     const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed,
     double* __restrict__ x, double* __restrict__ dx, const RollRec rec)
 {
-    NoTickHook none;
+    FedHook<SD, NoTickHook> none;
     qp_rollout_static_body<SD, RK>(img_g, q, y, dq, slack_out, status_out, B, tterms, n_ticks, dt, max_speed, x, dx, rec, none);
 }
 
@@ -416,7 +418,7 @@ inline hipError_t launch_qp_rollout_static_values_rec(const double* d_tterms, in
                                                       int32_t* status, double* x, double* dx, hipStream_t stream,
                                                       int stages, const RollRec* rec)
 {
-    if constexpr (QpLayout<SD>::BOX) {
+    if constexpr (QpLayout<SD>::BOX && kVelFeedbackN == 0) {       // (the lane kernels alone carry the velocity feedback)
         if (rec == nullptr || (SD.n_x != 0 && (x == nullptr || dx == nullptr))) return hipErrorInvalidValue;
         const RollRec rr = *rec;
         const unsigned grid = (unsigned)((B + WAVE - 1) / WAVE);
@@ -430,6 +432,20 @@ inline hipError_t launch_qp_rollout_static_values_rec(const double* d_tterms, in
     } else {
         return hipErrorNotSupported;
     }
+}
+
+// what a caller may ask about the lane kernels of a recording unit (clik_jit_rec_info, in the units built with the
+// velocity feedback): 0 / 1 bytes of scratch per lane of the Euler / Runge-Kutta kernel as the loaded code object states
+// them (-1: no device to ask), 2 / 3 LDS bytes of an Euler / Runge-Kutta block, 4 both fit the LDS of a CU, 5 + k the
+// compiled-in feedback map (velocity_feedback_info(k))
+template <const ShapeDesc& SD>
+inline long long rollout_rec_info(int what)
+{
+    constexpr size_t euler = QpLayout<SD>::LDS_BYTES, rk = euler + (size_t)2 * SD.n * WAVE * sizeof(double);
+    if (what == 0) return kernel_scratch_bytes((const void*)qp_rollout_static_rec_kernel<SD, false>);
+    if (what == 1) return kernel_scratch_bytes((const void*)qp_rollout_static_rec_kernel<SD, true>);
+    return what == 2 ? (long long)euler : what == 3 ? (long long)rk : what == 4 ? (rk <= kLaneLdsCap ? 1 : 0)
+         : what >= 5 ? velocity_feedback_info(what - 5) : -1;
 }
 
 }  // namespace clik

@@ -104,16 +104,107 @@ __device__ __forceinline__ double clamp_step_size(double (&v)[N], const double m
 // with the base of its own LDS_DOUBLES behind the wave's region; tick(S, tk, z, ys, lane, tick, n_ticks, valid) at the top
 // of a tick, with the record the tick acts on (Runge-Kutta: the first stage's); finish(valid, n_ticks, inst) after the
 // loop.  This one is nothing, at compile time: the recording rollouts.
+// A hook with FEEDS is also called at the end of a tick, behind the tick's record and the reload of a per-tick target with
+// its barrier: fed(v, bad_hi, yrow) with the velocity the tick was integrated with (after the clamp; Runge-Kutta: the
+// combined rate), the NaN bits of an instance the record shows as NaN (QP: infeasible so far) and the lane's own target
+// row in LDS.
 struct NoTickHook {
     static constexpr bool ACTIVE = false;
+    static constexpr bool FEEDS = false;
     static constexpr int LDS_DOUBLES = 0;
     template <class... A>
     __device__ __forceinline__ void start(const A&...) {}
     template <class... A>
     __device__ __forceinline__ void tick(const A&...) {}
     template <class... A>
+    __device__ __forceinline__ void fed(const A&...) {}
+    template <class... A>
     __device__ __forceinline__ void finish(const A&...) {}
 };
+
+// The velocity feedback of the on-device loops (include/clik.h: the rule), compiled in as CLIK_CONVERGE_GROUP is:
+// -DCLIK_VELOCITY_FEEDBACK={f_0,...,f_{N-1}}, one entry per state (robot variables, then virtual ones): f_j >= 0 names the
+// entry of the instance's input_var row that the next tick reads the velocity of state j in, -1 none.  Without the flag
+// there is no map, every use below is behind `if constexpr`, and the units compile to the code they had.
+#ifdef CLIK_VELOCITY_FEEDBACK
+inline constexpr int kVelFeedbackMap[] = CLIK_VELOCITY_FEEDBACK;
+constexpr int kVelFeedbackN = (int)(sizeof(kVelFeedbackMap) / sizeof(kVelFeedbackMap[0]));
+#else
+inline constexpr int kVelFeedbackMap[1] = {-1};
+constexpr int kVelFeedbackN = 0;
+#endif
+
+constexpr size_t kLaneLdsCap = 160u * 1024u;        // LDS of one compute unit (gfx950): what a block of a lane rollout may take
+
+// what a unit's info query says about the map: k = 0 its length (0: compiled without), k = 1 + j entry j (-1 beyond it)
+inline long long velocity_feedback_info(const int k)
+{
+    if (k == 0) return kVelFeedbackN;
+    return (k >= 1 && k <= kVelFeedbackN) ? kVelFeedbackMap[k - 1] : -1;
+}
+
+// the fed entries of the lane's own target row: every lane writes its own row and nobody else's, so no barrier
+template <const ShapeDesc& SD>
+__device__ __forceinline__ void velocity_feed(const double (&v)[SD.n], const unsigned bad_hi, double* yrow)
+{
+    static_assert(kVelFeedbackN == SD.n, "CLIK_VELOCITY_FEEDBACK has one entry per robot and virtual variable");
+    if constexpr (kVelFeedbackN == SD.n) {
+        static_for<0, SD.n>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int j = decltype(jc)::value;
+            constexpr int k = kVelFeedbackMap[j];
+            static_assert(k >= -1 && k < (SD.n_y > 0 ? SD.n_y : 0), "CLIK_VELOCITY_FEEDBACK: an entry outside input_var");
+            if constexpr (k >= 0) yrow[k] = nan_or(v[j], bad_hi);
+        });
+    }
+}
+
+// the feedback as a hook of the lane-per-instance rollouts
+template <const ShapeDesc& SD>
+struct VelocityFeedbackHook : NoTickHook {
+    static constexpr bool FEEDS = true;
+    __device__ __forceinline__ void fed(const double (&v)[SD.n], const unsigned bad_hi, double* yrow)
+    {
+        velocity_feed<SD>(v, bad_hi, yrow);
+    }
+};
+
+// two hooks as one: A (made from the constructor's arguments) with its LDS first, then B
+template <class A, class B>
+struct ComposeHook {
+    static constexpr bool ACTIVE = A::ACTIVE || B::ACTIVE;
+    static constexpr bool FEEDS = A::FEEDS || B::FEEDS;
+    static constexpr int LDS_DOUBLES = A::LDS_DOUBLES + B::LDS_DOUBLES;
+    A a;
+    B b;
+    template <class... P>
+    __device__ __forceinline__ explicit ComposeHook(const P&... p) : a{p...}, b{} {}
+    __device__ __forceinline__ void start(double* base, const int lane, const bool valid, const long long inst)
+    {
+        a.start(base, lane, valid, inst);
+        b.start(base + A::LDS_DOUBLES, lane, valid, inst);
+    }
+    template <class... P>
+    __device__ __forceinline__ void tick(const P&... p)
+    {
+        if constexpr (A::ACTIVE) a.tick(p...);
+        if constexpr (B::ACTIVE) b.tick(p...);
+    }
+    template <class V>
+    __device__ __forceinline__ void fed(const V& v, const unsigned bad_hi, double* yrow)
+    {
+        if constexpr (A::FEEDS) a.fed(v, bad_hi, yrow);
+        if constexpr (B::FEEDS) b.fed(v, bad_hi, yrow);
+    }
+    __device__ __forceinline__ void finish(const bool valid, const int n_ticks, const long long inst)
+    {
+        a.finish(valid, n_ticks, inst);
+        b.finish(valid, n_ticks, inst);
+    }
+};
+
+// the hook a lane rollout carries: H itself in a unit without the feedback, H and the feedback with it
+template <const ShapeDesc& SD, class H>
+using FedHook = std::conditional_t<(kVelFeedbackN > 0), ComposeHook<H, VelocityFeedbackHook<SD>>, H>;
 
 // waves per block, 1 to 4, of a kernel whose block of wv waves takes BYTES(wv) of LDS: what puts most waves on a compute
 // unit (four SIMDs, one wave each: the kernels hold the whole register file), the fewest waves per block among equals;

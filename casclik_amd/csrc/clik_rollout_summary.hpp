@@ -155,6 +155,7 @@ template <const ShapeDesc& SD, bool HYBRID>
 struct RollSumHook {
     using SL = SummaryLayout<SD>;
     static constexpr bool ACTIVE = true;
+    static constexpr bool FEEDS = false;
     static constexpr int LDS_DOUBLES = RollSumLayout<SD, HYBRID>::DOUBLES;
     const RollSumArgs& sa;
     typename RollSumLayout<SD, HYBRID>::Acc acc;
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(WV * WAVE) CLIK_ROLL_ATTR void pinv_rollout_static_
     const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed,
     double* __restrict__ x, double* __restrict__ dx, const RollRec ra, const RollSumArgs sa)
 {
-    RollSumHook<SD, true> hook{sa};
+    FedHook<SD, RollSumHook<SD, true>> hook{sa};
     pinv_rollout_static_body<SD, RK, WV, false>(img_g, q, y, dq, mode_out, B, tterms, n_ticks, dt, max_speed, x, dx, ra, hook);
 }
 
@@ -272,7 +273,7 @@ __global__ __launch_bounds__(WAVE) void qp_rollout_static_sum_kernel(
     const double* __restrict__ tterms, const int n_ticks, const double dt, const double max_speed,
     double* __restrict__ x, double* __restrict__ dx, const RollRec ra, const RollSumArgs sa)
 {
-    RollSumHook<SD, false> hook{sa};
+    FedHook<SD, RollSumHook<SD, false>> hook{sa};
     qp_rollout_static_body<SD, RK>(img_g, q, y, dq, slack_out, status_out, B, tterms, n_ticks, dt, max_speed, x, dx, ra, hook);
 }
 
@@ -318,11 +319,12 @@ inline hipError_t launch_qp_rollout_static_sum(const void* d_img, const double* 
 // what a caller may ask about the instantiation (clik_jit_rollsum_info): 0 rows, 1 SetConstraint rows, 2 LDS bytes of a
 // Runge-Kutta block, 3 fits the LDS of a CU, 4 LDS bytes of an Euler block, 5 / 6 bytes of scratch per lane of the Euler /
 // Runge-Kutta kernel as the loaded code object states them (-1: no device to ask), 7 / 8 waves of an Euler / Runge-Kutta
-// block
+// block, 9 + k the compiled-in velocity feedback map (velocity_feedback_info(k), clik_rollout_lane.hpp)
 template <const ShapeDesc& SD>
 inline long long rollsum_info(int what)
 {
     using LY = SummaryLayout<SD>;
+    if (what >= 9) return velocity_feedback_info(what - 9);
     if (what == 5 || what == 6) {
         if constexpr (!rollsum_fits<SD>()) {
             return -1;

@@ -371,7 +371,27 @@ int clik_pinv_rollout_batch_m(const clik_pinv* h, int64_t B, int32_t n_ticks, in
  * q / x / dq / dx / mode receive the end of the launch as before.  Needs the shape-specialised RECORDING rollout of the
  * skill, attached with clik_pinv_attach_rec_kernel (rollout_rec_fn: the image-reading one, needs a shape-specialised
  * kernel on the handle; value_rollout_rec_fn: the one with the skill's numbers compiled in, may be NULL; both NULL
- * detaches); a handle without one - one served by the built-in dynamic-shape kernel - gets CLIK_EUNSUPPORTED.   */
+ * detaches); a handle without one - one served by the built-in dynamic-shape kernel - gets CLIK_EUNSUPPORTED.
+ *
+ * Velocity feedback.  Like the group rule of clik_pinv_converge_batch it is a property of the attached kernel, not an
+ * argument: the lane-per-instance rollouts compiled with -DCLIK_VELOCITY_FEEDBACK={f_0,...,f_{N-1}} (clik_rollout_lane.hpp;
+ * N = n_q + n_x, robot variables first; f_j an index into the instance's y row, or -1 for none; no index twice).  jit.py
+ * builds one such unit per skill and map for the recording, the summarising (clik_*_rollout_batch_sum) and the converging
+ * (clik_*_converge_batch) rollouts, options["velocity_feedback"] of the Python controllers attaches them - same entries,
+ * same signatures, same attach functions - and their info queries report the map.  Where f_j >= 0, inside such a launch:
+ *   tick 0 reads y[b][f_j] as the caller gave it: the velocity before the launch, usually zero;
+ *   tick k + 1 reads in that entry the velocity of state j that tick k was integrated with - what the launch would
+ *     return in dq / dx if it ended after tick k, and what record k of record_every = 1 holds: after the clamp; with
+ *     Runge-Kutta the combined (k1 + 2 k2 + 2 k3 + k4) / 6, and all four stages of tick k + 1 read that same value.  A NaN
+ *     is fed like any other value (QP: the NaN of an instance that has been infeasible, as its records show it).
+ *   With y_per_tick != 0 tick i still takes its other entries from record i; the fed entries of records i >= 1 are
+ *     ignored.  y itself is never written: the fed values live in the kernel's copy of the row.
+ *   In clik_*_converge_batch only a tick that is integrated feeds: a stopped instance keeps its entries, and a stalled
+ *     or infeasible tick feeds nothing.
+ * Chunking: a launch of n1 + n2 ticks equals a launch of n1 ticks followed by a launch of n2 ticks whose fed entries are
+ * the first launch's dq / dx (pinv: bit for bit; QP: to rounding, its first tick being a cold solve).  Such a unit runs
+ * the lane-per-instance kernel at every batch size.  The ticks (clik_*_solve_batch), the plain, team and value-specialised
+ * rollouts and the resident kernels do not feed anything: the caller owns y there.   */
 int clik_pinv_attach_rec_kernel(clik_pinv* h, void* rollout_rec_fn, void* value_rollout_rec_fn);
 int clik_pinv_rollout_batch_rec(const clik_pinv* h, int64_t B, int32_t n_ticks, int32_t method,
                                 double dt, double max_speed, const double* tterms,

@@ -7,7 +7,10 @@ remarks (no GPU needed).      python tools/kernel_resources.py [stack|pose|qp] [
 Runge-Kutta; their LDS is dynamic - tools/rollout_summary_bench.py prints the launcher's figure).
 --converge: the converging rollout of that skill (jit._CONVERGE_TEMPLATE / _QP_CONVERGE_TEMPLATE: pinv_converge_static_kernel /
 qp_converge_static_kernel, image-reading, Euler; LDS dynamic - tools/converge_bench.py prints the launcher's figure);
---converge=G: the same unit with the group rule for groups of G lanes (-DCLIK_CONVERGE_GROUP=G, G in 2 .. 64)."""
+--converge=G: the same unit with the group rule for groups of G lanes (-DCLIK_CONVERGE_GROUP=G, G in 2 .. 64).
+--feedback=f0,f1,...: with --rec, --rollsum or --converge[=G] the variant of that unit with the velocity feedback map
+compiled in (-DCLIK_VELOCITY_FEEDBACK={f0,f1,...}: one entry per robot and virtual variable, an index into input_var or -1;
+--rec is then the image-reading recording rollout, jit.FEEDBACK_UNITS - the lane kernels alone carry the feedback)."""
 import os
 import subprocess
 import sys
@@ -48,6 +51,13 @@ if group:
     # (--converge=G: the unit with the group rule for groups of G lanes, as converge_batch(..., group=G) asks for it)
     template, words = jit.CONVERGE_UNITS["converge", req.kind]["template"], None
     defines = jit.converge_group_defines(int(group[-1].split("=", 1)[1]) if "=" in group[-1] else 1)
+feedback = [a.split("=", 1)[1] for a in sys.argv[2:] if a.startswith("--feedback=")]
+if feedback:
+    if "--rec" in sys.argv:
+        template, words, defines = jit.FEEDBACK_UNITS["rec", req.kind]["template"], None, ()
+    elif not ("--rollsum" in sys.argv or group):
+        sys.exit("--feedback goes with --rec, --rollsum or --converge")
+    defines = tuple(defines) + jit.velocity_feedback_defines([int(k) for k in feedback[-1].split(",")])
 text = jit.unit_text(template, req.init, req.extern, words)
 # (the scheduling strategy the shipped object is compiled with, casclik_amd/jit.py::sched_strategy - unless one is given)
 how = dict(extra=defines, csrc=csrc, more=flags, sched=None if any("sched-strategy" in f for f in flags) else "unit")
