@@ -1,15 +1,16 @@
-"""What the tests of ``converge_batch`` / ``ik_batch`` share and what needs no GPU: the fixtures' inputs, the stop rule of
-include/clik.h in plain numpy, a host loop on the oracle, and ``select_seeds`` as a plain-Python loop."""
+"""What the tests of ``converge_batch`` / ``ik_batch`` share and what needs no GPU: the fixtures' inputs and ``select_seeds``
+as a plain-Python loop.  The stop rule of include/clik.h in plain numpy and the host loop on the oracle are those of
+tests/host_loops.py (``converge_loop``), under the names they have always had here."""
 import numpy as np
 
 import casclik_amd as cc
 from casclik_amd import skills
 from casclik_amd.controllers.base_controller import constraint_row_slices
 from casclik_amd.lowering import lower_skill
-from oracle import clik_oracle
 
-MARGIN = 4e-12          # (tests/test_gpu_constraint_summary.py: an integer result decided by less is left out)
-DT = 0.05               # with gain 10 the error halves per tick
+from host_loops import DT, MARGIN, distances, oracle_values, stop_rule        # noqa: F401
+from time_skills import UR5_HOME
+
 B_ALL = 130             # every batch of the tests is a prefix of this one
 
 
@@ -26,9 +27,6 @@ def reach_inputs(fk, B, seed=3, lo_exp=-5.0, hi_exp=-1.2):
         T = fk["chain"].fk_numeric(near[b])
         Y[b, :3], Y[b, 3:] = T[:3, 3], skills.quat_from_matrix(T[:3, :3])
     return Q, Y
-
-
-UR5_HOME = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
 
 
 def path_skill(fk):
@@ -101,95 +99,6 @@ def tolerances(spec, by_label):
     for label, sl in rows.items():
         tol[sl] = by_label[label]
     return tol
-
-
-def oracle_values(spec, t, Q, X=None, Y=None):
-    """(e, set_min, set_max) [R, B, M_tot] and is_set [M_tot] of the records Q [R, B, n_q], all at time t, the target
-    shared by the records: the oracle's own evaluation of every constraint expression (as ``_oracle`` of
-    tests/test_gpu_constraint_summary.py)"""
-    R, B = Q.shape[:2]
-    flat = lambda A: None if A is None else A.reshape(R * B, -1)         # noqa: E731
-    Z = flat(Q) if X is None else np.hstack([flat(Q), flat(X)])
-    Yf = flat(None if Y is None else np.broadcast_to(Y, (R,) + Y.shape))
-    ev = clik_oracle.ExprEvaluator(spec, np.full(R * B, float(t)), Z, Yf)
-    rows = constraint_row_slices(lower_skill(spec))
-    m_tot = max(sl.stop for sl in rows.values())
-    e = np.zeros((R * B, m_tot))
-    lo, hi = np.full((R * B, m_tot), -np.inf), np.full((R * B, m_tot), np.inf)
-    is_set = np.zeros(m_tot, dtype=bool)
-    views = clik_oracle.attribute_views(ev, spec.constraints)
-    for c, view in zip(spec.constraints, views):
-        sl = rows[c.label]
-        e[:, sl] = ev.vector(c.expression)[0]
-        if clik_oracle._cls(c) == "SetConstraint":
-            is_set[sl] = True
-            m = sl.stop - sl.start
-            lo[:, sl] = np.stack([clik_oracle._num(v.set_min, m) for v in view])
-            hi[:, sl] = np.stack([clik_oracle._num(v.set_max, m) for v in view])
-    shape = (R, B, m_tot)
-    return e.reshape(shape), lo.reshape(shape), hi.reshape(shape), is_set
-
-
-def distances(e, lo, hi, is_set):
-    with np.errstate(invalid="ignore"):
-        return np.where(is_set, np.maximum(np.maximum(lo - e, e - hi), 0.0), np.abs(e))
-
-
-def stop_rule(e, lo, hi, is_set, tol, max_ticks):
-    """Steps 1 - 4 of the stop rule on the records r = 0 .. max_ticks of a rollout that never stops (e [max_ticks + 1, B,
-    M_tot]): ``(ticks [B], status [B], residual [B, M_tot], sure [B])``; ``sure``: no row of the instance comes within
-    MARGIN of its tolerance at any record up to its stop."""
-    R, B, M = e.shape
-    assert R == max_ticks + 1
-    d = distances(e, lo, hi, is_set)
-    with np.errstate(invalid="ignore"):
-        met = (d <= tol).all(axis=2)
-        close = (np.abs(d - tol) < MARGIN).any(axis=2)
-    bad = ~np.isfinite(e).all(axis=2)
-    ticks, status = np.full(B, max_ticks, dtype=np.int32), np.ones(B, dtype=np.int32)
-    for b in range(B):
-        for r in range(R):
-            if bad[r, b] or met[r, b]:
-                ticks[b], status[b] = r, 4 if bad[r, b] else 0
-                break
-    sure = np.array([not close[:ticks[b] + 1, b].any() for b in range(B)])
-    return ticks, status, d[ticks, np.arange(B)], sure
-
-
-def host_loop(spec, options, Q, Y, tol, max_ticks, dt=DT, max_speed=0.0, min_step=0.0, t=0.0, margin=MARGIN):
-    """The whole rule, every instance on its own, no device code: the oracle's constraint values and
-    ``clik_oracle.pinv_solve_batch`` per tick.  Returns ``(q, dq, ticks, status, residual, sure)``; ``sure``: no row of the
-    instance came within ``margin`` of its tolerance."""
-    B = Q.shape[0]
-    q, dq = Q.copy(), np.zeros_like(Q)
-    ticks, status = np.zeros(B, dtype=np.int32), np.full(B, -1, dtype=np.int32)
-    residual, sure = np.zeros((B, tol.size)), np.ones(B, dtype=bool)
-    for r in range(max_ticks + 1):
-        go = np.nonzero(status < 0)[0]
-        if go.size == 0:
-            break
-        e, lo, hi, is_set = oracle_values(spec, t, q[None, go], None, None if Y is None else Y[go])
-        d = distances(e, lo, hi, is_set)[0]
-        residual[go] = d
-        sure[go] &= ~(np.abs(d - tol) < margin).any(axis=1)
-        bad = ~np.isfinite(e[0]).all(axis=1)
-        with np.errstate(invalid="ignore"):
-            met = (d <= tol).all(axis=1)
-        st = np.where(bad, 4, np.where(met, 0, 1 if r == max_ticks else -1))
-        status[go] = st
-        ticks[go] = r
-        go = go[st < 0]
-        if go.size == 0:
-            continue
-        v = clik_oracle.pinv_solve_batch(spec, options, t, q[go], Y=None if Y is None else Y[go])[0][:, :Q.shape[1]]
-        if max_speed > 0.0:
-            v = np.clip(v, -max_speed, max_speed)
-        stall = (min_step > 0.0) & (np.abs(v).max(axis=1) * dt <= min_step)
-        status[go[stall]] = 2
-        go, v = go[~stall], v[~stall]
-        q[go] += v * dt
-        dq[go] = v
-    return q, dq, ticks, status, residual, sure
 
 
 def select_seeds_loop(ticks, status, residual, tol, S):

@@ -4,6 +4,7 @@ import numpy as np
 
 import casclik_amd as cc
 from casclik_amd import sym as cs
+from time_skills import UR5_HOME
 
 
 def double_pendulum_skill(track=False):
@@ -42,7 +43,7 @@ def moe_box_skill(fk, soft_walls=False):
     path = cs.vertcat(0.5 * cs.sin(omega * t) * cs.sin(omega * t) + 0.2,
                       0.5 * cs.cos(omega * t) + 0.25 * cs.sin(omega * t),
                       0.5 * cs.sin(omega * t) * cs.cos(omega * t) + 0.1)
-    home = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
+    home = UR5_HOME
     p_home = fk["chain"].fk_numeric(home)[:3, 3]
     box = [(c - 0.15, c + 0.15) for c in p_home]       # the notebook also starts inside its box
     kw = dict(constraint_type="soft") if soft_walls else {}

@@ -290,9 +290,9 @@ def box_move_skill(fk):
     box (general rows), a soft move, hard speed limits on the UR5 -> (spec, home)"""
     import casclik_amd as cc
     from casclik_amd import sym as cs
+    from time_skills import UR5_HOME as home
     t, q = cs.MX.sym("t"), cs.MX.sym("q", 6)
     p = fk["T_fk"](q)[:3, 3]
-    home = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
     p_home = fk["chain"].fk_numeric(home)[:3, 3]
     cons = [cc.SetConstraint("box_%d" % i, p[i], set_min=p_home[i] - 0.15, set_max=p_home[i] + 0.15, priority=i, gain=50.0)
             for i in range(3)]

@@ -7,6 +7,8 @@ import pytest
 import casclik_amd as cc
 from casclik_amd import skills
 from casclik_amd import sym as cs
+from host_loops import oracle_tick, rollout_loop
+from time_skills import UR5_HOME
 from tolerances import PINV_RTOL, pinv_close, qp_close
 
 pytestmark = pytest.mark.gpu
@@ -205,8 +207,7 @@ def test_virtual_variable_pinv(ur5_fk, kernel, monkeypatch):
         monkeypatch.setenv("CLIK_FORCE_DYNAMIC", "1")
     spec = _path_following_skill(ur5_fk)
     rng = np.random.default_rng(3)
-    home = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
-    Q = home + rng.normal(scale=0.2, size=(150, 6))
+    Q = UR5_HOME + rng.normal(scale=0.2, size=(150, 6))
     X = rng.uniform(-0.1, 1.1, size=(150, 1))
     ctrl = cc.PseudoInverseController(skill_spec=spec)
     ctrl.setup_problem_functions()
@@ -228,8 +229,7 @@ def test_virtual_variable_qp(ur5_fk, kernel, monkeypatch):
         monkeypatch.setenv("CLIK_FORCE_DYNAMIC", "1")
     spec = _path_following_skill(ur5_fk)
     rng = np.random.default_rng(4)
-    home = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
-    Q = home + rng.normal(scale=0.2, size=(150, 6))
+    Q = UR5_HOME + rng.normal(scale=0.2, size=(150, 6))
     X = rng.uniform(-0.1, 1.1, size=(150, 1))
     ctrl = cc.ReactiveQPController(skill_spec=spec)
     ctrl.setup_problem_functions()
@@ -257,7 +257,7 @@ def test_norm_rows_in_static_shapes(ur5_fk, kernel, monkeypatch):
     T = fk["T_fk"](q)
     p = T[:3, 3]
     lo, hi = np.array(fk["lower"]), np.array(fk["upper"])
-    home = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
+    home = UR5_HOME
     R_des = fk["chain"].fk_numeric(home + 0.3)[:3, :3]
     cons = [cc.EqualityConstraint("dist", cs.norm_2(np.array([0.5, 0.5, 0.5]) - p), gain=5.0, priority=6),
             cc.EqualityConstraint("rot", cs.norm_fro(T[:3, :3] - R_des), gain=2.0, priority=7),
@@ -466,23 +466,18 @@ def test_rollout_with_virtual_variable_matches_the_host_loop(ur5_fk, monkeypatch
     """Path following on the device (cart_on_track_1D...ipynb cell 60 integrates the path parameter next to
     the robot state): n ticks of solve -> clamp(robot velocities) -> Euler on [q; s] in one launch against the
     same loop over the oracle.  The built-in dynamic kernel cannot (loud refusal)."""
-    from oracle import clik_oracle
     spec = _path_following_skill(ur5_fk)
     rng = np.random.default_rng(5)
-    home = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
-    Q = home + rng.normal(scale=0.2, size=(70, 6))
+    Q = UR5_HOME + rng.normal(scale=0.2, size=(70, 6))
     X = rng.uniform(0.0, 0.9, size=(70, 1))
     ctrl = cc.PseudoInverseController(skill_spec=spec)
     ctrl.setup_problem_functions()
     dt, vmax, n_ticks = 0.01, 0.4, 40
     ts = dt * np.arange(n_ticks)
     qf, xf, dq_last, dx_last, mode = ctrl.rollout_batch(ts, Q, dt=dt, max_speed=vmax, virtual_var=X)
-    q, x = Q.copy(), X.copy()
-    for k in range(n_ticks):
-        r, rmode = clik_oracle.pinv_solve_batch(spec, None, ts[k], q, X=x)
-        dq, dx = np.clip(r[:, :6], -vmax, vmax), r[:, 6:]
-        q, x = q + dq * dt, x + dx * dt
-    assert np.array_equal(mode, rmode)
+    host = rollout_loop(oracle_tick(spec, False), False, ts, Q, X, lambda i: None, dt, vmax)[-1]
+    q, x, dq, dx = host["q"], host["x"], host["dq"], host["dx"]
+    assert np.array_equal(mode, host["flag"])
     assert np.abs(qf - q).max() < 1e-8 and np.abs(xf - x).max() < 1e-8
     assert np.abs(dq_last - dq).max() < 1e-7 and np.abs(dx_last - dx).max() < 1e-7
     assert np.abs(xf - X - 0.05 * dt * n_ticks).max() < 1e-6        # the path parameter advanced at its set rate
@@ -496,11 +491,9 @@ def test_rollout_with_virtual_variable_matches_the_host_loop(ur5_fk, monkeypatch
 def test_qp_rollout_with_virtual_variable_matches_the_host_loop(ur5_fk):
     """The same path-following loop through ReactiveQPController (clik_qp_rollout_batch_x): robot state and
     path parameter integrated on the device, working set carried between ticks."""
-    from oracle import clik_oracle
     spec = _path_following_skill(ur5_fk)
     rng = np.random.default_rng(6)
-    home = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
-    Q = home + rng.normal(scale=0.2, size=(40, 6))
+    Q = UR5_HOME + rng.normal(scale=0.2, size=(40, 6))
     X = rng.uniform(0.1, 0.8, size=(40, 1))
     ctrl = cc.ReactiveQPController(skill_spec=spec)
     ctrl.setup_problem_functions()
@@ -508,11 +501,9 @@ def test_qp_rollout_with_virtual_variable_matches_the_host_loop(ur5_fk):
     dt, vmax, n_ticks = 0.01, 0.4, 30
     ts = dt * np.arange(n_ticks)
     qf, xf, dq_last, dx_last, slack, status = ctrl.rollout_batch(ts, Q, dt=dt, max_speed=vmax, virtual_var=X)
-    q, x = Q.copy(), X.copy()
-    for k in range(n_ticks):
-        rdq, rdx, rsl, rst = clik_oracle.qp_solve_batch(spec, ts[k], q, X=x)
-        assert (rst == 0).all()
-        q, x = q + np.clip(rdq, -vmax, vmax) * dt, x + rdx * dt
+    host = rollout_loop(oracle_tick(spec, True), True, ts, Q, X, lambda i: None, dt, vmax)
+    assert all((h["flag"] == 0).all() for h in host)
+    q, x, rdx, rsl = host[-1]["q"], host[-1]["x"], host[-1]["dx"], host[-1]["slack"]
     assert (status == 0).all()
     assert np.abs(qf - q).max() < 1e-7 and np.abs(xf - x).max() < 1e-7
     assert np.abs(dx_last - rdx).max() < 1e-7 and np.abs(slack - rsl).max() < 1e-6

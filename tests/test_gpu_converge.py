@@ -16,6 +16,7 @@ from casclik_amd import sym as cs
 from casclik_amd.controllers.base_controller import select_seeds
 
 import converge_cases as K
+import host_loops as H
 from test_gpu_constraint_summary import TOL
 from test_gpu_rollout_record import Q_TOL, V_TOL
 
@@ -140,7 +141,7 @@ def test_a_host_loop_on_the_oracle_stops_at_the_same_ticks(iiwa_fk, ur5_fk):
     B, n, margin = 65, case["max_ticks"], 1e-8
     Q, _, Y = K.inputs("pose", iiwa_fk, B, seed=4)
     tol = K.tolerances(spec, case["tol"])
-    hq, hdq, hticks, hstatus, hres, sure = K.host_loop(spec, ctrl.options, Q, Y, tol, n, margin=margin)
+    hq, hdq, hticks, hstatus, hres, sure = H.converge_loop(spec, ctrl.options, Q, Y, tol, n, margin=margin)
     assert len(np.unique(hticks)) >= 8 and (hstatus == 0).any() and (hstatus == 1).any()
     got = _unpack(ctrl.converge_batch(Q, Y, tol=tol, max_ticks=n, dt=DT), False, False)
     print("host loop: %d of %d left out; |q| %.3e |dq| %.3e |residual| %.3e" % (

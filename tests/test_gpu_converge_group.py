@@ -13,6 +13,7 @@ from casclik_amd import jit, skills
 
 import converge_cases as K
 import group_cases as GC
+import host_loops as H
 from test_gpu_constraint_summary import TOL
 from test_gpu_converge import _ctrl, _quiet_nan, _reference, _same_bits, _unpack
 from test_gpu_rollout_record import Q_TOL, V_TOL
@@ -108,7 +109,7 @@ def test_a_host_loop_with_the_rule_stops_at_the_same_ticks(iiwa_fk, ur5_fk):
     B, G, n, margin = 128, 2, case["max_ticks"], 1e-8
     Q, _, Y = K.inputs("pose", iiwa_fk, B, seed=4)
     tol = K.tolerances(spec, case["tol"])
-    hq, hdq, hticks, hstatus, hres, sure = GC.host_loop(spec, ctrl.options, Q, Y, tol, n, G, margin=margin)
+    hq, hdq, hticks, hstatus, hres, sure = H.converge_loop(spec, ctrl.options, Q, Y, tol, n, margin=margin, group=G)
     sure = GC.whole_groups(sure, G)
     ok = (hstatus == 0).reshape(-1, G)
     ties = ok.all(axis=1) & (hticks.reshape(-1, G)[:, 0] == hticks.reshape(-1, G)[:, 1])

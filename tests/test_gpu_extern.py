@@ -12,6 +12,7 @@ import casclik_amd as cc
 from casclik_amd import skills
 from casclik_amd import sym as cs
 from extern_skills import double_pendulum_skill, mixed_frame_skill, dual_quaternion_skill, ops_inputs, ops_skill
+from host_loops import oracle_tick, rollout_loop
 from tolerances import PINV_RTOL, QP_RTOL, pinv_close, qp_close
 
 pytestmark = pytest.mark.gpu
@@ -63,15 +64,12 @@ def test_double_pendulum_notebook_loop_matches_the_rollout():
     q0 = np.array([[np.pi / 2 - 1e-5, 0.0], [1.0, 0.5], [2.0, -0.7]])
     ts = dt * np.arange(n_ticks)
     qf, dq_last, _, status = ctrl.rollout_batch(ts, q0, dt=dt)
-    w = clik_oracle.qp_weights(spec, [1.0, 1.0])
-    q = q0.copy()
-    for k in range(n_ticks):
-        rdq, _, _, rst = clik_oracle.qp_solve_batch(spec, ts[k], q, weights=w)
-        assert (rst == 0).all()
-        q = q + rdq * dt
+    tick = oracle_tick(spec, True, weights=clik_oracle.qp_weights(spec, [1.0, 1.0]))
+    host = rollout_loop(tick, True, ts, q0, None, lambda i: None, dt)
+    assert all((h["flag"] == 0).all() for h in host)
     assert (status == 0).all()
-    assert np.abs(qf - q).max() < 1e-7
-    assert np.abs(dq_last - rdq).max() < 1e-7
+    assert np.abs(qf - host[-1]["q"]).max() < 1e-7
+    assert np.abs(dq_last - host[-1]["dq"]).max() < 1e-7
 
 
 def test_double_pendulum_pseudo_inverse():
@@ -234,10 +232,7 @@ def test_dual_quaternion_pose_error_reactive_qp(ur5_fk, which):
     ts = dt * np.arange(n_ticks)
     q0 = np.stack([home, home + 0.2])
     qf, dq_last, _, st = ctrl.rollout_batch(ts, q0, dt=dt, max_speed=vmax)
-    q = q0.copy()
-    for k in range(n_ticks):
-        rdq, _, _, rst = clik_oracle.qp_solve_batch(spec, ts[k], q)
-        q = q + np.clip(rdq, -vmax, vmax) * dt
+    q = rollout_loop(oracle_tick(spec, True), True, ts, q0, None, lambda i: None, dt, vmax)[-1]["q"]
     assert (st == 0).all() and np.abs(qf - q).max() < 1e-7
 
 

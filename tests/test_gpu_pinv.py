@@ -6,6 +6,8 @@ import pytest
 import casclik_amd as cc
 from casclik_amd import skills
 from casclik_amd import sym as cs
+from host_loops import controller_tick, rollout_loop
+from time_skills import UR5_HOME
 from tolerances import PINV_RTOL, PINV_RTOL_TIGHT, pinv_close, qp_close
 
 pytestmark = pytest.mark.gpu
@@ -135,14 +137,10 @@ def test_rollout_matches_host_loop(iiwa_fk):
     ctrl = _controller(spec, skills.STACK_OPTIONS)
     Q, Y = skills.synthetic_inputs(iiwa_fk, 100, seed=13, distribution="mixed")
     dt, vmax, n_ticks = 0.008, np.pi / 5, 12
-    q = Q.copy()
-    for _ in range(n_ticks):
-        dq, _, mode = ctrl.solve_batch(0.0, q, input_var=Y)
-        dq = np.clip(dq, -vmax, vmax)
-        q = q + dq * dt
+    host = rollout_loop(controller_tick(ctrl, False), False, np.zeros(n_ticks), Q, None, lambda i: Y, dt, vmax)[-1]
     q_dev, dq_dev, mode_dev = ctrl.rollout_batch(np.zeros(n_ticks), Q, input_var=Y, dt=dt, max_speed=vmax)
-    assert np.array_equal(mode_dev, mode)
-    assert np.abs(q_dev - q).max() < 1e-9 and np.abs(dq_dev - dq).max() < 1e-7
+    assert np.array_equal(mode_dev, host["flag"])
+    assert np.abs(q_dev - host["q"]).max() < 1e-9 and np.abs(dq_dev - host["dq"]).max() < 1e-7
 
 
 def test_single_solve_api(iiwa_fk):
@@ -246,8 +244,7 @@ def test_rollout_with_time_trajectory(ur5_fk):
     ctrl = _controller(spec)
     assert ctrl.kernel_name != "dynamic"
     rng = np.random.default_rng(8)
-    home = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
-    Q = home + rng.normal(scale=0.1, size=(70, 6))
+    Q = UR5_HOME + rng.normal(scale=0.1, size=(70, 6))
     dt, n_ticks = 0.05, 9
     times = 3.0 + dt * np.arange(n_ticks)
     qh = Q.copy()

@@ -8,6 +8,8 @@ import pytest
 import casclik_amd as cc
 from casclik_amd import skills
 from casclik_amd import sym as cs
+from host_loops import controller_tick, rollout_loop
+from time_skills import UR5_HOME
 from tolerances import QP_RTOL, KKT_TOL, pinv_close, qp_close
 
 pytestmark = pytest.mark.gpu
@@ -77,7 +79,7 @@ def test_qp_moe_style_skill_ur5(ur5_fk):
     path = cs.vertcat(0.5 * cs.sin(omega * t) * cs.sin(omega * t) + 0.2,
                       0.5 * cs.cos(omega * t) + 0.25 * cs.sin(omega * t),
                       0.5 * cs.sin(omega * t) * cs.cos(omega * t) + 0.1)
-    home = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
+    home = UR5_HOME
     p_home = fk["chain"].fk_numeric(home)[:3, 3]
     box = [(c - 0.15, c + 0.15) for c in p_home]       # the notebook also starts inside its box
     cons = [cc.SetConstraint("colav_%d" % i, p[i], set_min=lo, set_max=hi, priority=7 + i, gain=5e2)
@@ -178,7 +180,7 @@ def test_qp_soft_set_hard_equality_mix(ur5_fk):
     t = cs.MX.sym("t")
     q = cs.MX.sym("q", 6)
     p = fk["T_fk"](q)[:3, 3]
-    home = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
+    home = UR5_HOME
     p_home = fk["chain"].fk_numeric(home)[:3, 3]
     cons = [
         cc.VelocityEqualityConstraint("wrist_rate", q[5], target=0.05, priority=0),
@@ -241,16 +243,12 @@ def test_qp_rollout_matches_host_loop(iiwa_fk, variant, monkeypatch):
     ctrl = _controller(spec)
     Q, Y = skills.synthetic_inputs(iiwa_fk, 100, seed=14, distribution="mixed")
     dt, vmax, n_ticks = 0.008, 1.0, 10
-    q = Q.copy()
-    for _ in range(n_ticks):
-        dq, _, slack, status = ctrl.solve_batch(0.0, q, input_var=Y)
-        assert (status == 0).all()
-        dq = np.clip(dq, -vmax, vmax)
-        q = q + dq * dt
+    host = rollout_loop(controller_tick(ctrl, True), True, np.zeros(n_ticks), Q, None, lambda i: Y, dt, vmax)
+    assert all((h["flag"] == 0).all() for h in host)
     q_dev, dq_dev, slack_dev, status_dev = ctrl.rollout_batch(np.zeros(n_ticks), Q, input_var=Y, dt=dt, max_speed=vmax)
     assert (status_dev == 0).all()
-    assert np.abs(q_dev - q).max() < 1e-9 and np.abs(dq_dev - dq).max() < 1e-7
-    assert np.abs(slack_dev - slack).max() < 1e-7
+    assert np.abs(q_dev - host[-1]["q"]).max() < 1e-9 and np.abs(dq_dev - host[-1]["dq"]).max() < 1e-7
+    assert np.abs(slack_dev - host[-1]["slack"]).max() < 1e-7
 
 
 def test_qp_rollout_needs_a_static_kernel(iiwa_fk, monkeypatch):
@@ -276,15 +274,12 @@ def test_qp_rollout_with_time_trajectory(ur5_fk):
     ctrl = _controller(spec)
     assert ctrl.kernel_name != "dynamic"
     rng = np.random.default_rng(18)
-    home = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
-    Q = home + rng.normal(scale=0.1, size=(70, 6))
+    Q = UR5_HOME + rng.normal(scale=0.1, size=(70, 6))
     dt, n_ticks = 0.05, 8
     times = 3.0 + dt * np.arange(n_ticks)
-    qh = Q.copy()
-    for tv in times:
-        dq, _, slack, status = ctrl.solve_batch(float(tv), qh)
-        assert (status == 0).all()
-        qh = qh + dq * dt
+    host = rollout_loop(controller_tick(ctrl, True), True, times, Q, None, lambda i: None, dt)
+    assert all((h["flag"] == 0).all() for h in host)
+    qh, dq, slack = host[-1]["q"], host[-1]["dq"], host[-1]["slack"]
     assert (np.abs(np.abs(dq) - 0.3) < 1e-12).any()          # the speed limits are active somewhere
     q_dev, dq_dev, slack_dev, status_dev = ctrl.rollout_batch(times, Q, dt=dt)
     assert (status_dev == 0).all()
@@ -603,7 +598,7 @@ def test_qp_value_specialised_kernel_outside_the_box_family(ur5_fk):
     fk = ur5_fk
     t, q = cs.MX.sym("t"), cs.MX.sym("q", 6)
     p = fk["T_fk"](q)[:3, 3]
-    home = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
+    home = UR5_HOME
     p_home = fk["chain"].fk_numeric(home)[:3, 3]
     cons = [cc.SetConstraint("box_%d" % i, p[i], set_min=p_home[i] - 0.15, set_max=p_home[i] + 0.15, priority=i, gain=50.0)
             for i in range(3)]

@@ -1,14 +1,18 @@
 """GPU: rollouts that record their trajectory (``record_every``) and follow one target per tick (``input_var
-[n_ticks, B, n_y]``), both controllers, every instantiated rollout kernel.  The yardstick is the host loop of the
-existing rollout tests (``solve_batch`` -> ``np.clip`` -> ``q += dq * dt``, tests/test_gpu_pinv.py::
-test_rollout_matches_host_loop, tests/test_gpu_qp.py::test_qp_rollout_matches_host_loop) with their tolerances:
-|q| < 1e-9, |dq| and |slack| < 1e-7, modes equal, status 0."""
+[n_ticks, B, n_y]``), both controllers, every instantiated rollout kernel.  The yardstick is the host loop of all
+rollout tests (tests/host_loops.py::rollout_loop: ``solve_batch`` -> ``np.clip`` -> ``q += dq * dt``) with the
+tolerances of tests/test_gpu_pinv.py::test_rollout_matches_host_loop and tests/test_gpu_qp.py::
+test_qp_rollout_matches_host_loop: |q| < 1e-9, |dq| and |slack| < 1e-7, modes equal, status 0."""
 import numpy as np
 import pytest
 
 import casclik_amd as cc
 from casclik_amd import skills
 from casclik_amd import sym as cs
+
+from host_loops import controller_tick, rollout_loop
+from test_gpu_branches import _path_following_skill
+from time_skills import UR5_HOME
 
 pytestmark = pytest.mark.gpu
 
@@ -27,19 +31,6 @@ def _point_skill(fk):
         cons.append(cc.SetConstraint("limit_q_%d" % i, q[i], set_min=0.3 * lo[i], set_max=0.3 * hi[i], priority=i))
     return cc.SkillSpecification("point", t, q, constraints=cons)
 
-
-def _path_skill(fk):
-    """the path-following skill of tests/test_gpu_branches.py (one virtual variable)"""
-    t, q, s = cs.MX.sym("t"), cs.MX.sym("q", 6), cs.MX.sym("s", 1)
-    p = fk["T_fk"](q)[:3, 3]
-    p0, d = np.array([0.3, 0.1, 0.4]), np.array([0.2, -0.1, 0.05])
-    cons = [cc.EqualityConstraint("follow", p - (p0 + d * s), gain=2.0, priority=1, constraint_type="soft"),
-            cc.VelocityEqualityConstraint("progress", s, target=0.05, priority=0),
-            cc.SetConstraint("s_range", s, set_min=0.0, set_max=1.0, priority=2)]
-    return cc.SkillSpecification("path", t, q, virtual_var=s, constraints=cons)
-
-
-UR5_HOME = np.array([-50.0, -160.0, -110.0, -90.0, -90.0, 0.0]) * np.pi / 180.0
 
 # family -> (controller class, dt, max_speed, variant a rollout of 100 instances must be served by or None)
 FAMILIES = ["stack_values", "stack_image", "pose", "point", "virtual", "qp_box", "qp_walls"]
@@ -62,7 +53,7 @@ def _family(name, iiwa_fk, ur5_fk, monkeypatch):
     elif name == "point":
         spec, opts, fk, dt, vmax = _point_skill(ur5_fk), None, ur5_fk, 0.008, 0.4
     elif name == "virtual":
-        spec, opts, fk, dt, vmax = _path_skill(ur5_fk), None, ur5_fk, 0.01, 0.4
+        spec, opts, fk, dt, vmax = _path_following_skill(ur5_fk), None, ur5_fk, 0.01, 0.4
     else:
         from extern_skills import moe_box_skill
         spec, _ = moe_box_skill(ur5_fk, soft_walls=False)       # (hard walls: general rows, the image-reading QP rollout)
@@ -85,53 +76,6 @@ def _family(name, iiwa_fk, ur5_fk, monkeypatch):
 
     _made[name] = (ctrl, qp, dt, vmax, inputs)
     return _made[name]
-
-
-def _tick(ctrl, qp, t, q, x, y):
-    """one host tick -> (dq, dx | None, slack | None, flag)"""
-    res = ctrl.solve_batch(t, q, virtual_var=x, input_var=y)
-    if qp:
-        return res[0], res[1], res[2], res[3]
-    return res[0], res[1], None, res[2]
-
-
-def _host_loop(ctrl, qp, times, Q, X, y_of, dt, vmax, rk4=False):
-    """the yardstick: per tick (state after it, clamped velocity applied in it, slack, flag).  ``y_of(i)``: the
-    target of tick i.  ``rk4``: four solves per tick, all with the tick's target, staged as tests/test_gpu_rollout.py
-    does (integration_methods.py:17-23, each stage clamped; the virtual variables are never clamped)."""
-    q, x = Q.copy(), None if X is None else X.copy()
-    nq = q.shape[1]
-    out = []
-    for i, tv in enumerate(times):
-        y = y_of(i)
-        if not rk4:
-            dq, dx, sl, flag = _tick(ctrl, qp, float(tv), q, x, y)
-            dq = np.clip(dq, -vmax, vmax)
-        else:
-            z = q if x is None else np.hstack([q, x])
-            flags, sls = [], []
-
-            def f(tt, zz):
-                d, ddx, s_, fl = _tick(ctrl, qp, float(tt), zz[:, :nq], None if x is None else zz[:, nq:], y)
-                flags.append(fl)
-                sls.append(s_)
-                d = np.clip(d, -vmax, vmax)
-                return d if ddx is None else np.hstack([d, ddx])
-            k1 = f(tv, z)
-            k2 = f(tv + dt / 2, z + dt / 2 * k1)
-            k3 = f(tv + dt / 2, z + dt / 2 * k2)
-            k4 = f(tv + dt, z + dt * k3)
-            v = (k1 + 2 * k2 + 2 * k3 + k4) / 6.0
-            dq, dx = v[:, :nq], None if x is None else v[:, nq:]
-            sl = sls[-1]
-            flag = np.maximum.reduce(flags) if qp else flags[0]
-        q = q + dq * dt
-        if x is not None:
-            x = x + dx * dt
-        if qp and out:
-            flag = np.maximum(flag, out[-1]["flag"])        # (status: the worst so far)
-        out.append({"q": q.copy(), "x": None if x is None else x.copy(), "dq": dq, "dx": dx, "slack": sl, "flag": flag})
-    return out
 
 
 def _check_records(rec, host, k, qp, label):
@@ -168,7 +112,7 @@ def test_records_equal_the_host_loop_at_every_recorded_tick(iiwa_fk, ur5_fk, mon
     ctrl, qp, dt, vmax, inputs = _family(family, iiwa_fk, ur5_fk, monkeypatch)
     Q, X, Y = inputs(B)
     times = dt * np.arange(N_TICKS)
-    host = _host_loop(ctrl, qp, times, Q, X, lambda i: Y, dt, vmax)
+    host = rollout_loop(controller_tick(ctrl, qp), qp, times, Q, X, lambda i: Y, dt, vmax)
     plain = ctrl.rollout_batch(times, Q, input_var=Y, dt=dt, max_speed=vmax, virtual_var=X)
     for k in (1, 4, 12):
         res = ctrl.rollout_batch(times, Q, input_var=Y, dt=dt, max_speed=vmax, virtual_var=X, record_every=k)
@@ -230,7 +174,7 @@ def test_per_tick_target_matches_the_host_loop(iiwa_fk, ur5_fk, monkeypatch, fam
     n = 7
     times = dt * np.arange(n)
     Y3 = _moving(Y, n)
-    host = _host_loop(ctrl, qp, times, Q, X, lambda i: Y3[i], dt, vmax, rk4=method == "rk4")
+    host = rollout_loop(controller_tick(ctrl, qp), qp, times, Q, X, lambda i: Y3[i], dt, vmax, rk4=method == "rk4")
     res = ctrl.rollout_batch(times, Q, input_var=Y3, dt=dt, max_speed=vmax, method=method, record_every=3)
     assert len(res) == (5 if qp else 4)
     eq, ev = np.abs(res[0] - host[-1]["q"]).max(), np.abs(res[1] - host[-1]["dq"]).max()

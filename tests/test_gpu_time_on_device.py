@@ -11,6 +11,7 @@ from casclik_amd import _capi, skills
 from casclik_amd.controllers.base_controller import rollout_stage_times
 
 import time_skills
+from host_loops import oracle_tick, rollout_loop
 from tolerances import PINV_RTOL, QP_RTOL
 
 pytestmark = pytest.mark.gpu
@@ -126,33 +127,17 @@ def test_table_is_deterministic_and_keeps_the_container(table_ctrls):
 
 
 # ---- B3 ---------------------------------------------------------------------------------------------------------------
-def _host_loop(solve, times, Q, dt, vmax, method):
-    q = Q.copy()
-    f = lambda tt, qq: np.clip(solve(float(tt), qq), -vmax, vmax)      # noqa: E731
-    for tv in times:
-        if method == "rk4":
-            k1 = f(tv, q)
-            k2 = f(tv + dt / 2, q + dt / 2 * k1)
-            k3 = f(tv + dt / 2, q + dt / 2 * k2)
-            k4 = f(tv + dt, q + dt * k3)
-            v = (k1 + 2 * k2 + 2 * k3 + k4) / 6.0
-        else:
-            v = f(tv, q)
-        q = q + dt * v
-    return q, v
-
-
 @pytest.mark.parametrize("method", ["euler", "rk4"])
 def test_rollout_with_device_time(track, method):
     import torch
-    from oracle import clik_oracle
     spec, on, off = track
     assert on._time_kernel and off._time_kernel is None and on.kernel_name == off.kernel_name
     Q = _start(70, 8)
     n_ticks, vmax = 6, 0.4
     times = 3.0 + DT * np.arange(n_ticks)
     q_on, dq_on, mode_on = on.rollout_batch(times, Q, dt=DT, max_speed=vmax, method=method)
-    qo, vo = _host_loop(lambda t, q: clik_oracle.pinv_solve_batch(spec, None, t, q)[0], times, Q, DT, vmax, method)
+    orc = rollout_loop(oracle_tick(spec, False), False, times, Q, None, lambda i: None, DT, vmax, rk4=method == "rk4")[-1]
+    qo, vo = orc["q"], orc["dq"]
     print("%s: against the oracle loop |q| %.3g |dq| %.3g" % (method, np.abs(q_on - qo).max(), np.abs(dq_on - vo).max()))
     assert np.abs(q_on - qo).max() < 1e-9 and np.abs(dq_on - vo).max() < 1e-8
     q_off, dq_off, mode_off = off.rollout_batch(times, Q, dt=DT, max_speed=vmax, method=method)

@@ -4,7 +4,7 @@ in one launch: ``rollout_batch`` plain, recording, with a per-tick target, summa
 ``converge_batch``.
 
 The yardstick is the host loop the launch replaces: one ``solve_batch`` call per tick (rk4: per stage) that rewrites the
-fed entries between ticks (velocity_feedback_cases.host_loop), with the tolerances of tests/test_gpu_rollout_record.py:
+fed entries between ticks (host_loops.rollout_loop with the map), with the tolerances of tests/test_gpu_rollout_record.py:
 |q| < 1e-9, |dq| < 1e-7.  The skills are made so that the feed matters: on the oracle, feeding back against frozen entries
 moves q by 1.8e-3 (QP skill: an acceleration limit around the last velocity) and 1.1e-3 (pinv skill: a null-space pull
 towards it), so a launch that ignores the option misses Q_TOL by six orders of magnitude.  iiwa inputs from
@@ -16,6 +16,7 @@ import casclik_amd as cc
 from casclik_amd import jit, skills
 
 import converge_cases as K
+import host_loops as H
 import velocity_feedback_cases as V
 from test_gpu_constraint_summary import _check, _oracle, _reduce, _tolerances
 from test_gpu_rollout_record import Q_TOL, V_TOL
@@ -52,7 +53,8 @@ def _host(cases, iiwa_fk, name, method, B=100):
     if key not in _HOST:
         spec, ctrl, qp, fb = cases(name)
         Q, Y = V.iiwa_inputs(iiwa_fk, 100)
-        _HOST[key] = V.host_loop(V.controller_tick(ctrl, qp), TIMES, Q, None, lambda i: Y, fb, DT, rk4=method == "rk4")
+        _HOST[key] = H.rollout_loop(H.controller_tick(ctrl, qp), qp, TIMES, Q, None, lambda i: Y, DT, rk4=method == "rk4",
+                                    fb=fb)
     return [{k: (None if v is None else v[:B]) for k, v in h.items()} for h in _HOST[key]]
 
 
@@ -135,18 +137,17 @@ def test_every_tick_is_the_oracle_s_at_the_fed_target(cases, iiwa_fk, name):
     res = ctrl.rollout_batch(TIMES, Q, input_var=Y, dt=DT, record_every=1)
     rec = res[-1]
     close = qp_close if qp else pinv_close
+    tick = H.oracle_tick(spec, qp, {})
     q, y = Q, Y
     for k in range(N):
+        ref, _, _, flag = tick(float(TIMES[k]), q, None, y)
         if qp:
-            ref, _, _, status = V.clik_oracle.qp_solve_batch(spec, float(TIMES[k]), q, Y=y)
-            assert (status == 0).all()
-        else:
-            ref, _ = V.clik_oracle.pinv_solve_batch(spec, {}, float(TIMES[k]), q, Y=y)
+            assert (flag == 0).all()
         ok = close(rec["dq"][k], ref)
         print("%s tick %d: %s" % (name, k, dict(LAST)))
         assert ok, (name, k, dict(LAST))
         assert np.abs(rec["q"][k] - (q + rec["dq"][k] * DT)).max() < 1e-15 * 8
-        q, y = rec["q"][k], V.feed(Y, fb, rec["dq"][k])
+        q, y = rec["q"][k], H.feed(Y, fb, rec["dq"][k])
 
 
 # ---- 3: chunking ----------------------------------------------------------------------------------------------------------
@@ -158,7 +159,7 @@ def test_a_launch_is_two_launches_whose_second_is_fed_the_first_one_s_velocity(c
     kw = dict(dt=DT, method=method)
     whole = ctrl.rollout_batch(TIMES, Q, input_var=Y, **kw)
     first = ctrl.rollout_batch(TIMES[:4], Q, input_var=Y, **kw)
-    second = ctrl.rollout_batch(TIMES[4:], first[0], input_var=V.feed(Y, fb, first[1]), **kw)
+    second = ctrl.rollout_batch(TIMES[4:], first[0], input_var=H.feed(Y, fb, first[1]), **kw)
     if qp:
         # (the second launch's first tick is a cold solve, the whole launch's a hot one: the same minimiser to rounding)
         eq, ev = np.abs(whole[0] - second[0]).max(), np.abs(whole[1] - second[1]).max()
@@ -178,7 +179,7 @@ def test_a_per_tick_target_keeps_its_other_entries_and_loses_the_fed_ones(cases,
     Y3 = np.repeat(Y[None], N, axis=0)
     Y3[:, :, :3] += 0.002 * np.arange(N)[:, None, None] * rng.normal(size=(1, 100, 3))     # (the pose target drifts)
     Y3[1:, :, 7:] = rng.normal(scale=50.0, size=(N - 1, 100, 7))                           # (garbage where the feed goes)
-    host = V.host_loop(V.controller_tick(ctrl, qp), TIMES, Q, None, lambda i: Y3[i], fb, DT)
+    host = H.rollout_loop(H.controller_tick(ctrl, qp), qp, TIMES, Q, None, lambda i: Y3[i], DT, fb=fb)
     for B in BATCHES:
         res = ctrl.rollout_batch(TIMES, Q[:B], input_var=np.ascontiguousarray(Y3[:, :B]), dt=DT, record_every=1)
         hostB = [{k: (None if v is None else v[:B]) for k, v in h.items()} for h in host]
@@ -224,7 +225,7 @@ def test_the_summary_is_of_the_trajectory_the_recording_launch_returns(cases, ii
             err = np.abs(rec[key] - recd[-1][key]).max()
             assert err < (Q_TOL if key == "q" else V_TOL), (key, err)
         Qs = np.concatenate([Q[None], rec["q"][:-1]])
-        Ys = np.stack([Y] + [V.feed(Y, fb, rec["dq"][r]) for r in range(N - 1)])
+        Ys = np.stack([Y] + [H.feed(Y, fb, rec["dq"][r]) for r in range(N - 1)])
         orc = _oracle(spec, TIMES, Qs, None, Ys)
         tol = _tolerances(*orc)
         res = ctrl.rollout_batch(TIMES, Q, summary=True, summary_tol=tol, **kw)
@@ -246,7 +247,7 @@ def test_the_rate_of_a_virtual_variable_is_fed(cases, method):
     spec, ctrl, qp, fb = cases("path")
     assert ctrl.descriptor.n_x == 1 and fb == V.FB_PATH
     Q, X, Y = V.path_inputs(100)
-    host = V.host_loop(V.controller_tick(ctrl, False), TIMES, Q, X, lambda i: Y, fb, DT, rk4=method == "rk4")
+    host = H.rollout_loop(H.controller_tick(ctrl, False), False, TIMES, Q, X, lambda i: Y, DT, rk4=method == "rk4", fb=fb)
     # the feed is what the skill turns on: the parameter's rate follows ds_k = 0.5 ds_{k-1} + 0.002 from rest towards its
     # fixed point 0.004 (within 2^-11 of it after 11 ticks); with nothing fed it would stay at 0.002
     assert np.abs(host[0]["dx"] - 0.002).max() < 1e-6 and np.abs(host[-1]["dx"] - 0.004).max() < 1e-5
@@ -268,8 +269,8 @@ def test_a_launch_with_the_times_on_the_device_is_fed(cases, iiwa_fk):
     assert ctrl._time_kernel is not None and ctrl.descriptor.n_tslots > 0
     Q, Y = V.iiwa_inputs(iiwa_fk, 100)
     times = 0.3 + TIMES
-    host = V.host_loop(V.controller_tick(ctrl, False), times, Q, None, lambda i: Y, fb, DT)
-    frozen = V.host_loop(V.controller_tick(ctrl, False), times, Q, None, lambda i: Y, (-1,) * 7, DT)
+    host = H.rollout_loop(H.controller_tick(ctrl, False), False, times, Q, None, lambda i: Y, DT, fb=fb)
+    frozen = H.rollout_loop(H.controller_tick(ctrl, False), False, times, Q, None, lambda i: Y, DT, fb=(-1,) * 7)
     assert np.abs(frozen[-1]["q"] - host[-1]["q"]).max() > 1e-6            # (the feed matters here too)
     for tv in (times, torch.from_numpy(times).to(ctrl._device)):
         plain = ctrl.rollout_batch(tv, Q, input_var=Y, dt=DT)
@@ -282,7 +283,7 @@ def test_a_launch_with_the_times_on_the_device_is_fed(cases, iiwa_fk):
 # ---- 8: converge_batch ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("group", [1, 4])
 def test_converge_batch_feeds_the_ticks_it_integrates(cases, iiwa_fk, group):
-    """``ticks`` and ``status`` exactly, on every instance, against converge_cases.host_loop extended by the feed (the
+    """``ticks`` and ``status`` exactly, on every instance, against host_loops.converge_loop with the feed (the
     oracle; none of the 100 instances comes within MARGIN of its tolerance).  The state and the velocity at the stop are
     held to Q_TOL / V_TOL against the same loop with every pseudo-inverse taken through the SVD filter factors
     (exact_yardstick.dpinv_stable, the evaluation tolerances.py calls the stable one), and to Q_TOL / V_TOL plus the
@@ -296,11 +297,11 @@ def test_converge_batch_feeds_the_ticks_it_integrates(cases, iiwa_fk, group):
     spec, ctrl, qp, fb = cases("pinv")
     Q, Y = V.iiwa_inputs(iiwa_fk, 100)
     tol = K.tolerances(spec, {"tool_pose": 1e-5, "smooth": np.inf})
-    hq, hdq, hticks, hstatus, hres, sure = V.converge_host_loop(spec, Q, Y, fb, tol, 60)
+    hq, hdq, hticks, hstatus, hres, sure = H.converge_loop(spec, {}, Q, Y, tol, 60, fb=fb)
     print("host loop: ticks %d .. %d, status %s, sure %d of %d" % (hticks.min(), hticks.max(), np.bincount(hstatus),
                                                                    sure.sum(), sure.size))
     assert (hstatus == 0).all() and hticks.min() >= 1 and hticks.max() <= 14 and sure.all()
-    sq, sdq, sticks, sstatus, _, _ = V.converge_host_loop(spec, Q, Y, fb, tol, 60, pinv_fn=dpinv_stable)
+    sq, sdq, sticks, sstatus, _, _ = H.converge_loop(spec, {}, Q, Y, tol, 60, fb=fb, pinv_fn=dpinv_stable)
     assert np.array_equal(sticks, hticks) and np.array_equal(sstatus, hstatus)
     own_q, own_v = np.abs(hq - sq).max(), np.abs(hdq - sdq).max()
     print("the literal oracle's loop against its stable evaluation: |q| %.3g |dq| %.3g" % (own_q, own_v))
@@ -316,7 +317,7 @@ def test_converge_batch_feeds_the_ticks_it_integrates(cases, iiwa_fk, group):
             assert eq < Q_TOL and ev < V_TOL
             assert lq < Q_TOL + own_q and lv < V_TOL + own_v
         # the feed is seen: frozen at rest, the smoothing task pulls the null-space motion to zero instead
-        frozen = V.converge_host_loop(spec, Q, Y, (-1,) * 7, tol, 60)
+        frozen = H.converge_loop(spec, {}, Q, Y, tol, 60, fb=(-1,) * 7)
         assert np.abs(frozen[0] - hq).max() > 1e-6
     else:
         # groups of four copies of an instance: the copies arrive together, so the rule cancels nobody and every copy is

@@ -1,12 +1,11 @@
 """What the tests of ``options["velocity_feedback"]`` share and what needs no GPU: the skills that read the last velocity
-in ``input_var``, their maps, their inputs, and the host loops that rewrite the fed entries between ticks - of
-``solve_batch`` calls (the yardstick) and of oracle calls (the independent one)."""
+in ``input_var``, their maps and their inputs.  The host loops that rewrite the fed entries between ticks are those of
+tests/host_loops.py with the map given (``rollout_loop(..., fb=)``, ``converge_loop(..., fb=)``)."""
 import numpy as np
 
 import casclik_amd as cc
 from casclik_amd import skills
 from casclik_amd import sym as cs
-from oracle import clik_oracle
 
 import converge_cases as K
 
@@ -93,102 +92,3 @@ def iiwa_inputs(fk, B=100):
 def path_inputs(B=100):
     Q, X, _ = K.inputs("virtual", None, B)
     return Q, X, np.zeros((B, 1))
-
-
-def feed(Y, fb, v):
-    """Y with the fed entries rewritten from the velocities v [B, n_q + n_x]"""
-    Y = Y.copy()
-    for j, k in enumerate(fb):
-        if k >= 0:
-            Y[:, k] = v[:, j]
-    return Y
-
-
-def host_loop(tick, times, Q, X, y_of, fb, dt, vmax=0.0, rk4=False):
-    """The yardstick: one call of ``tick(t, q, x, y) -> (dq, dx | None, flag)`` per tick (rk4: per stage, all four with
-    the tick's target), the fed entries of the target rewritten between ticks from the velocity the last tick was
-    integrated with.  ``y_of(i)``: what the caller gives tick i; its fed entries count at tick 0 only.  Returns one dict
-    per tick: the state after it, the velocity applied in it, the flag (QP: the worst status so far)."""
-    q, x = Q.copy(), None if X is None else X.copy()
-    nq = q.shape[1]
-    clamp = (lambda d: np.clip(d, -vmax, vmax)) if vmax > 0.0 else (lambda d: d)
-    out, v_last = [], None
-    for i, tv in enumerate(times):
-        y = y_of(i) if v_last is None else feed(y_of(i), fb, v_last)
-        if not rk4:
-            dq, dx, flag = tick(float(tv), q, x, y)
-            dq = clamp(dq)
-        else:
-            z = q if x is None else np.hstack([q, x])
-            flags = []
-
-            def f(tt, zz):
-                d, ddx, fl = tick(float(tt), zz[:, :nq], None if x is None else zz[:, nq:], y)
-                flags.append(fl)
-                d = clamp(d)
-                return d if ddx is None else np.hstack([d, ddx])
-            k1 = f(tv, z)
-            k2 = f(tv + dt / 2, z + dt / 2 * k1)
-            k3 = f(tv + dt / 2, z + dt / 2 * k2)
-            k4 = f(tv + dt, z + dt * k3)
-            v = (k1 + 2 * k2 + 2 * k3 + k4) / 6.0
-            dq, dx = v[:, :nq], None if x is None else v[:, nq:]
-            flag = flags[0]
-        q = q + dq * dt
-        if x is not None:
-            x = x + dx * dt
-        v_last = dq if dx is None else np.hstack([dq, dx])
-        out.append({"q": q.copy(), "x": None if x is None else x.copy(), "dq": dq, "dx": dx, "flag": flag})
-    return out
-
-
-def controller_tick(ctrl, qp):
-    """``tick`` of ``host_loop`` on a controller's ``solve_batch``"""
-    def tick(t, q, x, y):
-        res = ctrl.solve_batch(t, q, virtual_var=x, input_var=y)
-        return (res[0], res[1], res[3]) if qp else (res[0], res[1], res[2])
-    return tick
-
-
-def oracle_tick(spec, qp, options=None):
-    """``tick`` of ``host_loop`` on the oracle (skills without virtual variables)"""
-    def tick(t, q, x, y):
-        assert x is None
-        if qp:
-            dq, _, _, status = clik_oracle.qp_solve_batch(spec, t, q, Y=y)
-            return dq[:, :q.shape[1]], None, status
-        dq, mode = clik_oracle.pinv_solve_batch(spec, options or {}, t, q, Y=y)
-        return dq[:, :q.shape[1]], None, mode
-    return tick
-
-
-def converge_host_loop(spec, Q, Y, fb, tol, max_ticks, dt=K.DT, pinv_fn=None):
-    """converge_cases.host_loop extended by the feed: an instance's tick that is integrated rewrites its fed entries,
-    a stopped instance keeps them.  ``pinv_fn``: the oracle's pseudo-inverse (None: its literal ``dpinv``).  Returns
-    ``(q, dq, ticks, status, residual, sure)``."""
-    B = Q.shape[0]
-    q, dq, Y = Q.copy(), np.zeros_like(Q), Y.copy()
-    ticks, status = np.zeros(B, dtype=np.int32), np.full(B, -1, dtype=np.int32)
-    residual, sure = np.zeros((B, tol.size)), np.ones(B, dtype=bool)
-    for r in range(max_ticks + 1):
-        go = np.nonzero(status < 0)[0]
-        if go.size == 0:
-            break
-        e, lo, hi, is_set = K.oracle_values(spec, 0.0, q[None, go], None, Y[go])
-        d = K.distances(e, lo, hi, is_set)[0]
-        residual[go] = d
-        sure[go] &= ~(np.abs(d - tol) < K.MARGIN).any(axis=1)
-        bad = ~np.isfinite(e[0]).all(axis=1)
-        with np.errstate(invalid="ignore"):
-            met = (d <= tol).all(axis=1)
-        st = np.where(bad, 4, np.where(met, 0, 1 if r == max_ticks else -1))
-        status[go] = st
-        ticks[go] = r
-        go = go[st < 0]
-        if go.size == 0:
-            continue
-        v = clik_oracle.pinv_solve_batch(spec, {}, 0.0, q[go], Y=Y[go], pinv_fn=pinv_fn)[0][:, :Q.shape[1]]
-        q[go] += v * dt
-        dq[go] = v
-        Y[go] = feed(Y[go], fb, v)
-    return q, dq, ticks, status, residual, sure
