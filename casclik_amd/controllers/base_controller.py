@@ -238,6 +238,15 @@ def rollout_records(n_ticks, record_every):
     return int(n_ticks) // int(record_every)
 
 
+def ring_depth_request(ring_depth):
+    """``ring_depth`` of ``resident_start`` as an int: 1 for plain ``[B, n]`` tensors, D > 1 for rings ``[D, B, n]``.
+    ValueError below 1."""
+    D = int(ring_depth)
+    if D < 1:
+        raise ValueError("ring_depth must be at least 1")
+    return D
+
+
 def per_tick_input(input_var, n_ticks, n_y):
     """Is ``input_var`` one target per tick?  True for a ``[n_ticks, B, n_y]`` array or tensor (tick i reads record
     i); False for what a rollout took before (``[B, n_y]``, a vector, None).  ValueError for a 3-D ``input_var`` whose
@@ -444,7 +453,8 @@ def trajectory_rows(val, width, what, lead=None):
 class BaseController(object):
     """What a device controller is apart from its mathematics.  A controller class names the C entry points that make
     and free its handle (``_create_fn`` / ``_destroy_fn``), returns their options structure from ``_c_options(descriptor)``, says
-    in ``_slot_results()`` how many doubles and int32 its ``solve()`` brings back, and has ``skill_spec`` and
+    in ``_slot_results()`` how many doubles and int32 its ``solve()`` brings back, names its tick entry points
+    (``_tick_fn`` / ``_tick_t_fn``) and the outputs behind the velocities (``_rollout_tail``), and has ``skill_spec`` and
     ``options``; ``_create_handle()`` then gives it ``_lib``, ``_handle``, ``_device`` and ``descriptor``, which every
     other helper here works from."""
     controller_type = "BaseController"
@@ -519,6 +529,24 @@ class BaseController(object):
             except RuntimeError as exc:
                 warnings.warn("%s: %s" % (instead, str(exc)[:limit]))
                 return None
+
+    def _setup_shape_kernel(self, attach):
+        """``kernel_name`` of the handle; where no ahead-of-time shape serves the skill ("dynamic" / "none") and kernels
+        may be instantiated, ``attach()`` - the controller's ``jit.attach*`` call - instantiates one for its structure
+        (the reference JIT-compiles its functions at this point too)."""
+        self.kernel_name = getattr(self._lib, "clik_%s_kernel_name" % self._kind)(self._handle).decode()
+        if self.kernel_name in ("dynamic", "none") and self._want_jit():
+            name = self._attach_or_warn(
+                attach, "run-time kernel instantiation failed, using the built-in dynamic-shape kernel", 400)
+            if name:
+                self.kernel_name = name
+
+    def _setup_value_kernel(self, wanted, attach, instead):
+        """``value_kernel``: the tag of the kernel with the skill's own numbers compiled in - one more hipcc run at set-up,
+        ``attach()`` - when the controller's rule says it is ``wanted`` and kernels may be instantiated; else None."""
+        self.value_kernel = None
+        if wanted and self._want_jit():
+            self.value_kernel = self._attach_or_warn(attach, instead, 300)
 
     def _require_generated_code_kernel(self):
         """Constraints outside the row-table family exist only as generated code inside a run-time instantiated
@@ -739,6 +767,100 @@ class BaseController(object):
                 if o is not None:
                     o.index_copy_(0, rows, r)
 
+    # -- outputs of a batch -------------------------------------------------------------------------------------
+    def _tail(self):
+        """``_rollout_tail`` with this skill's widths: ``[(name, width | None: one number per instance, dtype name)]``"""
+        d = self.descriptor
+        return [(name, None if width is None else getattr(d, width), dtype) for name, width, dtype in self._rollout_tail]
+
+    def _batch_outputs(self, B, lead=(), given=None, skip=(), init=False):
+        """``[dQ, dX, *tail]`` of a batch of ``B`` instances on the controller's device: the velocities ``[B, n_q]`` and
+        ``[B, n_x]``, then what ``_rollout_tail`` names, in its order; None for a width of 0 and for a name in ``skip``.
+        ``lead``: the leading dimensions of a ring, ``(D,)``.  ``given``: the caller's own tensors, ``{"out": ..., tail
+        name: ...}`` (None: not given) - checked as ``out`` / ``<name>_out`` (``check_out_tensor``) and used in place as
+        they are.  New tensors are uninitialised, or with ``init`` zeros and, the int32 ones, -1: no tick wrote there."""
+        torch = _torch()
+        d, dev = self.descriptor, self._device
+        given = given or {}
+        outs = []
+        for name, width, dtype in [("out", d.n_q, "float64"), ("dx", d.n_x, "float64")] + self._tail():
+            shape = tuple(lead) + ((B,) if width is None else (B, width))
+            t = given.get(name)
+            if t is not None:
+                check_out_tensor(t, shape, dtype, dev, "out" if name == "out" else name + "_out")
+            elif width != 0 and name not in skip:
+                if init:
+                    t = torch.full(shape, -1 if dtype == "int32" else 0.0, dtype=getattr(torch, dtype), device=dev)
+                else:
+                    t = torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
+            outs.append(t)
+        return outs
+
+    # -- ticks --------------------------------------------------------------------------------------------------
+    # Every tick entry point takes (handle, B, time terms, q, x, y, dq, dx, *tail, *extra, stream): the controller
+    # names the entry for one stamp per batch and the one for a stamp per instance, and what ``extra`` is.
+    _tick_fn = _tick_t_fn = None
+
+    def _tick_batch(self, time_var, robot_var, virtual_var, input_var, again, given=None, skip=(), extra=None):
+        """One tick of a batch, the body of ``solve_batch``: marshal the inputs (``_batch_inputs``), the time
+        (``_instance_times``) and the outputs (``_batch_outputs`` of ``given`` and ``skip``), launch ``_tick_fn`` or -
+        a stamp per instance - ``_tick_t_fn`` on torch's current stream, and return ``(dQ, dX, *tail)`` in the caller's
+        container.  ``extra(B)`` returns the controller's extra launch arguments and the tensors they carry, ``(args,
+        carried)``.  A skill on the dynamic fallback kernel has no per-instance-time variant (``CLIK_EUNSUPPORTED``): one
+        launch per distinct stamp (``_solve_per_stamp``) of ``again(t, Q, X, Y, *carried)``, the controller's own
+        single-stamp call, which returns the outputs followed by the carried rows."""
+        self._require_handle()
+        torch = _torch()
+        d, dev = self.descriptor, self._device
+        Q, X, Y, B, was_np = self._batch_inputs(robot_var, virtual_var, input_var)
+        time_var, T, stamps = self._instance_times(time_var, B)
+        outs = tuple(self._batch_outputs(B, given=given, skip=skip))
+        args, carried = extra(B) if extra else ((), ())
+        with torch.cuda.device(dev):
+            if T is not None:
+                fn, tt = getattr(self._lib, self._tick_t_fn), ptr(T)
+            else:
+                fn, (_, tt) = getattr(self._lib, self._tick_fn), _capi.tterms_arg(d.time_terms(time_var))
+            rc = fn(self._handle, B, tt, ptr(Q), ptr(X), ptr(Y), *map(ptr, outs), *args, current_stream(dev))
+        if T is not None and stamps is not None and rc == _capi.CLIK_EUNSUPPORTED:
+            self._solve_per_stamp(stamps, again, (Q, X, Y) + carried, outs + carried)
+            rc = 0
+        _capi.check(self._lib, rc)
+        return self._to_caller(outs, was_np)
+
+    def _bind_tick(self, robot_var, input_var, virtual_var, given=None, extra=None):
+        """The body of ``bind_batch``: marshal once, return ``tick(time_var=0.0, stream_handle=None)`` - per call the
+        time terms (unless the skill has no time slots), the stream, ONE launch of ``_tick_fn`` and a status check.
+        ``extra(B)`` returns ``(first, later, carried)``: the controller's extra launch arguments of the first call and of
+        every later one - and of the first as well once ``tick.primed`` is set - and the tensors they carry.
+        ``tick.tensors`` holds everything the launch reads and writes (``Q, X, Y, dQ, dX, *tail, *carried``),
+        ``tick.out`` the velocities and ``tick.<name>`` each output of ``_rollout_tail``."""
+        self._require_handle()
+        d, dev = self.descriptor, self._device
+        Q, X, Y, B, _ = self._batch_inputs(robot_var, virtual_var, input_var)
+        outs = self._batch_outputs(B, given=given)
+        first, later, carried = extra(B) if extra else ((), (), ())
+        fn, handle, lib = getattr(self._lib, self._tick_fn), self._handle, self._lib
+        args = tuple(map(ptr, (Q, X, Y, *outs)))
+        static_tt = _capi.tterms_arg(np.zeros(0)) if d.n_tslots == 0 else None
+        ticked = [extra is None]        # (without extra arguments there is no first call to tell from the others)
+
+        def tick(time_var=0.0, stream_handle=None):
+            tt, ttp = static_tt if static_tt is not None else _capi.tterms_arg(d.time_terms(time_var))
+            sh = stream_handle if stream_handle is not None else current_stream(dev)
+            rc = fn(handle, B, ttp, *args, *(later if ticked[0] or tick.primed else first), sh)
+            ticked[0] = True
+            if rc != 0:
+                _capi.check(lib, rc)
+
+        if extra is not None:
+            tick.primed = False
+        tick.tensors = (Q, X, Y, *outs) + tuple(carried)
+        tick.out = outs[0]
+        for (name, _, _), t in zip(self._rollout_tail, outs[2:]):
+            setattr(tick, name, t)
+        return tick
+
     # -- rollouts -----------------------------------------------------------------------------------------------
     def _rollout_times(self, time_vars, dt, method):
         """``(n_ticks, stages, tterms)`` of a rollout: ``stages`` is 1 for ``method="rk4"`` (the right-hand side at t,
@@ -878,14 +1000,11 @@ class BaseController(object):
         else:
             n_ticks, stages, (tt, ttp) = self._rollout_times(time_vars, dt, method)
         want_sum, tol = rollout_summary_request(summary, summary_tol, n_ticks, sum(int(t["m"]) for t in d.tasks))
-        tail = [(name, None if width is None else getattr(d, width), dtype) for name, width, dtype in self._rollout_tail]
+        tail = self._tail()
         Q, X, Y, B, was_np, y_per_tick, rec = self._rollout_io(
             robot_var, virtual_var, input_var, n_ticks, record_every, record_out,
             [("q", d.n_q, "float64"), ("dq", d.n_q, "float64"), ("x", d.n_x, "float64"), ("dx", d.n_x, "float64")] + tail)
-        dQ = torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
-        dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
-        last = [None if width == 0 else torch.empty((B,) if width is None else (B, width), dtype=getattr(torch, dtype),
-                                                    device=dev) for _, width, dtype in tail]
+        dQ, dX, *last = self._batch_outputs(B)
         args = (self._handle, B, n_ticks, stages, float(dt), float(max_speed), ttp,
                 ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX), *map(ptr, last), current_stream(dev))
         # (without records or per-tick targets: 0, 0 and NULL for every record)
@@ -1145,20 +1264,19 @@ class BaseController(object):
         if B < 1:
             raise ValueError("converge_batch needs at least one instance")
         group = converge_group_request(group, B)
-        dQ =torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
-        dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
-        mode = torch.empty((B,), dtype=torch.int32, device=dev)
+        # (of the tail only its last output, the one number per instance - the mode, the QP's worst status - is returned:
+        # the entry takes it first and NULL for the others, the QP's slack)
+        dQ, dX, *unused, mode = self._batch_outputs(B, skip=[name for name, _, _ in self._rollout_tail[:-1]])
         info = {"ticks": torch.empty((B,), dtype=torch.int32, device=dev),
                 "status": torch.empty((B,), dtype=torch.int32, device=dev),
                 "residual": torch.empty((B, m_tot), dtype=torch.float64, device=dev)}
         tol_dev = torch.from_numpy(tol_np).to(dev)
         tt, ttp = _capi.tterms_arg(d.time_terms(float(scalar_of(time_var))))
         self._require_converge_kernel(group)
-        extra = (None,) if self._kind == "qp" else ()       # (QP: slack, not returned)
         with torch.cuda.device(dev):
             rc = getattr(self._lib, "clik_%s_converge_batch" % self._kind)(
                 self._handle, B, max_ticks, float(dt), float(max_speed), float(min_step), ttp, ptr(Q), ptr(X), ptr(Y),
-                ptr(dQ), ptr(dX), ptr(mode), *extra, ptr(tol_dev), ptr(info["ticks"]), ptr(info["status"]),
+                ptr(dQ), ptr(dX), ptr(mode), *map(ptr, unused), ptr(tol_dev), ptr(info["ticks"]), ptr(info["status"]),
                 ptr(info["residual"]), current_stream(dev))
         _capi.check(self._lib, rc)
         outs = (Q, X, dQ, dX, mode) if d.n_x > 0 else (Q, dQ, mode)
@@ -1221,6 +1339,52 @@ class BaseController(object):
         return res, out
 
     # -- resident ticks -----------------------------------------------------------------------------------------
+    def _resident_inputs(self, robot_var, input_var, D):
+        """``(Q, Y | None, B, lead)`` of a resident launch: ``robot_var`` / ``input_var`` are read in place by a kernel
+        that stays, so each must be a contiguous float64 device tensor ``[B, n]``, with ``ring_depth`` D > 1 a ring
+        ``[D, B, n]`` (``lead = (D,)``).  The batch size is ``robot_var``'s and ``input_var`` must have THAT many rows -
+        the kernel reads ``y[row * n_y + ...]`` for every row of ``robot_var`` -; a tensor of the wrong rank is a
+        ValueError, not an IndexError.  A skill without ``input_var`` ignores what is passed for it."""
+        torch = _torch()
+        d = self.descriptor
+        B = None
+        lead = (D,) if D > 1 else ()
+        for name, tns, n in (("robot_var", robot_var, d.n_q), ("input_var", input_var, d.n_y)):
+            if n == 0:
+                continue
+            if not isinstance(tns, torch.Tensor) or not tns.is_cuda or tns.dtype != torch.float64 or not tns.is_contiguous():
+                raise ValueError("resident ticks: %s must be a contiguous float64 device tensor (read in place)" % name)
+            if tns.dim() != len(lead) + 2:
+                raise ValueError("resident ticks with ring_depth %d: %s must have %d dimensions %s, got shape %s"
+                                 % (D, name, len(lead) + 2, "[D, B, n]" if D > 1 else "[B, n]", list(tns.shape)))
+            if B is None:
+                B = int(tns.shape[-2])
+            want = lead + (B, n)
+            if tuple(tns.shape) != tuple(want):
+                raise ValueError("resident ticks with ring_depth %d: %s must have shape %s, got %s"
+                                 % (D, name, list(want), list(tns.shape)))
+        return robot_var, (input_var if d.n_y > 0 else None), B, lead
+
+    def _resident_run(self, entry, robot_var, input_var, D, n_ticks, time_var, timeout_s, stream, publish_ahead,
+                      given=None, extra=()):
+        """The body of ``resident_start``: check the inputs (``_resident_inputs``), make the outputs - zeros, -1 for the
+        int32 ones, or the caller's ``given`` as they are (``_batch_outputs``) -, set the run up (``_resident_setup``)
+        and launch ``entry(handle, B, n_ticks, time terms, q, y, dq, *tail, ticket, done, *extra, timeout_s, stream)``.
+        Returns the dict of the run: ``ticket``, ``done``, ``waves``, ``out``, each output of ``_rollout_tail`` under
+        its name, ``stream`` and ``keep`` (what must outlive the kernel)."""
+        Q, Y, B, lead = self._resident_inputs(robot_var, input_var, D)
+        dQ, _, *tail = self._batch_outputs(B, lead, given, skip=("dx",), init=True)
+        waves = getattr(self._lib, "clik_%s_resident_waves" % self._kind)(self._handle, B)
+        ticket, done, stream, (tt, ttp) = self._resident_setup(waves, D, publish_ahead, stream, time_var)
+        with _torch().cuda.device(self._device):
+            rc = getattr(self._lib, entry)(self._handle, B, int(n_ticks), ttp, ptr(Q), ptr(Y), ptr(dQ), *map(ptr, tail),
+                                           ptr(ticket), ptr(done), *extra, float(timeout_s),
+                                           C.c_void_p(stream.cuda_stream))
+        _capi.check(self._lib, rc)
+        run = {"ticket": ticket, "done": done, "waves": waves, "out": dQ, "stream": stream, "keep": (Q, Y, tt)}
+        run.update(zip((name for name, _, _ in self._rollout_tail), tail))
+        return run
+
     def _resident_setup(self, waves, ring_depth, publish_ahead, stream, time_var):
         """What a resident launch needs beside its tensors: the ``ticket`` (64 int32 words: [0] in_seq, [16] ring
         depth, [32] stop, [48] waves, [49] ticks_done), one ``done`` slot per wave, the launch stream (a new one by
@@ -1285,9 +1449,34 @@ class BaseController(object):
         slot = getattr(self, "_slot", None)
         if slot is None:
             slot = self._slot = SingleSlot(self._device, nq + nx + ny, *self._slot_results())
+            # where the launch writes dq, dx and the tail, in that order: the doubles one after the other, then the int32
+            ptrs, at, n_int = [], 0, 0
+            for _, width, dtype in [("out", nq, "float64"), ("dx", nx, "float64")] + self._tail():
+                if dtype == "int32":
+                    ptrs.append(slot.int_ptr(n_int))
+                    n_int += 1
+                else:
+                    ptrs.append(slot.out_ptr(at) if width else None)
+                    at += width
+            slot.result_ptrs = tuple(ptrs)
         slot.in_np[:nq] = q
         if nx:
             slot.in_np[nq:nq + nx] = x
         if ny:
             slot.in_np[nq + nx:nq + nx + ny] = y
         return slot, slot.in_ptr(0), slot.in_ptr(nq) if nx else None, slot.in_ptr(nq + nx) if ny else None
+
+    def _solve_slot(self, time_var, robot_var, virtual_var, input_var, extra=None):
+        """The launch of a single-instance ``solve()``: B = 1 through the persistent pinned / device staging (one copy
+        each way), ``_tick_fn`` with the results written into the slot at ``slot.result_ptrs`` and the controller's
+        extra launch arguments ``extra(slot)``.  Returns the slot once its results are on the host: the doubles in
+        ``slot.out_f`` (dq, dx, then the tail's), the int32 in ``slot.out_i``."""
+        slot, pq, px, py = self._stage_solve(robot_var, virtual_var, input_var)
+        tt, ttp = _capi.tterms_arg(self.descriptor.time_terms(float(scalar_of(time_var))))
+        with slot.guard():
+            stream = slot.begin()
+            rc = getattr(self._lib, self._tick_fn)(self._handle, 1, ttp, pq, px, py, *slot.result_ptrs,
+                                                   *(extra(slot) if extra else ()), stream)
+            _capi.check(self._lib, rc)
+            slot.download()
+        return slot

@@ -10,7 +10,6 @@ of scanning modes in Python (:512-556).
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 
 import numpy as np
@@ -18,8 +17,7 @@ import numpy as np
 from .. import _capi
 from .. import sym as cs
 from ..lowering import DYN_MAX_M
-from .base_controller import (BaseController, current_stream, ptr, to_device_matrix, check_out_tensor, scalar_of,
-                              _torch)
+from .base_controller import BaseController, ring_depth_request, _torch
 
 
 class PseudoInverseController(BaseController):
@@ -39,6 +37,7 @@ class PseudoInverseController(BaseController):
     _create_fn, _destroy_fn = "clik_pinv_create", "clik_pinv_destroy"
     _kind = "pinv"
     _rollout_tail = (("mode", None, "int32"),)
+    _tick_fn, _tick_t_fn = "clik_pinv_solve_batch", "clik_pinv_solve_batch_t"
 
     def __init__(self, skill_spec, options=None):
         self._handle = None
@@ -183,35 +182,25 @@ class PseudoInverseController(BaseController):
     def setup_problem_functions(self):
         """Lower the skill and create the device handle (replaces the
         per-mode ``cs.Function`` JIT of pseudo_inverse.py:453-483)."""
+        from .. import jit
         self.get_problem_expressions()
         cdesc, copts = self._create_handle()
         handle, d = self._handle, self.descriptor
-        self.kernel_name = self._lib.clik_pinv_kernel_name(handle).decode()
         # no AOT shape for this skill: instantiate the static templates for it
-        want_jit = self._want_jit()
-        if self.kernel_name in ("dynamic", "none") and want_jit:
-            from .. import jit
-            name = self._attach_or_warn(
-                lambda: jit.attach(self._lib, handle, cdesc, copts, extern=d.extern_source()),
-                "run-time kernel instantiation failed, using the built-in dynamic-shape kernel", 400)
-            if name:
-                self.kernel_name = name
+        self._setup_shape_kernel(lambda: jit.attach(self._lib, handle, cdesc, copts, extern=d.extern_source()))
         # The skill's kernels with its own numbers compiled in (the reference's JIT compiles its functions with the
         # constants of the skill too): for the config-3 family (four lanes per instance at small batches, one lane per
         # instance above) and for single-mode skills without virtual variables (BASELINE configs 1 and 2: one lane
         # per instance, no LDS) - one more hipcc run at set-up.  function_opts["jit_values"] = False or
         # CLIK_JIT_VALUES=0 keeps the kernels that read the skill image from memory.
-        self.value_kernel = None
         jv = self.options["function_opts"].get("jit_values", None)
         env_jv = os.environ.get("CLIK_JIT_VALUES", "1")
         variant1 = self._lib.clik_pinv_kernel_variant(handle, 1).decode()
         single_mode = (d.n_x == 0 and d.n_sets == 0 and variant1 == "lane")
-        wanted = (variant1 == "team4" or single_mode) and jv is not False
-        if want_jit and wanted and env_jv != "0":
-            from .. import jit
-            self.value_kernel = self._attach_or_warn(
-                lambda: jit.attach_values(self._lib, handle, cdesc, copts, extern=d.extern_source()),
-                "value-specialised kernel could not be built, using the image-reading one", 300)
+        wanted = (variant1 == "team4" or single_mode) and jv is not False and env_jv != "0"
+        self._setup_value_kernel(
+            wanted, lambda: jit.attach_values(self._lib, handle, cdesc, copts, extern=d.extern_source()),
+            "value-specialised kernel could not be built, using the image-reading one")
         if self.kernel_name == "none":
             raise NotImplementedError(
                 "a constraint of this skill has more rows than the built-in kernels are wide (%d) and no "
@@ -261,33 +250,10 @@ class PseudoInverseController(BaseController):
         batch (its time terms travel by value with the launch).  Returns (robot_vel [B,n_q], virtual_vel | None,
         mode [B]) in the container type of ``robot_var``.  The launch is asynchronous on
         torch's current stream when tensors are passed."""
-        self._require_handle()
-        torch = _torch()
-        d = self.descriptor
-        dev = self._device
-        Q, X, Y, B, was_np = self._batch_inputs(robot_var, virtual_var, input_var)
-        time_var, T, stamps = self._instance_times(time_var, B)
-        check_out_tensor(out, (B, d.n_q), "float64", dev, "out")
-        dQ = out if out is not None else torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
-        dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
-        mode = torch.empty((B,), dtype=torch.int32, device=dev) if return_mode else None
-        with torch.cuda.device(dev):
-            if T is not None:
-                rc = self._lib.clik_pinv_solve_batch_t(self._handle, B, ptr(T), ptr(Q), ptr(X), ptr(Y), ptr(dQ),
-                                                       ptr(dX), ptr(mode), current_stream(dev))
-            else:
-                tt, ttp = _capi.tterms_arg(d.time_terms(time_var))
-                rc = self._lib.clik_pinv_solve_batch(
-                    self._handle, B, ttp, ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX),
-                    ptr(mode), current_stream(dev))
-        if T is not None and stamps is not None and rc == _capi.CLIK_EUNSUPPORTED:
-            self._solve_per_stamp(
-                stamps, lambda tv, Qk, Xk, Yk: self.solve_batch(tv, Qk, virtual_var=Xk, input_var=Yk,
-                                                                return_mode=return_mode),
-                (Q, X, Y), (dQ, dX, mode))
-            rc = 0
-        _capi.check(self._lib, rc)
-        return self._to_caller((dQ, dX, mode), was_np)
+        def one_stamp(tv, Qk, Xk, Yk):
+            return self.solve_batch(tv, Qk, virtual_var=Xk, input_var=Yk, return_mode=return_mode)
+        return self._tick_batch(time_var, robot_var, virtual_var, input_var, one_stamp, given={"out": out},
+                                skip=() if return_mode else ("mode",))
 
     def bind_batch(self, robot_var, input_var=None, virtual_var=None, out=None,
                    mode_out=None, stream=None):
@@ -295,36 +261,7 @@ class PseudoInverseController(BaseController):
         kernel launch per call with no per-call tensor handling (the lean path
         for control loops, CUDA-graph capture and benchmarks).  All tensors
         must already live on the controller's device."""
-        self._require_handle()
-        torch = _torch()
-        d = self.descriptor
-        dev = self._device
-        Q, X, Y, B, _ = self._batch_inputs(robot_var, virtual_var, input_var)
-        check_out_tensor(out, (B, d.n_q), "float64", dev, "out")
-        check_out_tensor(mode_out, (B,), "int32", dev, "mode_out")
-        dQ = out if out is not None else torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
-        dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
-        mode = mode_out if mode_out is not None else torch.empty((B,), dtype=torch.int32, device=dev)
-        fn = self._lib.clik_pinv_solve_batch
-        handle = self._handle
-        args = (ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX), ptr(mode))
-        keep = (Q, X, Y, dQ, dX, mode)
-        static_tt = None
-        if d.n_tslots == 0:
-            static_tt = _capi.tterms_arg(np.zeros(0))
-        lib = self._lib
-
-        def tick(time_var=0.0, stream_handle=None):
-            tt, ttp = static_tt if static_tt is not None else _capi.tterms_arg(d.time_terms(time_var))
-            sh = stream_handle if stream_handle is not None else current_stream(dev)
-            rc = fn(handle, B, ttp, args[0], args[1], args[2], args[3], args[4], args[5], sh)
-            if rc != 0:
-                _capi.check(lib, rc)
-
-        tick.tensors = keep
-        tick.out = dQ
-        tick.mode = mode
-        return tick
+        return self._bind_tick(robot_var, input_var, virtual_var, given={"out": out, "mode": mode_out})
 
     # -- resident ticks ----------------------------------------------------------------------------------------
     def resident_start(self, robot_var, input_var, n_ticks, time_var=0.0, out=None, mode_out=None, timeout_s=2.0,
@@ -345,68 +282,23 @@ class PseudoInverseController(BaseController):
         share a hardware queue with ``stream``: ``resident_feed_stream()`` hands one out (asking for another priority is
         not enough: which queue a new stream lands on depends on how many the process has made)."""
         self._require_handle()
-        torch = _torch()
-        d = self.descriptor
-        dev = self._device
-        D = int(ring_depth)
-        if D < 1:
-            raise ValueError("ring_depth must be at least 1")
+        D = ring_depth_request(ring_depth)
         if self._feedback is not None and integrate_dt > 0.0:
             raise NotImplementedError(
                 "options['velocity_feedback'] has no resident form: resident_start(integrate_dt > 0) keeps the state in "
                 "the kernel and would feed nothing back (resident ticks fed by a producer are unchanged: the caller "
                 "owns input_var there)")
-        if not isinstance(robot_var, torch.Tensor) or not robot_var.is_cuda:
-            raise ValueError("resident ticks: robot_var must be a device tensor")
-        if D > 1:
-            # a RING of D slots: robot_var [D, B, n_q], input_var [D, B, n_y]; tick k reads and writes slot (k - 1) % D
-            # (include/clik.h): a producer fills slot k % D while tick k runs and publishes ticket k + 1 ahead
-            if robot_var.dim() != 3 or robot_var.shape[0] != D or robot_var.shape[2] != d.n_q:
-                raise ValueError("resident ticks with ring_depth %d: robot_var must have shape [%d, B, %d]" % (D, D, d.n_q))
-            B = int(robot_var.shape[1])
-            Q = robot_var
-            Y = None
-            if d.n_y > 0:
-                if (not isinstance(input_var, torch.Tensor) or not input_var.is_cuda
-                        or tuple(input_var.shape) != (D, B, d.n_y)):
-                    raise ValueError("resident ticks with ring_depth %d: input_var must be a device tensor of shape "
-                                     "[%d, %d, %d]" % (D, D, B, d.n_y))
-                Y = input_var
-            for tns in (Q, Y):
-                if tns is not None and (tns.dtype != torch.float64 or not tns.is_contiguous()):
-                    raise ValueError("resident ticks: inputs must be contiguous float64 device tensors (read in place)")
-            out_shape, mode_shape = (D, B, d.n_q), (D, B)
+        # (one instance may come as a 1-D device tensor: what to_device_matrix made of it here, kept)
+        robot_var, input_var = (v.reshape(1, -1) if D == 1 and isinstance(v, _torch().Tensor) and v.dim() == 1 else v
+                                for v in (robot_var, input_var))
+        if integrate_dt > 0.0:
+            # the state stays in the kernel (include/clik.h): q is read at tick 1 and stepped with
+            # q += clamp(dq, +-max_speed) * integrate_dt after every tick; only input_var comes from outside
+            entry, extra = "clik_pinv_resident_run_state", (float(integrate_dt), float(max_speed))
         else:
-            Q, _ = to_device_matrix(robot_var, d.n_q, dev, "robot_var")
-            B = Q.shape[0]
-            Y = None
-            if d.n_y > 0:
-                if not isinstance(input_var, torch.Tensor) or not input_var.is_cuda:
-                    raise ValueError("resident ticks: input_var must be a device tensor")
-                Y, _ = to_device_matrix(input_var, d.n_y, dev, "input_var", B)
-            if Q.data_ptr() != robot_var.data_ptr() or (Y is not None and Y.data_ptr() != input_var.data_ptr()):
-                raise ValueError("resident ticks: inputs must be contiguous float64 device tensors (they are read in place)")
-            out_shape, mode_shape = (B, d.n_q), (B,)
-        check_out_tensor(out, out_shape, "float64", dev, "out")
-        check_out_tensor(mode_out, mode_shape, "int32", dev, "mode_out")
-        dQ = out if out is not None else torch.zeros(out_shape, dtype=torch.float64, device=dev)
-        mode = mode_out if mode_out is not None else torch.full(mode_shape, -1, dtype=torch.int32, device=dev)
-        waves = self._lib.clik_pinv_resident_waves(self._handle, B)
-        ticket, done, stream, (tt, ttp) = self._resident_setup(waves, D, publish_ahead, stream, time_var)
-        with torch.cuda.device(dev):
-            if integrate_dt > 0.0:
-                # the state stays in the kernel (include/clik.h): q is read at tick 1 and stepped with
-                # q += clamp(dq, +-max_speed) * integrate_dt after every tick; only input_var comes from outside
-                rc = self._lib.clik_pinv_resident_run_state(
-                    self._handle, B, int(n_ticks), ttp, ptr(Q), ptr(Y), ptr(dQ), ptr(mode), ptr(ticket), ptr(done),
-                    float(integrate_dt), float(max_speed), float(timeout_s), C.c_void_p(stream.cuda_stream))
-            else:
-                rc = self._lib.clik_pinv_resident_run(self._handle, B, int(n_ticks), ttp, ptr(Q), ptr(Y), ptr(dQ),
-                                                      ptr(mode), ptr(ticket), ptr(done), float(timeout_s),
-                                                      C.c_void_p(stream.cuda_stream))
-        _capi.check(self._lib, rc)
-        return {"ticket": ticket, "done": done, "waves": waves, "out": dQ, "mode": mode, "stream": stream,
-                "keep": (Q, Y, tt)}
+            entry, extra = "clik_pinv_resident_run", ()
+        return self._resident_run(entry, robot_var, input_var, D, n_ticks, time_var, timeout_s, stream, publish_ahead,
+                                  given={"out": out, "mode": mode_out}, extra=extra)
 
     def solve(self, time_var, robot_var, virtual_var=None, input_var=None,
               warmstart_robot_vel_var=None, warmstart_virtual_vel_var=None,
@@ -414,18 +306,9 @@ class PseudoInverseController(BaseController):
         """Single-instance tick with the reference's signature and return
         convention (pseudo_inverse.py:512-556): ``(robot_vel DM n x 1,
         virtual_vel DM | None, None)`` and ``self.current_mode``."""
-        # B = 1 through persistent pinned / device staging (one copy each way)
-        slot, pq, px, py = self._stage_solve(robot_var, virtual_var, input_var)
+        slot = self._solve_slot(time_var, robot_var, virtual_var, input_var)
         d = self.descriptor
         nq, nx = d.n_q, d.n_x
-        tt, ttp = _capi.tterms_arg(d.time_terms(float(scalar_of(time_var))))
-        with slot.guard():
-            stream = slot.begin()
-            rc = self._lib.clik_pinv_solve_batch(
-                self._handle, 1, ttp, pq, px, py, slot.out_ptr(0), slot.out_ptr(nq) if nx else None,
-                slot.int_ptr(0), stream)
-            _capi.check(self._lib, rc)
-            slot.download()
         self.current_mode = int(slot.out_i[0])
         cntrl_rob = cs.DM(slot.out_f[:nq].copy())
         cntrl_virt = None

@@ -13,7 +13,6 @@ ignored.
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 
 import numpy as np
@@ -22,7 +21,7 @@ from .. import _capi
 from .. import sym as cs
 from ..constraints import (EqualityConstraint, SetConstraint, VelocityEqualityConstraint,
                            VelocitySetConstraint)
-from .base_controller import (BaseController, current_stream, ptr, check_out_tensor, scalar_of, _torch)
+from .base_controller import BaseController, current_stream, ptr, ring_depth_request, _torch
 
 
 def _weights(weights, n, what):
@@ -68,6 +67,8 @@ class ReactiveQPController(BaseController):
     _create_fn, _destroy_fn = "clik_qp_create", "clik_qp_destroy"
     _kind = "qp"
     _rollout_tail = (("slack", "n_slack", "float64"), ("status", None, "int32"))
+    # (both tick entries take the working sets and the hot-start flag behind the outputs)
+    _tick_fn, _tick_t_fn = "clik_qp_solve_batch_hot", "clik_qp_solve_batch_t"
 
     def __init__(self, skill_spec, robot_var_weights=None,
                  virtual_var_weights=None, slack_var_weights=None, options=None):
@@ -147,22 +148,15 @@ class ReactiveQPController(BaseController):
     def setup_problem_functions(self):
         """Lower the skill, upload it with the cost weights (replaces the
         H/A/Blb/Bub ``cs.Function`` objects of reactive_qp.py:262-298)."""
+        from .. import jit
         cdesc, _ = self._create_handle()
         handle, d = self._handle, self.descriptor
         self._slot_calls = 0        # (solve() hot-starts from its previous call: none yet on this handle)
         self.n_qp_vars = self._lib.clik_qp_n_vars(handle)
         self.n_qp_rows = self._lib.clik_qp_n_rows(handle)
-        self.kernel_name = self._lib.clik_qp_kernel_name(handle).decode()
         # no AOT shape for this skill: instantiate the shape-specialised QP kernel for
         # it (the reference JIT-compiles its H/A/lbA/ubA functions here, reactive_qp.py:283-298)
-        want_jit = self._want_jit()
-        if self.kernel_name in ("dynamic", "none") and want_jit:
-            from .. import jit
-            name = self._attach_or_warn(
-                lambda: jit.attach_qp(self._lib, handle, cdesc, extern=d.extern_source()),
-                "run-time kernel instantiation failed, using the built-in dynamic-shape kernel", 400)
-            if name:
-                self.kernel_name = name
+        self._setup_shape_kernel(lambda: jit.attach_qp(self._lib, handle, cdesc, extern=d.extern_source()))
         self._require_generated_code_kernel()
         if self.kernel_name == "none":
             raise NotImplementedError(
@@ -175,18 +169,16 @@ class ReactiveQPController(BaseController):
         # value-specialised kernel needs no LDS at all (config 4: 11.3 against 12.9 us per tick, hot-started 5.6
         # against 7.4); for other skills on request (function_opts["jit_values"] = True or CLIK_JIT_VALUES=2: it keeps
         # the LDS work area and gains about 1 %); function_opts["jit_values"] = False or CLIK_JIT_VALUES=0: never.
-        self.value_kernel = None
         jv = (self.options.get("function_opts") or {}).get("jit_values", None)
         env_jv = os.environ.get("CLIK_JIT_VALUES", "1")
         # (skills with more than ten state variables - two arms - keep the image-reading kernel unless asked: the
         # value-specialised one holds its n x n factor in registers)
         wanted = jv is True or env_jv == "2" or (jv is None and self._lib.clik_qp_is_box_family(handle) == 1
                                                   and d.n_state <= 10)
-        if want_jit and wanted and jv is not False and env_jv != "0" and self.kernel_name not in ("dynamic", "none"):
-            from .. import jit
-            self.value_kernel = self._attach_or_warn(
-                lambda: jit.attach_qp_values(self._lib, handle, cdesc, extern=d.extern_source()),
-                "value-specialised QP kernel could not be built, using the image-reading one", 300)
+        wanted = wanted and jv is not False and env_jv != "0" and self.kernel_name not in ("dynamic", "none")
+        self._setup_value_kernel(
+            wanted, lambda: jit.attach_qp_values(self._lib, handle, cdesc, extern=d.extern_source()),
+            "value-specialised QP kernel could not be built, using the image-reading one")
         self._setup_time_kernel()
 
     def _c_options(self, d):
@@ -498,46 +490,12 @@ class ReactiveQPController(BaseController):
         with forward kinematics and without virtual variables; ``NotImplementedError`` otherwise.  Returns a dict with
         ``ticket``, ``done``, ``waves``, ``out`` (velocities), ``slack``, ``status`` and the launch ``stream``."""
         self._require_handle()
-        torch = _torch()
-        d = self.descriptor
-        dev = self._device
-        D = int(ring_depth)
-        if D < 1:
-            raise ValueError("ring_depth must be at least 1")
-        if d.n_x > 0:
+        D = ring_depth_request(ring_depth)
+        if self.descriptor.n_x > 0:
             raise NotImplementedError("resident QP ticks: skills without virtual variables only")
-        # (the batch size is robot_var's; input_var must have THAT many rows - the kernel reads y[row * n_y + ...] for
-        # every row of robot_var - and a tensor of the wrong rank is a ValueError, not an IndexError)
-        B = None
-        lead = (D,) if D > 1 else ()
-        for name, tns, n in (("robot_var", robot_var, d.n_q), ("input_var", input_var, d.n_y)):
-            if n == 0:
-                continue
-            if not isinstance(tns, torch.Tensor) or not tns.is_cuda or tns.dtype != torch.float64 or not tns.is_contiguous():
-                raise ValueError("resident ticks: %s must be a contiguous float64 device tensor (read in place)" % name)
-            if tns.dim() != len(lead) + 2:
-                raise ValueError("resident ticks with ring_depth %d: %s must have %d dimensions %s, got shape %s"
-                                 % (D, name, len(lead) + 2, "[D, B, n]" if D > 1 else "[B, n]", list(tns.shape)))
-            if B is None:
-                B = int(tns.shape[-2])
-            want = lead + (B, n)
-            if tuple(tns.shape) != tuple(want):
-                raise ValueError("resident ticks with ring_depth %d: %s must have shape %s, got %s"
-                                 % (D, name, list(want), list(tns.shape)))
-        dQ = torch.zeros(lead + (B, d.n_q), dtype=torch.float64, device=dev)
-        slack = torch.zeros(lead + (B, d.n_slack), dtype=torch.float64, device=dev) if d.n_slack > 0 else None
-        status = torch.full(lead + (B,), -1, dtype=torch.int32, device=dev)
-        waves = self._lib.clik_qp_resident_waves(self._handle, B)
-        ticket, done, stream, (tt, ttp) = self._resident_setup(waves, D, publish_ahead, stream, time_var)
-        with torch.cuda.device(dev):
-            rc = self._lib.clik_qp_resident_run(self._handle, B, int(n_ticks), ttp, ptr(robot_var),
-                                                ptr(input_var) if d.n_y > 0 else None, ptr(dQ), ptr(slack), ptr(status),
-                                                ptr(ticket), ptr(done), float(timeout_s), C.c_void_p(stream.cuda_stream))
-        if rc == _capi.CLIK_EUNSUPPORTED:
-            raise NotImplementedError(self._lib.clik_last_error().decode())
-        _capi.check(self._lib, rc)
-        return {"ticket": ticket, "done": done, "waves": waves, "out": dQ, "slack": slack, "status": status,
-                "stream": stream, "keep": (robot_var, input_var, tt)}
+        # (a skill the resident kernel does not serve: NotImplementedError with the library's reason, from the launch)
+        return self._resident_run("clik_qp_resident_run", robot_var, input_var, D, n_ticks, time_var, timeout_s, stream,
+                                  publish_ahead)
 
     def solve_batch(self, time_var, robot_var, virtual_var=None, input_var=None,
                     return_status=True, hot_set=None, use_hot=True):
@@ -556,40 +514,18 @@ class ReactiveQPController(BaseController):
         ``options["time_on_device"]`` the per-instance time terms come from the time kernel (``time_terms_batch``) and
         ``time_var`` may be a device tensor, read in place; a skill on the dynamic fallback kernel keeps the host
         evaluation, and so does one stamp for the whole batch (its time terms travel by value with the launch)."""
-        self._require_handle()
-        torch = _torch()
-        d = self.descriptor
-        dev = self._device
-        Q, X, Y, B, was_np = self._batch_inputs(robot_var, virtual_var, input_var)
-        time_var, T, stamps = self._instance_times(time_var, B)
-        dQ = torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
-        dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
-        ns = d.n_slack
-        SL = torch.empty((B, ns), dtype=torch.float64, device=dev) if ns else None
-        status = torch.empty((B,), dtype=torch.int32, device=dev) if return_status else None
-        if hot_set is not None and (hot_set.dtype != torch.int32 or hot_set.numel() != B or not hot_set.is_cuda):
-            raise ValueError("hot_set must be an int32 device tensor with one entry per instance")
-        hot_flag = 1 if (hot_set is not None and use_hot) else 0
-        with torch.cuda.device(dev):
-            if T is not None:
-                rc = self._lib.clik_qp_solve_batch_t(
-                    self._handle, B, ptr(T), ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX),
-                    ptr(SL), ptr(status), ptr(hot_set), hot_flag, current_stream(dev))
-            else:
-                tt, ttp = _capi.tterms_arg(d.time_terms(time_var))
-                rc = self._lib.clik_qp_solve_batch_hot(
-                    self._handle, B, ttp, ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX),
-                    ptr(SL), ptr(status), ptr(hot_set), hot_flag, current_stream(dev))
-        if T is not None and stamps is not None and rc == _capi.CLIK_EUNSUPPORTED:
-            # (a skill on the dynamic fallback kernel: one launch per distinct time stamp; each group's working sets
-            # travel through its own rows of hot_set)
-            def one_stamp(tv, Qk, Xk, Yk, hs):
-                return self.solve_batch(tv, Qk, virtual_var=Xk, input_var=Yk, return_status=return_status,
-                                        hot_set=hs, use_hot=use_hot) + (hs,)
-            self._solve_per_stamp(stamps, one_stamp, (Q, X, Y, hot_set), (dQ, dX, SL, status, hot_set))
-            rc = 0
-        _capi.check(self._lib, rc)
-        return self._to_caller((dQ, dX, SL, status), was_np)
+        def hot_args(B):
+            if hot_set is not None and (hot_set.dtype != _torch().int32 or hot_set.numel() != B or not hot_set.is_cuda):
+                raise ValueError("hot_set must be an int32 device tensor with one entry per instance")
+            return (ptr(hot_set), 1 if (hot_set is not None and use_hot) else 0), (hot_set,)
+
+        # (a skill on the dynamic fallback kernel: one launch per distinct time stamp; each group's working sets
+        # travel through its own rows of hot_set)
+        def one_stamp(tv, Qk, Xk, Yk, hs):
+            return self.solve_batch(tv, Qk, virtual_var=Xk, input_var=Yk, return_status=return_status,
+                                    hot_set=hs, use_hot=use_hot) + (hs,)
+        return self._tick_batch(time_var, robot_var, virtual_var, input_var, one_stamp,
+                                skip=() if return_status else ("status",), extra=hot_args)
 
     def bind_batch(self, robot_var, input_var=None, virtual_var=None, out=None, hot_start=False, hot_set=None):
         """Pre-bind device tensors and return ``tick(time_var=0.0)``: one kernel
@@ -598,39 +534,19 @@ class ReactiveQPController(BaseController):
         tensor [B] to keep them in - several bound ticks given the SAME tensor hand their working sets on to each other
         (a loop whose ticks rotate through input buffers), and a tick bound with one is hot-started from its first call
         on when the tensor already holds sets (``tick.primed = True``)."""
-        self._require_handle()
-        torch = _torch()
-        d = self.descriptor
-        dev = self._device
-        Q, X, Y, B, _ = self._batch_inputs(robot_var, virtual_var, input_var)
-        check_out_tensor(out, (B, d.n_q), "float64", dev, "out")
-        dQ = out if out is not None else torch.empty((B, d.n_q), dtype=torch.float64, device=dev)
-        dX = torch.empty((B, d.n_x), dtype=torch.float64, device=dev) if d.n_x else None
-        SL = torch.empty((B, d.n_slack), dtype=torch.float64, device=dev) if d.n_slack else None
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-        fn, handle, lib = self._lib.clik_qp_solve_batch_hot, self._handle, self._lib
-        if hot_set is not None:
-            if not (isinstance(hot_set, torch.Tensor) and hot_set.is_cuda and hot_set.dtype == torch.int32
-                    and hot_set.is_contiguous() and tuple(hot_set.shape) == (B,)):
+        def hot_args(B):
+            torch = _torch()
+            hot = hot_set
+            if hot is not None and not (isinstance(hot, torch.Tensor) and hot.is_cuda and hot.dtype == torch.int32
+                                        and hot.is_contiguous() and tuple(hot.shape) == (B,)):
                 raise ValueError("hot_set must be a contiguous int32 device tensor of shape [%d]" % B)
-            hot_start = True
-        hot = hot_set if hot_set is not None else (torch.zeros((B,), dtype=torch.int32, device=dev) if hot_start else None)
-        args = (ptr(Q), ptr(X), ptr(Y), ptr(dQ), ptr(dX), ptr(SL), ptr(status), ptr(hot))
-        static_tt = _capi.tterms_arg(np.zeros(0)) if d.n_tslots == 0 else None
-        state = {"ticks": 0}
+            if hot is None and hot_start:
+                hot = torch.zeros((B,), dtype=torch.int32, device=self._device)
+            # (the first call is a cold solve that leaves its working sets in `hot`; every later one starts from them)
+            return (ptr(hot), 0), (ptr(hot), 1 if hot is not None else 0), (hot,)
 
-        def tick(time_var=0.0, stream_handle=None):
-            tt, ttp = static_tt if static_tt is not None else _capi.tterms_arg(d.time_terms(time_var))
-            sh = stream_handle if stream_handle is not None else current_stream(dev)
-            rc = fn(handle, B, ttp, *args, 1 if (hot is not None and (state["ticks"] > 0 or tick.primed)) else 0, sh)
-            state["ticks"] += 1
-            if rc != 0:
-                _capi.check(lib, rc)
-
-        tick.primed = False
-        tick.tensors = (Q, X, Y, dQ, dX, SL, status, hot)
-        tick.hot_set = hot
-        tick.out, tick.slack, tick.status = dQ, SL, status
+        tick = self._bind_tick(robot_var, input_var, virtual_var, given={"out": out}, extra=hot_args)
+        tick.hot_set = tick.tensors[-1]
         return tick
 
     def qp_data_batch(self, time_var, robot_var, virtual_var=None, input_var=None):
@@ -663,18 +579,11 @@ class ReactiveQPController(BaseController):
         reference surfaces qpOASES failure as a CasADi RuntimeError)."""
         # B = 1 through persistent pinned / device staging (one copy each way); the working set of
         # the previous call hot-starts this one, like the reference's stateful qpOASES instance
-        slot, pq, px, py = self._stage_solve(robot_var, virtual_var, input_var)
+        # (the working set lives in the slot's second int32, behind the status)
+        slot = self._solve_slot(time_var, robot_var, virtual_var, input_var,
+                                lambda slot: (slot.int_ptr(1), 1 if self._slot_calls > 0 else 0))
         d = self.descriptor
         nq, nx, ns = d.n_q, d.n_x, d.n_slack
-        tt, ttp = _capi.tterms_arg(d.time_terms(float(scalar_of(time_var))))
-        with slot.guard():
-            stream = slot.begin()
-            rc = self._lib.clik_qp_solve_batch_hot(
-                self._handle, 1, ttp, pq, px, py, slot.out_ptr(0), slot.out_ptr(nq) if nx else None,
-                slot.out_ptr(nq + nx) if ns else None, slot.int_ptr(0), slot.int_ptr(1),
-                1 if self._slot_calls > 0 else 0, stream)
-            _capi.check(self._lib, rc)
-            slot.download()
         self._slot_calls += 1
         status = int(slot.out_i[0])
         if status != 0:

@@ -573,3 +573,185 @@ def test_solve_staging_helpers():
             ctrl.solve(0.0, np.zeros(3), virtual_var=[0.0], input_var=np.zeros(3))
         with pytest.raises(RuntimeError, match="setup"):
             ctrl.solve(0.0, np.zeros(3), virtual_var=[0.0], input_var=np.zeros(2))
+
+
+def _soft_qp_controller():
+    """a QP controller whose skill has slack (six rows) and no virtual variables, lowered, on torch's CPU device"""
+    import torch
+    ctrl = cc.ReactiveQPController(skill_spec=skills.qp_skill())
+    ctrl.descriptor = lower_skill(ctrl.skill_spec)
+    ctrl._device = torch.device("cpu")
+    assert (ctrl.descriptor.n_x, ctrl.descriptor.n_slack) == (0, 6)
+    return ctrl
+
+
+def test_batch_outputs_follow_the_tail_table():
+    """BaseController._batch_outputs: dQ, dX, then the outputs `_rollout_tail` names, in its order - pinv `mode`, QP
+    `slack`, `status` -, None for a width of 0 and for a skipped name; a leading ring dimension; a given tensor checked
+    and used in place; the initial fill of a resident run (zeros, -1 for int32) only where asked for, never into a
+    given tensor"""
+    import torch
+    pinv, qp = _plumbing_controllers()
+    soft = _soft_qp_controller()
+    assert [n for n, _, _ in pinv._tail()] == ["mode"] and [n for n, _, _ in qp._tail()] == ["slack", "status"]
+    assert soft._tail() == [("slack", 6, "float64"), ("status", None, "int32")]
+
+    def shapes(outs):
+        return [None if t is None else (tuple(t.shape), str(t.dtype).replace("torch.", "")) for t in outs]
+    assert shapes(pinv._batch_outputs(5)) == [((5, 3), "float64"), ((5, 1), "float64"), ((5,), "int32")]
+    assert shapes(qp._batch_outputs(5)) == [((5, 3), "float64"), ((5, 1), "float64"), None, ((5,), "int32")]
+    assert shapes(soft._batch_outputs(5)) == [((5, 7), "float64"), None, ((5, 6), "float64"), ((5,), "int32")]
+    assert shapes(pinv._batch_outputs(5, skip=("mode",))) == [((5, 3), "float64"), ((5, 1), "float64"), None]
+    assert shapes(soft._batch_outputs(5, skip=("status", "dx"))) == [((5, 7), "float64"), None, ((5, 6), "float64"), None]
+    assert shapes(soft._batch_outputs(5, lead=(2,))) == [((2, 5, 7), "float64"), None, ((2, 5, 6), "float64"),
+                                                         ((2, 5), "int32")]
+    for ctrl in (pinv, qp, soft):
+        assert all(t is None or t.device == torch.device("cpu") for t in ctrl._batch_outputs(3))
+    # given tensors: used in place, as they are
+    out, mode_out = torch.full((2, 5, 3), 7.0, dtype=torch.float64), torch.full((2, 5), 5, dtype=torch.int32)
+    dQ, dX, mode = pinv._batch_outputs(5, (2,), {"out": out, "mode": mode_out}, init=True)
+    assert dQ is out and mode is mode_out and bool((out == 7.0).all()) and bool((mode_out == 5).all())
+    assert bool((dX == 0.0).all())
+    dQ, dX, mode = pinv._batch_outputs(5, given={"out": None, "mode": None}, init=True)
+    assert bool((dQ == 0.0).all()) and bool((mode == -1).all())
+    dQ, _, slack, status = soft._batch_outputs(4, (3,), init=True)
+    assert bool((dQ == 0.0).all()) and bool((slack == 0.0).all()) and bool((status == -1).all())
+    with pytest.raises(ValueError, match=r"out must have shape \(5, 3\), got \(4, 3\)"):
+        pinv._batch_outputs(5, given={"out": torch.zeros(4, 3, dtype=torch.float64)})
+    with pytest.raises(ValueError, match="mode_out must be torch.int32"):
+        pinv._batch_outputs(5, given={"mode": torch.zeros(5, dtype=torch.int64)})
+    with pytest.raises(ValueError, match=r"out must have shape \(2, 5, 3\)"):
+        pinv._batch_outputs(5, (2,), {"out": torch.zeros(5, 3, dtype=torch.float64)})
+    with pytest.raises(ValueError, match="out must be contiguous"):
+        pinv._batch_outputs(5, given={"out": torch.zeros(3, 5, dtype=torch.float64).T})
+
+
+class _FakeEntries(object):
+    """stands in for the library: every entry point records (name, arguments) and returns what `rc(name)` says"""
+
+    def __init__(self, rc=lambda name: 0):
+        self.calls, self._rc = [], rc
+
+    def clik_last_error(self):
+        return b"not served"
+
+    def __getattr__(self, name):
+        def entry(*args):
+            self.calls.append((name, args))
+            return self._rc(name)
+        return entry
+
+
+def _addresses(args):
+    """launch arguments with pointers as addresses"""
+    import ctypes
+    return [a.value if isinstance(a, ctypes.c_void_p) else a for a in args]
+
+
+@pytest.fixture
+def fake_launches(monkeypatch):
+    """the two controllers of `_plumbing_controllers` with a recording library, a handle, no device guard and "STREAM"
+    as torch's current stream: their tick methods then run on CPU tensors"""
+    import contextlib
+    import torch
+    from casclik_amd.controllers import base_controller
+    monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
+    monkeypatch.setattr(base_controller, "current_stream", lambda dev: "STREAM")
+    ctrls = _plumbing_controllers()
+    for ctrl in ctrls:
+        ctrl._lib, ctrl._handle = _FakeEntries(), "HANDLE"
+    yield ctrls
+    for ctrl in ctrls:
+        ctrl._handle = None      # (nothing to destroy)
+
+
+def _cpu_batch(B=4):
+    import torch
+    rng = np.random.default_rng(2)
+    return tuple(torch.from_numpy(rng.normal(size=(B, n))) for n in (3, 1, 2))
+
+
+def test_tick_launch_argument_order(fake_launches):
+    """solve_batch of both controllers: (handle, B, time terms | T, q, x, y, dq, dx, *tail, *extra, stream) - pinv
+    `mode` and no extra; QP `slack`, `status`, then the working sets and the hot-start flag - on the single-stamp entry,
+    or with one stamp per instance on the `_t` entry"""
+    import ctypes
+    pinv, qp = fake_launches
+    Q, X, Y = _cpu_batch()
+    addr = lambda *ts: [None if t is None else t.data_ptr() for t in ts]      # noqa: E731
+    out = Q.new_empty((4, 3))
+    dq, dx, mode = pinv.solve_batch(0.25, Q, virtual_var=X, input_var=Y, out=out)
+    (name, args), = pinv._lib.calls
+    assert name == "clik_pinv_solve_batch" and dq is out
+    assert np.array_equal(np.ctypeslib.as_array(args[2], (4,)), pinv.descriptor.time_terms(0.25))
+    assert _addresses(args[:2] + args[3:]) == ["HANDLE", 4] + addr(Q, X, Y, out, dx, mode) + ["STREAM"]
+    pinv._lib.calls.clear()
+    dq, dx, mode = pinv.solve_batch(np.array([0.1, 0.3, 0.1, 0.7]), Q, virtual_var=X, input_var=Y, return_mode=False)
+    (name, args), = pinv._lib.calls
+    assert name == "clik_pinv_solve_batch_t" and mode is None and isinstance(args[2], ctypes.c_void_p)
+    assert _addresses(args[:2] + args[3:]) == ["HANDLE", 4] + addr(Q, X, Y, dq, dx, None) + ["STREAM"]
+    # the QP: the plumbing skill has no slack (NULL), no working sets are given (NULL, flag 0)
+    dq, dx, slack, status = qp.solve_batch(0.25, Q, virtual_var=X, input_var=Y)
+    (name, args), = qp._lib.calls
+    assert name == "clik_qp_solve_batch_hot" and slack is None
+    assert _addresses(args[:2] + args[3:]) == ["HANDLE", 4] + addr(Q, X, Y, dq, dx, None, status) + [None, 0, "STREAM"]
+    qp._lib.calls.clear()
+    dq, dx, slack, status = qp.solve_batch([0.1, 0.3, 0.1, 0.7], Q, virtual_var=X, input_var=Y, return_status=False)
+    (name, args), = qp._lib.calls
+    assert name == "clik_qp_solve_batch_t" and status is None
+    assert _addresses(args[:2] + args[3:]) == ["HANDLE", 4] + addr(Q, X, Y, dq, dx, None, None) + [None, 0, "STREAM"]
+
+
+def test_tick_launch_falls_back_to_one_launch_per_stamp(fake_launches):
+    """an entry without a per-instance-time variant (CLIK_EUNSUPPORTED from the `_t` entry): the controller's own
+    single-stamp call once per distinct stamp, on that stamp's rows; any other refusal is raised"""
+    from casclik_amd import _capi
+    Q, X, Y = _cpu_batch(5)
+    times = np.array([0.3, 0.1, 0.3, 0.7, 0.1])
+    for ctrl, single in zip(fake_launches, ("clik_pinv_solve_batch", "clik_qp_solve_batch_hot")):
+        ctrl._lib = _FakeEntries(lambda name: _capi.CLIK_EUNSUPPORTED if name.endswith("_t") else 0)
+        res = ctrl.solve_batch(times, Q, virtual_var=X, input_var=Y)
+        assert tuple(res[0].shape) == (5, 3) and tuple(res[-1].shape) == (5,)
+        assert [(name, args[1]) for name, args in ctrl._lib.calls] == [(single + "_t" if "pinv" in single else
+                                                                        "clik_qp_solve_batch_t", 5), (single, 2), (single, 2),
+                                                                       (single, 1)]
+        ctrl._lib = _FakeEntries(lambda name: _capi.CLIK_EUNSUPPORTED)
+        with pytest.raises(NotImplementedError, match="not served"):
+            ctrl.solve_batch(0.3, Q, virtual_var=X, input_var=Y)
+
+
+def test_bound_tick_launch_arguments_and_attributes(fake_launches):
+    """bind_batch: the same argument order, marshalled once; the tick's attributes; the QP's hot-start flag is 0 at the
+    first call and 1 from then on, or 1 from the first call of a primed tick"""
+    import torch
+    pinv, qp = fake_launches
+    Q, X, Y = _cpu_batch()
+    addr = lambda *ts: [None if t is None else t.data_ptr() for t in ts]      # noqa: E731
+    mode_out = torch.zeros(4, dtype=torch.int32)
+    tick = pinv.bind_batch(Q, input_var=Y, virtual_var=X, mode_out=mode_out)
+    assert sorted(vars(tick)) == ["mode", "out", "tensors"] and tick.mode is mode_out
+    assert addr(*tick.tensors) == addr(Q, X, Y, tick.out, tick.tensors[4], mode_out) and len(tick.tensors) == 6
+    tick(0.25)
+    tick(0.5, stream_handle="OTHER")
+    assert [name for name, _ in pinv._lib.calls] == ["clik_pinv_solve_batch"] * 2
+    for (_, args), t, stream in zip(pinv._lib.calls, (0.25, 0.5), ("STREAM", "OTHER")):
+        assert np.array_equal(np.ctypeslib.as_array(args[2], (4,)), pinv.descriptor.time_terms(t))
+        assert _addresses(args[:2] + args[3:]) == ["HANDLE", 4] + addr(*tick.tensors) + [stream]
+    for hot_start, primed, flags in ((False, False, [0, 0, 0]), (True, False, [0, 1, 1]), (True, True, [1, 1, 1])):
+        qp._lib.calls.clear()
+        tick = qp.bind_batch(Q, input_var=Y, virtual_var=X, hot_start=hot_start)
+        assert sorted(vars(tick)) == ["hot_set", "out", "primed", "slack", "status", "tensors"]
+        assert tick.primed is False and tick.slack is None and (tick.hot_set is not None) == hot_start
+        assert len(tick.tensors) == 8 and tick.tensors[7] is tick.hot_set and tick.tensors[6] is tick.status
+        if hot_start:
+            assert tick.hot_set.dtype == torch.int32 and tuple(tick.hot_set.shape) == (4,) and not tick.hot_set.any()
+        tick.primed = primed
+        for _ in flags:
+            tick()
+        for (name, args), flag in zip(qp._lib.calls, flags):
+            assert name == "clik_qp_solve_batch_hot"
+            assert _addresses(args[:2] + args[3:]) == ["HANDLE", 4] + addr(*tick.tensors) + [flag, "STREAM"]
+    qp._lib = _FakeEntries(lambda name: -1)
+    tick = qp.bind_batch(Q, input_var=Y, virtual_var=X)
+    with pytest.raises(ValueError, match="not served"):
+        tick()
