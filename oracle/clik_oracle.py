@@ -34,7 +34,8 @@ NOT resolved by any stored output, because no notebook exercises the difference 
 reading above and on the fixtures made by the reference's own Python over the stand-in casadi, nothing else):
     the 1e-12 margins of the tangent cones and which side the boundary belongs to (D4, D5): measure-zero events
     the multidimensional cone's corner rule against the row-wise 1-D rule (:222-252): the stored runs never leave
-        the box through a corner
+        the box through a corner.  The fixtures do: `*_stack_corner` and `iiwa_taskbox_corner` (429 corner states of the
+        reference's run; tests/test_cone_pins.py states which wrong corner rules they reject)
     an active set that would push back instead of freezing its rows (D2): < 0.3 px on every stored run
     converge_final_set_to_max (D3), a leading VelocityEqualityConstraint, pinv_method "standard" away from
         singularities: 0 uses in the notebooks
@@ -480,9 +481,14 @@ def _sym_cond(A):
     return float(hi / lo) if lo > 0.0 else float("inf")
 
 
-def in_tangent_cone_1d(e, set_min, set_max, dexpr, eps=1e-12):
+def in_tangent_cone_1d(e, set_min, set_max, dexpr, eps=1e-12, strict_inside=False):
     """pseudo_inverse.py:162-185 (boundary counts as inside, 1e-12 margin; `eps` is that margin - only the tests that
-    state what the stored figures resolve pass another)."""
+    state what the stored figures resolve pass another; `strict_inside` gives it the multidimensional function's inside
+    test `e - min >= eps`, quirk D5 the other way round - a deliberate deviation for tests/test_cone_pins.py only)."""
+    if strict_inside:
+        if e - set_min >= eps and e - set_max <= eps:
+            return True
+        return bool(dexpr > 0.0) if e - set_min < eps else bool(dexpr < 0.0)
     if set_min - e < eps:
         if e - set_max < eps:
             return True
@@ -490,9 +496,16 @@ def in_tangent_cone_1d(e, set_min, set_max, dexpr, eps=1e-12):
     return bool(dexpr > 0.0)
 
 
-def in_tangent_cone_multidim(e, set_min, set_max, dexpr, eps=1e-12, loose_inside=False):
-    """pseudo_inverse.py:222-252 (`eps`, `loose_inside`: deliberate deviations for the resolution tests only -
-    `loose_inside` is the 1-D function's inside test `min - e < eps`, quirk D5)."""
+CORNER_RULES = (None, "rowwise", "never", "gt", "cos40", "cos50", "sign0_plus", "sign0_minus")
+
+
+def in_tangent_cone_multidim(e, set_min, set_max, dexpr, eps=1e-12, loose_inside=False, rule=None):
+    """pseudo_inverse.py:222-252 (`eps`, `loose_inside`, `rule`: deliberate deviations for the resolution tests only -
+    `loose_inside` is the 1-D function's inside test `min - e < eps`, quirk D5; `rule` names a wrong reading of the
+    corner branch (:229-245): "rowwise" asks only out_dir . de < 0 at a corner as anywhere else, "never" lets no corner
+    state count as going in, "gt" turns the comparison with cos(pi/4) round, "cos40" / "cos50" move that threshold by
+    five degrees, "sign0_plus" / "sign0_minus" take sign(0) as +1 / -1 where a row sits exactly on its bound)."""
+    assert rule in CORNER_RULES, rule
     le = e - set_min
     ue = e - set_max
     if loose_inside:
@@ -501,23 +514,43 @@ def in_tangent_cone_multidim(e, set_min, set_max, dexpr, eps=1e-12, loose_inside
         inside = bool(np.all(le >= eps) and np.all(ue <= eps))
     if inside:
         return True
-    out_dir = (np.sign(le) + np.sign(ue)) / 2.0
-    corner = bool(np.all(np.sign(le) == np.sign(ue)))
+    sle, sue = np.sign(le), np.sign(ue)
+    if rule in ("sign0_plus", "sign0_minus"):
+        zero = 1.0 if rule == "sign0_plus" else -1.0
+        sle, sue = np.where(le == 0.0, zero, sle), np.where(ue == 0.0, zero, sue)
+    out_dir = (sle + sue) / 2.0
+    corner = bool(np.all(sle == sue))
     od = float(out_dir.dot(dexpr))
-    if corner:
-        if od < 0.0:
+    if corner and rule != "rowwise":
+        if od < 0.0 and rule != "never":
             dists = (np.linalg.norm(dexpr) + 1e-10) * np.linalg.norm(out_dir)
-            return bool(abs(-od) / dists < math.cos(math.pi / 4))
+            ratio = abs(-od) / dists
+            if rule == "gt":
+                return bool(ratio > math.cos(math.pi / 4))
+            threshold = {"cos40": math.cos(math.radians(40.0)), "cos50": math.cos(math.radians(50.0))}
+            return bool(ratio < threshold.get(rule, math.cos(math.pi / 4)))
         return False
     return bool(od < 0.0)
 
 
-def tangent_cone_margin(e, set_min, set_max, dexpr):
+def is_corner(e, set_min, set_max):
+    """every row of a multidimensional set strictly outside its bounds: the state at which :232 takes the corner branch"""
+    e, set_min, set_max = (np.atleast_1d(np.asarray(v, dtype=float)) for v in (e, set_min, set_max))
+    return bool(np.all(np.sign(e - set_min) == np.sign(e - set_max)))
+
+
+def tangent_cone_margin(e, set_min, set_max, dexpr, position_side=True):
     """Distance of one tangent-cone decision (either function above) from flipping, as the smallest of
     the quantities it thresholds: |e - bound -/+ 1e-12| of every row (the inside test), and - outside -
     the normalised |out_dir . de| (or the distance of the corner ratio from cos(pi/4)).  A diagnostic for
     the parity tests: two correct fp64 evaluations of de differ by ~1e-9 relative, so a decision with a
-    margin far above that cannot depend on which of them made it."""
+    margin far above that cannot depend on which of them made it.
+
+    `position_side=False` leaves the |e - bound| terms out: what remains is the margin of the quantities that hold a
+    derivative (out_dir . de, the corner ratio, de of a 1-D set), infinite where the decision read none of them.  Where
+    the set's expression is the state itself, e - bound is one exact fp64 subtraction in any correct evaluation and
+    only this side can differ between two of them."""
+    pos = (lambda *v: float(min(v))) if position_side else (lambda *v: float("inf"))
     e = np.atleast_1d(np.asarray(e, dtype=float))
     set_min = np.atleast_1d(np.asarray(set_min, dtype=float))
     set_max = np.atleast_1d(np.asarray(set_max, dtype=float))
@@ -525,16 +558,20 @@ def tangent_cone_margin(e, set_min, set_max, dexpr):
     le, ue = e - set_min, e - set_max
     if e.shape[0] == 1:
         inside = (set_min[0] - e[0] < 1e-12) and (e[0] - set_max[0] < 1e-12)
-        margin = min(abs(set_min[0] - e[0] - 1e-12), abs(e[0] - set_max[0] - 1e-12))
+        margin = pos(abs(set_min[0] - e[0] - 1e-12), abs(e[0] - set_max[0] - 1e-12))
         return float(margin if inside else min(margin, abs(dexpr[0])))
     inside = bool(np.all(le >= 1e-12) and np.all(ue <= 1e-12))
-    margin = float(min(np.abs(le - 1e-12).min(), np.abs(ue - 1e-12).min()))
+    margin = pos(np.abs(le - 1e-12).min(), np.abs(ue - 1e-12).min())
     if inside:
         return margin
     out_dir = (np.sign(le) + np.sign(ue)) / 2.0
+    if not position_side and not out_dir.any():
+        # (every row between its bounds, one of them within the 1e-12 margin: out_dir . de is an exact zero, "not going
+        # in" whatever de is)
+        return margin
     od = float(out_dir.dot(dexpr))
-    scale = (np.linalg.norm(dexpr) + 1e-10) * max(np.linalg.norm(out_dir), 1e-300)
-    margin = min(margin, float(np.abs(le).min()), float(np.abs(ue).min()), abs(od) / scale)
+    scale =(np.linalg.norm(dexpr) + 1e-10) * max(np.linalg.norm(out_dir), 1e-300)
+    margin = min(margin, pos(np.abs(le).min(), np.abs(ue).min()), abs(od) / scale)
     if bool(np.all(np.sign(le) == np.sign(ue))) and od < 0.0:
         margin = min(margin, abs(abs(od) / scale - math.cos(math.pi / 4)))
     return margin
@@ -544,10 +581,14 @@ def tangent_cone_margin(e, set_min, set_max, dexpr):
 # PseudoInverseController
 # ==========================================================================
 def pinv_solve_batch(spec, options, t, Q, X=None, Y=None, return_all_modes=False, margins_out=None, _wrong=None,
-                     cond_out=None, pinv_fn=None):
+                     cond_out=None, pinv_fn=None, deriv_margins_out=None, corner_out=None):
     """Literal PseudoInverseController: returns (dZ [B,n_state], mode [B]).
 
     dZ[:, :n_q] is robot_vel, the rest virtual_vel.
+
+    `margins_out` [B] (filled with inf by the caller) receives the smallest tangent_cone_margin of the decisions the scan
+    took up to the accepted mode, `deriv_margins_out` the same with the |e - bound| terms left out, `corner_out` [B] of
+    bool (False) whether one of those decisions met a multidimensional set at a corner.
 
     `cond_out` [B] (optional) receives, per instance, the SUM of the condition numbers of the matrices the reference's
     algorithm hands to its linear solver in the accepted mode (pseudo_inverse.py:92-105; the errors of successive solves add
@@ -566,11 +607,16 @@ def pinv_solve_batch(spec, options, t, Q, X=None, Y=None, return_all_modes=False
     rule (:162-185 in place of :222-252), "boundary_flipped" moves the 1e-12 margins of both cone functions to the
     other side of the bounds (the class docstring's reading, quirk D4), "multidim_loose" gives the multidimensional
     cone the 1-D function's inside test (quirk D5), "set_pushes_back" lets an active set drive its violated rows
-    back to the bound with its gain instead of only freezing them (quirk D2)."""
+    back to the bound with its gain instead of only freezing them (quirk D2).  For tests/test_cone_pins.py:
+    "corner_<rule>" hands <rule> to in_tangent_cone_multidim (the wrong corner rules listed there), "cone_1d_strict"
+    gives the 1-D cone the multidimensional function's inside test, "cone_eps_zero" sets the 1e-12 margins of both
+    cone functions to zero."""
+    corner_rule = _wrong[len("corner_"):] if _wrong is not None and _wrong.startswith("corner_") else None
     assert _wrong in (None, "no_S", "no_D1", "textbook_projection", "active_first", "cone_1d_rows", "boundary_flipped",
-                      "multidim_loose", "set_pushes_back"), _wrong
+                      "multidim_loose", "set_pushes_back", "cone_1d_strict", "cone_eps_zero") or (
+                          corner_rule in CORNER_RULES), _wrong
     pinv = dpinv if pinv_fn is None else pinv_fn
-    cone_eps = -1e-12 if _wrong == "boundary_flipped" else 1e-12
+    cone_eps = {"boundary_flipped": -1e-12, "cone_eps_zero": 0.0}.get(_wrong, 1e-12)
     opt = default_pinv_options(options)
     Q = np.atleast_2d(np.asarray(Q, dtype=float))
     B = Q.shape[0]
@@ -702,14 +748,19 @@ def pinv_solve_batch(spec, options, t, Q, X=None, Y=None, return_all_modes=False
                 smin = _num(a.set_min, m)
                 smax = _num(a.set_max, m)
                 if m == 1:
-                    good = in_tangent_cone_1d(e[0], smin[0], smax[0], dexpr[0], cone_eps)
+                    good = in_tangent_cone_1d(e[0], smin[0], smax[0], dexpr[0], cone_eps, _wrong == "cone_1d_strict")
                 elif _wrong == "cone_1d_rows":
                     good = all(in_tangent_cone_1d(e[k], smin[k], smax[k], dexpr[k]) for k in range(m))
                 else:
-                    good = in_tangent_cone_multidim(e, smin, smax, dexpr, cone_eps, _wrong == "multidim_loose")
+                    good = in_tangent_cone_multidim(e, smin, smax, dexpr, cone_eps, _wrong == "multidim_loose",
+                                                    corner_rule)
                 if margins_out is not None and modes[b] < 0:
                     # (every decision of the scan up to and including the accepted mode)
                     margins_out[b] = min(margins_out[b], tangent_cone_margin(e, smin, smax, dexpr))
+                if deriv_margins_out is not None and modes[b] < 0:
+                    deriv_margins_out[b] = min(deriv_margins_out[b], tangent_cone_margin(e, smin, smax, dexpr, False))
+                if corner_out is not None and modes[b] < 0 and m > 1:
+                    corner_out[b] |= is_corner(e, smin, smax)
                 if not good:
                     ok = False
                     break

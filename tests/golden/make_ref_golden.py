@@ -172,11 +172,72 @@ PLAN = [   # (fixture name, robot, case, B, input distribution, times)
     # round 4: atan2 / asin / acos / atan / tanh / fmin / fmax in task errors
     ("iiwa_heading", "iiwa", "heading", 64, "mixed", [0.0, 1.3]),
     ("ur5_qp_heading", "ur5", "qp_heading", 48, "interior", [0.7]),
+    # the tangent-cone tests at corners and bounds (tests/test_cone_pins.py): every corner of the limit box, rows on and
+    # next to a bound with the rest outside, the 1-D thresholds, a task-space box left through its corners
+    ("iiwa_stack_corner", "iiwa", "stack_corner", 320, "corner", [0.0]),
+    ("ur5_stack_corner", "ur5", "stack_corner", 192, "corner", [0.0]),
+    ("iiwa_sets1d_boundary", "iiwa", "sets1d_boundary", 192, "boundary", [0.0]),
+    ("iiwa_taskbox_corner", "iiwa", "taskbox_corner", 256, "interior_resolved", [0.0]),
 ]
 # offsets from a joint limit the "boundary" distribution plants (pseudo_inverse.py:222-252 thresholds e - bound
 # at 1e-12): exactly on the limit, either side of the 1e-12 margin, and up to 1e-6 away
 BOUNDARY_OFFSETS = [0.0, 5e-13, -5e-13, 1e-12, -1e-12, 2e-12, -2e-12, 1e-10, -1e-10, 1e-9, -1e-9, 1e-7, -1e-7,
                     1e-6, -1e-6]
+
+
+CORNER_PART_C = 64       # states of part C of the "corner" distribution (parts A and B: 2^n each)
+
+
+def corner_states(lo, hi, B, rng):
+    """The "corner" distribution: states at which the multidimensional tangent cone of the joint-limit box takes its
+    corner branch (pseudo_inverse.py:229-245: every row outside its bounds), and their neighbours on the bounds.
+      part A  every corner of the box once: 2^n sign patterns, each joint beyond its limit by 10**uniform(-4, -1);
+      part B  every corner once more, one joint per state replaced by limit + o;
+      part C  CORNER_PART_C states of random corners, with two (first half) and three (second half) joints planted.
+    o runs through BOUNDARY_OFFSETS, one step per planted joint - in part B on the lower and the upper limit in turn,
+    in part C on a limit drawn per joint: a row sits on or next to its bound, sign(0) enters out_dir, and whether the
+    state is a corner hangs on 5e-13.  In every fourth
+    state of part B and every second of part C the joints that are not planted lie INSIDE their limits: with one joint
+    far outside, the inside test (:222-228) is false whatever its margin, so only there do its 1e-12 thresholds decide
+    anything.  Those states take their offsets, in a cycle of their own, from the seven within 2e-12 of the limit, and
+    in part C their first planted joint sits exactly on a limit."""
+    n = len(lo)
+    nA = 2 ** n
+    assert B == 2 * nA + CORNER_PART_C, (B, n)
+
+    def outside(patterns):
+        beyond = 10.0 ** rng.uniform(-4.0, -1.0, size=(len(patterns), n))
+        up = (patterns[:, None] >> np.arange(n)) & 1
+        return np.where(up == 1, hi + beyond, lo - beyond)
+    every = np.arange(nA)
+    Q = np.vstack([outside(every), outside(every), outside(rng.integers(0, nA, size=CORNER_PART_C))])
+    near = BOUNDARY_OFFSETS[:7]
+    steps = {False: 0, True: 0}
+    for b in range(nA, B):
+        if b < 2 * nA:
+            count, rest_inside = 1, b % 4 == 3
+        else:
+            count, rest_inside = (2 if b - 2 * nA < CORNER_PART_C // 2 else 3), b % 2 == 1
+        planted = rng.choice(n, size=count, replace=False)
+        if rest_inside:
+            Q[b] = rng.uniform(0.9 * lo, 0.9 * hi)
+        offsets = near if rest_inside else BOUNDARY_OFFSETS
+        for k, j in enumerate(planted):
+            if count > 1 and rest_inside and k == 0:
+                # (part C: the first planted joint of such a state sits exactly ON a limit - sign(0) beside other rows
+                # next to their bounds)
+                Q[b, j] = lo[j] if rng.random() < 0.5 else hi[j]
+                continue
+            step = steps[rest_inside]
+            if count == 1:
+                lower = (step // len(offsets)) % 2 == 0
+            else:
+                # (consecutive offsets have opposite signs: on one limit two planted joints would never both be outside)
+                lower = rng.random() < 0.5
+            lim = lo[j] if lower else hi[j]
+            Q[b, j] = lim + offsets[step % len(offsets)]
+            steps[rest_inside] = step + 1
+    return Q
 
 
 def inputs(chain, T_fk, B, dist, seed):
@@ -185,6 +246,11 @@ def inputs(chain, T_fk, B, dist, seed):
     rng = np.random.default_rng(seed)
     if dist == "interior":
         Q = rng.uniform(0.9 * lo, 0.9 * hi, size=(B, len(lo)))
+    elif dist == "interior_resolved":
+        B = 2 * B               # candidates: main() keeps the first half that pass `resolved`
+        Q = rng.uniform(0.9 * lo, 0.9 * hi, size=(B, len(lo)))
+    elif dist == "corner":
+        Q = corner_states(lo, hi, B, rng)
     elif dist == "narrow":
         # around sets drawn at 0.3 of the joint ranges (pin_skills.sets_per_joint): each joint outside with p = 1/6
         Q = rng.uniform(0.36 * lo, 0.36 * hi, size=(B, len(lo)))
@@ -204,6 +270,24 @@ def inputs(chain, T_fk, B, dist, seed):
         T = numeric_fk(T_fk, len(lo), Qd[b])
         Y[b, :3], Y[b, 3:] = T[:3, 3], quat_from_matrix(T[:3, :3])
     return Q, Y
+
+
+RESOLVED = 1e-13         # a tenth of the floor of every parity bound (tests/tolerances.py: max(1e-12, 8 u kappa))
+
+
+def resolved(ctrl, t, q):
+    """Does the reference's own answer at q survive the last bit of q?  Where the box of `taskbox` is active in all its
+    rows the task behind it is projected through N = I - pinv(J) J of its OWN Jacobian: the velocity is the damping
+    residual lam J'(J J' + lam)^-2 des, formed by cancellation from terms of the size of pinv(J) des, and carries their
+    rounding whatever the condition number of J J' + lam says.  A state whose answer moves by more than RESOLVED
+    (relative to 1 + max|dq|, the measure of the parity rule) when every joint angle moves by one ulp either way cannot
+    be held to that rule by any two evaluations, the reference's and the oracle's included: it is not kept."""
+    dq = ctrl.solve(t, q)[0].full().reshape(-1)
+    worst = 0.0
+    for towards in (np.inf, -np.inf):
+        moved = ctrl.solve(t, np.nextafter(q, towards))[0].full().reshape(-1)
+        worst = max(worst, np.abs(moved - dq).max() / (1.0 + np.abs(dq).max()))
+    return worst < RESOLVED
 
 
 def check_reference_held_outputs():
@@ -418,6 +502,13 @@ def main():
         if built["controller"] == "pinv":
             ctrl = cc.PseudoInverseController(skill_spec=spec, options=dict(built["options"]))
             ctrl.setup_problem_functions()
+            if dist == "interior_resolved":
+                keep = np.array([resolved(ctrl, times[0], q) for q in Q])
+                assert not ny and not nx and keep.sum() >= B, (name, int(keep.sum()))
+                print("%-26s %d of the first %d candidates not resolved by the reference's own run, left out" % (
+                    name, int((~keep[:np.nonzero(keep)[0][B - 1] + 1]).sum()), np.nonzero(keep)[0][B - 1] + 1))
+                Q = Q[keep][:B]
+                out[name + "_Q"] = Q
             dq = np.zeros((len(times), B, n))
             mode = np.zeros((len(times), B), dtype=np.int32)
             for ti, t in enumerate(times):

@@ -371,7 +371,27 @@ def qp_heading(env):
     return dict(spec=spec, controller="qp", options={}, ny=0)
 
 
+TASKBOX_MIN, TASKBOX_MAX, TASKBOX_TARGET = (0.3, -0.1, 0.4), (0.5, 0.1, 0.6), (0.45, 0.3, 0.2)
+
+
+def taskbox(env):
+    """a three-row box on the tool position (a multidimensional SetConstraint on T_fk(q)[:3, 3], the wall sets of
+    ur5_moe2016_example2.ipynb cell 6 taken as one set) in front of a position task whose target lies outside the box:
+    rows of the set's Jacobian are no unit vectors, and a state outside the box in all three coordinates leaves it
+    through a corner (pseudo_inverse.py:229-245)"""
+    cc, s = env.cc, _syms(env)
+    T = env.T_fk(s["q"])
+    box = cc.SetConstraint(label="tool_position", expression=T[:3, 3], set_min=np.array(TASKBOX_MIN),
+                           set_max=np.array(TASKBOX_MAX), priority=0)
+    reach = cc.EqualityConstraint(label="reach_target", expression=T[:3, 3] - np.array(TASKBOX_TARGET), gain=2.0,
+                                  constraint_type="soft", priority=1)
+    spec = cc.SkillSpecification(label="taskbox", time_var=s["t"], robot_var=s["q"], robot_vel_var=s["dq"],
+                                 constraints=[reach, box])
+    return dict(spec=spec, controller="pinv", options={"multidim_sets": True}, ny=0)
+
+
 CASES = {
+    "stack_corner": stack_const, "sets1d_boundary": stack_sets1d, "taskbox_corner": taskbox,
     "heading": heading, "qp_heading": qp_heading,
     "two_frames": two_frames, "qp_two_virtual": qp_two_virtual, "sets_per_joint": sets_per_joint,
     "stack_boundary": stack_const, "qp_wall": qp_wall,

@@ -12,30 +12,13 @@ import functools
 import numpy as np
 import pytest
 
-import casclik_amd as cc
 import exact_yardstick as ey
+import kernel_variants
 from tolerances import ILL_POSED, LAST, MAX_LEFT_OUT, MODE_MARGIN, U, pinv_close_structural, rel_err, rtol_from_cond
 
 pytestmark = pytest.mark.gpu
 
-_SWITCHES = ("CLIK_LANES", "CLIK_JIT_VALUES", "CLIK_MODE_PARALLEL", "CLIK_FORCE_DYNAMIC")
-# the switches that make a kernel variant serve a SMALL batch of the config-3 family (tests/test_capi.py holds the
-# whole table); "quadv" is the library's own choice for a single-mode skill with forward kinematics
-_ENV = {
-    "team4": {"CLIK_JIT_VALUES": "0"},
-    "team4v": {},
-    "mp2": {"CLIK_LANES": "1", "CLIK_JIT_VALUES": "0"},
-    "lane": {"CLIK_LANES": "1", "CLIK_JIT_VALUES": "0", "CLIK_MODE_PARALLEL": "0"},
-    "lanev": {},                # (the library's choice beyond the team kernel's 16384 instances: see _PAD)
-    "quadv": {},
-    "dynamic": {"CLIK_FORCE_DYNAMIC": "1"},
-    "built-in": {},             # (a skill outside every shape-specialised family: the dynamic kernel by the library's choice)
-}
-# "lanev" serves the family only with the numbers compiled in, which the controller asks for when the team kernel is the
-# skill's first choice - no switch makes it serve 257 instances.  Its cases run the smallest batch the library gives
-# it, 16384 instances of the same distribution in front of the case's 257 (so the case's rows are the last four waves
-# and the ragged tail), and compare those 257.
-_PAD = {"lanev": 16384}
+_PAD = kernel_variants.PAD
 
 
 @functools.lru_cache(maxsize=None)
@@ -57,18 +40,7 @@ def _reference(case, literal=False):
 def _controller(case, variant, monkeypatch):
     """the controller of the case's skill with the switches of `variant`; asserts that this variant serves the batch"""
     spec, opts, _, Q, _ = case.build()
-    for name in _SWITCHES:
-        monkeypatch.delenv(name, raising=False)
-    for name, value in _ENV[variant].items():
-        monkeypatch.setenv(name, value)
-    ctrl = cc.PseudoInverseController(skill_spec=spec, options=None if opts is None else dict(opts))
-    ctrl.setup_problem_functions()
-    served = ctrl.kernel_variant(len(Q) + _PAD.get(variant, 0))
-    if variant in ("dynamic", "built-in"):
-        assert ctrl.kernel_name == "dynamic" and served == "dynamic/dynamic", served
-    else:
-        assert ctrl.kernel_name != "dynamic" and served.endswith("/" + variant), served
-    return ctrl
+    return kernel_variants.controller(spec, opts, len(Q), variant, monkeypatch)
 
 
 def _ticks(case, ctrl, pad=None):
